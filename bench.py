@@ -11,6 +11,12 @@ Workload (default = BASELINE.json configs[2], the one the metric is quoted on): 
 N > 1: frames shard one-per-GPU (camera k yawed; --frames-per-rank K: K per GPU, gradients accumulated), then ONE gradient
 exchange per step over RCCL -- weak scaling, value = P * frames / s summed over ranks.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline (metric, value, unit, ms_per_step, ...).  --full adds
+everything else, as untimed extras after the timed steps: scene statistics, per-stage times, roofline / vector-issue figures, the
+CPU-oracle baseline, the training-step pattern, the camera-inside-the-scene and `-r 4` operating points, and for N > 1 the
+exchange report (exposed stalls, the collectives timed alone).  --dump-outputs DIR writes what the last timed step handed its caller
+(maps, radii, parameter gradients) as float32 .npy files, at fixed seeded samples of pixels and Gaussians (dump_outputs).
 """
 import argparse
 import json
@@ -67,6 +73,11 @@ def parse():
                     help="gradient accumulation: K frames (cameras) per rank and step, ONE gradient exchange per step -- the colour gradients of "
                          "frame j travel while frame j + 1 is computed (factored exchange); value counts all K * N frames")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-oracle work for the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: scene statistics, stage times, roofline, CPU baseline, training-step and other "
+                         "operating points, the N > 1 exchange report (--no-cpu-baseline / --no-train-step drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, seeded samples of pixels and Gaussians, < 64 MB)")
     a = ap.parse_args()
     custom = any(v is not None for v in (a.gaussians, a.width, a.height)) or (a.no_aux and a.config is None)
     P, W, H, aux, label = CONFIGS[a.config or "c3"]
@@ -90,6 +101,42 @@ def algorithmic_bytes(P, V, D, npx, deg):
         "blend_bwd": D * 76 + D * 72 * 2 + npx * (60 + 40),
         "preprocess_bwd": V * (232 + 36 + 72 + 240),
     }
+
+
+DUMP_PIXELS = 1 << 18      # pixels kept per map (every pixel of a smaller frame)
+DUMP_ROWS = 1 << 16        # Gaussians kept per per-Gaussian array (every row of a smaller scene)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_index(n, keep, seed):
+    """Sorted positions of a fixed seeded sample of `keep` out of `n` (None: keep all); depends on (n, keep, seed) only."""
+    if n <= keep:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+
+
+def dump_outputs(out_dir, npx, P, maps, rows, whole=None):
+    """--dump-outputs: DIR/<name>.npy in float32 for every output the caller of the timed path received in the last step, so two builds
+    can be compared output for output.  `maps` are images ([..., H, W], npx = H * W pixels) -> [channels, pixels of the sample];
+    `rows` are per-Gaussian arrays ([P, ...]) -> [Gaussians of the sample, ...]; `whole` are small arrays kept as they are.  The samples
+    are the same for every map / array of a run and for every run with the same sizes."""
+    pix, row = _dump_index(npx, DUMP_PIXELS, seed=0), _dump_index(P, DUMP_ROWS, seed=1)
+    arrays = {}
+    for name, t in maps.items():
+        t = t.detach().reshape(-1, npx)
+        arrays[name] = t if pix is None else t[:, pix.to(t.device)]
+    for name, t in rows.items():
+        t = t.detach()
+        arrays[name] = t if row is None else t[row.to(t.device)]
+    arrays.update({name: t.detach().reshape(-1) for name, t in (whole or {}).items()})
+    arrays = {name: t.float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} B, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def profiled(kind, args):
@@ -598,49 +645,57 @@ def train_step_main(args):
             t.grad = None
         m = fn(cam, pc, bg, weights)
         m["loss"].backward()
-        return m
+        # (detached: what the caller keeps of a step must not keep its autograd graph alive into the next one)
+        return {k: v.detach() if torch.is_tensor(v) else [x.detach() for x in v] for k, v in m.items()}
     for _ in range(max(args.warmup, 1)):
         m = step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        m = step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
-    # per-stage ms on extra steps (HIP event pairs recorded by the library on the launch stream)
-    iters = 5
-    lib.sr_set_stage_timing(1)
-    for _ in range(iters):
-        step()
-    torch.cuda.synchronize()
-    st = _lib.stage_stats(); lib.sr_set_stage_timing(0)
-    stage_ms = {k: round(v / iters, 4) for k, (v, n) in st.items() if n}
-    # scene statistics
-    with torch.no_grad():
-        from diff_surfel_rasterization import _C
-        e = torch.empty(0, device=dev)
-        D, _, _, radii0, *_ = _C.rasterize_gaussians(bg, params["means3D"].detach(), e, params["opacities"].detach(), params["scales"].detach(), params["rotations"].detach(),
-                                                     1.0, e, cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), H, W,
-                                                     params["shs"].detach(), deg, cam.camera_center, False, False)
-        V = int((radii0 > 0).sum())
-    ref_ms = None
-    if not args.no_train_step:   # the reference's eight calls beside it (untimed extra)
-        for _ in range(2):
-            step(reference_pattern)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        for _ in range(3):
-            step(reference_pattern)
-        torch.cuda.synchronize(); ref_ms = round((time.perf_counter() - t0) * 1e3 / 3, 3)
-    prof_args = argparse.Namespace(**{**vars(args), "tag": "c3"})
-    roof = train_step_roofline(prof_args, stage_ms, D, V, n_classes=5)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, H * W, P,
+                     maps={**{k: m[k] for k in ("render", "render_semantics", "rend_dist", "rend_normal")}, "class_dist": torch.stack(m["class_dist"])},
+                     rows={"grad_" + k: t.grad for k, t in params.items()}, whole={"loss": m["loss"]})
+    del m
     out = {"metric": "Msplats/s, one training view fwd+bwd (9-channel render + 5 per-class distortion maps on one plan) @1920x1080, 3M Gaussians",
            "value": round(P / ms / 1e3, 3), "unit": "Msplats/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "train_step: the rasterizer work of one late training iteration of the reference [train.py:84-109] on the C3 scene -- render + "
                                   "render_semantic + five class-filtered rend_dist maps -- as render_train_view (one K1, one binning, one K8); incl. allmap post-processing and loss kernels",
-                      "baseline_config": "train_step", "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": V, "duplicates_D": int(D), "parallelism": "single GPU"},
-           "roofline": roof, "stage_ms": stage_ms, "stage_ms_sum": round(sum(stage_ms.values()), 4),
-           "reference_8_calls_ms": ref_ms, "speedup_over_the_reference_call_pattern": None if not ref_ms else round(ref_ms / ms, 2)}
+                      "baseline_config": "train_step", "gaussians": P, "width": W, "height": H, "sh_degree": deg, "parallelism": "single GPU"}}
+    if args.full:
+        # per-stage ms on extra steps (HIP event pairs recorded by the library on the launch stream)
+        iters = 5
+        lib.sr_set_stage_timing(1)
+        for _ in range(iters):
+            step()
+        torch.cuda.synchronize()
+        st = _lib.stage_stats(); lib.sr_set_stage_timing(0)
+        stage_ms = {k: round(v / iters, 4) for k, (v, n) in st.items() if n}
+        # scene statistics
+        with torch.no_grad():
+            from diff_surfel_rasterization import _C
+            e = torch.empty(0, device=dev)
+            D, _, _, radii0, *_ = _C.rasterize_gaussians(bg, params["means3D"].detach(), e, params["opacities"].detach(), params["scales"].detach(), params["rotations"].detach(),
+                                                         1.0, e, cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), H, W,
+                                                         params["shs"].detach(), deg, cam.camera_center, False, False)
+            V = int((radii0 > 0).sum())
+        ref_ms = None
+        if not args.no_train_step:   # the reference's eight calls beside it (untimed extra)
+            for _ in range(2):
+                step(reference_pattern)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(3):
+                step(reference_pattern)
+            torch.cuda.synchronize(); ref_ms = round((time.perf_counter() - t0) * 1e3 / 3, 3)
+        prof_args = argparse.Namespace(**{**vars(args), "tag": "c3"})
+        roof = train_step_roofline(prof_args, stage_ms, D, V, n_classes=5)
+        out["config"].update(visible=V, duplicates_D=int(D))
+        out.update({"roofline": roof, "stage_ms": stage_ms, "stage_ms_sum": round(sum(stage_ms.values()), 4),
+                    "reference_8_calls_ms": ref_ms, "speedup_over_the_reference_call_pattern": None if not ref_ms else round(ref_ms / ms, 2)})
     print(json.dumps(out), flush=True)
 
 
@@ -706,13 +761,13 @@ def main():
 
     exchange_log = {"ms": 0.0, "bytes": 0, "calls": 0, "early_starts": 0}
 
-    def frame(j):   # one frame: operator forward + backward; parameter gradients accumulate in the leaves
+    def frame(j):   # one frame: operator forward + backward; parameter gradients accumulate in the leaves -> (color, radii, allmap)
         color, radii, allmap = rasterizers[j](means3D=params["means3D"], means2D=means2D, shs=params["shs"],
                                               opacities=params["opacities"], scales=params["scales"], rotations=params["rotations"])
         torch.autograd.backward([color, allmap], [dc, da])
-        return radii
+        return color.detach(), radii, allmap.detach()
 
-    def step():     # K frames per rank, then (N > 1) ONE gradient exchange
+    def step():     # K frames per rank, then (N > 1) ONE gradient exchange -> the K frames' outputs
         for t in leaves:
             t.grad = None
         if multi and args.exchange == "factored":
@@ -720,16 +775,16 @@ def main():
             # frame's kernels) + local expansion of all K * N views; the other 40 B/Gaussian: one all-reduce -- inside the last
             # backward for K = 1 (every gradient leaves backward summed over the ranks), after the K-th frame otherwise
             with factored_sh_exchange(all_campos=all_campos, reduce_all=K == 1, frames_per_rank=K) as ex:
-                for j in range(K):
-                    radii = frame(j)
+                outs = [frame(j) for j in range(K)]
                 if K > 1:
                     ex.finish([t.grad for t in (leaves[0], leaves[2], leaves[3], leaves[4])])
             exchange_log["ms"] += ex.exchange_ms; exchange_log["bytes"] += ex.bytes_sent; exchange_log["calls"] += ex.calls
             exchange_log["early_starts"] += ex.early_starts
         else:
-            seen = None
+            seen, outs = None, []
             for j in range(K):
-                radii = frame(j)
+                outs.append(frame(j))
+                radii = outs[-1][1]
                 seen = (radii > 0) if seen is None else (seen | (radii > 0))   # (the rows this rank's frames reached)
             if multi and args.exchange == "compacted":
                 t0 = time.perf_counter()
@@ -741,30 +796,31 @@ def main():
                 allreduce_gradients([t.grad for t in leaves[:5]])   # 232 B/Gaussian, one collective over the flat buffer
                 exchange_log["ms"] += (time.perf_counter() - t0) * 1e3; exchange_log["calls"] += 1
                 exchange_log["bytes"] += sum(t.grad.numel() * 4 for t in leaves[:5])
-        return radii
+        return outs
 
-    # scene statistics (outside the timed region)
-    with torch.no_grad():
-        e = torch.empty(0, device=dev)
-        D, _, _, radii0, *_ = _C.rasterize_gaussians(settings.bg, params["means3D"].detach(), e, params["opacities"].detach(),
-                                                     params["scales"].detach(), params["rotations"].detach(), 1.0, e,
-                                                     settings.viewmatrix, settings.projmatrix, settings.tanfovx, settings.tanfovy,
-                                                     H, W, params["shs"].detach(), deg, settings.campos, False, False)
-        V = int((radii0 > 0).sum().item())
-    del radii0
+    if args.full:
+        # scene statistics (outside the timed region)
+        with torch.no_grad():
+            e = torch.empty(0, device=dev)
+            D, _, _, radii0, *_ = _C.rasterize_gaussians(settings.bg, params["means3D"].detach(), e, params["opacities"].detach(),
+                                                         params["scales"].detach(), params["rotations"].detach(), 1.0, e,
+                                                         settings.viewmatrix, settings.projmatrix, settings.tanfovx, settings.tanfovy,
+                                                         H, W, params["shs"].detach(), deg, settings.campos, False, False)
+            V = int((radii0 > 0).sum().item())
+        del radii0
 
-    # what the blend kernels execute on this scene (device counters of one forward, outside the timed region)
-    counters = torch.zeros(16, dtype=torch.int64, device=dev)
-    with torch.no_grad():
-        GaussianRasterizer(settings, blend_counters=counters)(means3D=params["means3D"], means2D=means2D, shs=params["shs"],
-                                                              opacities=params["opacities"], scales=params["scales"], rotations=params["rotations"])
-    torch.cuda.synchronize()
-    st = counters.tolist()
-    blend_counts = {"staged_entries_D_eff": int(st[0]), "entries_after_quadrant_cull": int(st[1]), "quadrant_tests": int(st[2]),
-                    "quadrant_tests_with_a_hit": int(st[3]), "contributing_pairs": int(st[4]), "entries_with_a_hit": int(st[7]),
-                    "cell_pairs_4x4": int(st[8]), "row_mapping_steps": int(st[9]),
-                    "cell_pairs_4x4_octagon_culling": int(st[10]), "row_mapping_steps_octagon_culling": int(st[11]),
-                    "cell_pairs_4x4_box_culling": int(st[12]), "row_mapping_steps_box_culling": int(st[13]), "box_culling_dropped_hits": int(st[14])}
+        # what the blend kernels execute on this scene (device counters of one forward, outside the timed region)
+        counters = torch.zeros(16, dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            GaussianRasterizer(settings, blend_counters=counters)(means3D=params["means3D"], means2D=means2D, shs=params["shs"],
+                                                                  opacities=params["opacities"], scales=params["scales"], rotations=params["rotations"])
+        torch.cuda.synchronize()
+        st = counters.tolist()
+        blend_counts = {"staged_entries_D_eff": int(st[0]), "entries_after_quadrant_cull": int(st[1]), "quadrant_tests": int(st[2]),
+                        "quadrant_tests_with_a_hit": int(st[3]), "contributing_pairs": int(st[4]), "entries_with_a_hit": int(st[7]),
+                        "cell_pairs_4x4": int(st[8]), "row_mapping_steps": int(st[9]),
+                        "cell_pairs_4x4_octagon_culling": int(st[10]), "row_mapping_steps_octagon_culling": int(st[11]),
+                        "cell_pairs_4x4_box_culling": int(st[12]), "row_mapping_steps_box_culling": int(st[13]), "box_culling_dropped_hits": int(st[14])}
 
     def sync():
         if multi:
@@ -801,7 +857,7 @@ def main():
             rccl_info["warning"] = msg
             if rank == 0:
                 print(f"bench.py: warning: {msg}", file=sys.stderr, flush=True)
-        par.STALLS.enabled = True   # compute-stream stalls at the collectives' wait points = the exposed part of the exchange
+        par.STALLS.enabled = args.full   # compute-stream stalls at the collectives' wait points = the exposed part of the exchange
         if args.exchange == "factored":
             # one untimed trial step of the factored exchange.  Only a failure of the COLLECTIVE LAYER (a backend that lacks
             # all_gather_into_tensor, a communicator error: torch.distributed raises DistBackendError / NotImplementedError, on every
@@ -838,16 +894,17 @@ def main():
     sync()
     par.STALLS.drain_ms()
     exchange_log.update(ms=0.0, bytes=0, calls=0, early_starts=0)
-    # Timed region: HIP events (recorded by the library on the launch stream) around the DOMINANT kernel only -- the blend backward,
-    # the kernel of `roofline` -- because every event record costs ~5 us of stream time (tools/step_timeline.py: bracketing both blend
-    # kernels cost 30 us per step, all nine stages ~1.4 %).  Every other stage is timed right after the timed region, on extra steps.
-    blend_mask = 1 << list(_lib.SR_STAGE_NAMES).index("blend_bwd")
-    lib.sr_set_stage_timing(2 * blend_mask)
+    # Timed region.  --full: HIP events (recorded by the library on the launch stream) around the DOMINANT kernel only -- the blend
+    # backward, the kernel of `roofline` -- because every event record costs ~5 us of stream time (tools/step_timeline.py: bracketing both
+    # blend kernels cost 30 us per step, all nine stages ~1.4 %).  Every other stage is timed right after the timed region, on extra steps.
+    if args.full:
+        blend_mask = 1 << list(_lib.SR_STAGE_NAMES).index("blend_bwd")
+        lib.sr_set_stage_timing(2 * blend_mask)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
-        step()
+        outs = step()
         marks[k + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
@@ -856,24 +913,34 @@ def main():
     par.STALLS.enabled = False
     per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     pct = lambda q: round(per_step[min(len(per_step) - 1, int(q * len(per_step)))], 4)
-    stats = _lib.stage_stats()
-    lib.sr_set_stage_timing(1)
-    for _ in range(min(args.steps, 5)):
-        step()
-    sync()
-    stats_all = _lib.stage_stats()
-    lib.sr_set_stage_timing(0)
-    stats = {k: (stats[k] if stats[k][1] else stats_all[k]) for k in stats_all}
+    if args.dump_outputs and rank == 0:   # the last timed step's outputs, before any extra step overwrites the gradients
+        names = ["color", "radii", "allmap"]
+        tag = (lambda j: "") if K == 1 else (lambda j: f"_frame{j}")
+        dump_outputs(args.dump_outputs, W * H, P,
+                     maps={names[i] + tag(j): o[i] for j, o in enumerate(outs) for i in (0, 2)},
+                     rows={**{"radii" + tag(j): o[1] for j, o in enumerate(outs)},
+                           **{"grad_" + n: t.grad for n, t in zip(["means3D", "shs", "opacities", "scales", "rotations", "means2D"], leaves)}})
+    del outs
+    if args.full:
+        stats = _lib.stage_stats()
+        lib.sr_set_stage_timing(1)
+        for _ in range(min(args.steps, 5)):
+            step()
+        sync()
+        stats_all = _lib.stage_stats()
+        lib.sr_set_stage_timing(0)
+        stats = {k: (stats[k] if stats[k][1] else stats_all[k]) for k in stats_all}
     exchange_detail = None
     if multi:
-        mine = torch.tensor([elapsed / args.steps * 1e3, exposed_ms], device=dev, dtype=torch.float64)
-        allr = torch.empty(2 * world, device=dev, dtype=torch.float64)
-        dist.all_gather_into_tensor(allr, mine)
-        allr = allr.view(world, 2).tolist()
-        exchange_detail = {"per_rank_ms_per_step": [round(a, 4) for a, _ in allr],
-                           "exposed_ms_per_step_per_rank": [round(b, 4) for _, b in allr],
-                           "exposed_definition": "time rank r's compute stream stood still at the collectives' wait points (event pairs around work.wait()), per step"}
-        exchange_detail["isolated_collectives"] = isolated_collectives(P, world, dev, args.exchange)
+        if args.full:
+            mine = torch.tensor([elapsed / args.steps * 1e3, exposed_ms], device=dev, dtype=torch.float64)
+            allr = torch.empty(2 * world, device=dev, dtype=torch.float64)
+            dist.all_gather_into_tensor(allr, mine)
+            allr = allr.view(world, 2).tolist()
+            exchange_detail = {"per_rank_ms_per_step": [round(a, 4) for a, _ in allr],
+                               "exposed_ms_per_step_per_rank": [round(b, 4) for _, b in allr],
+                               "exposed_definition": "time rank r's compute stream stood still at the collectives' wait points (event pairs around work.wait()), per step"}
+            exchange_detail["isolated_collectives"] = isolated_collectives(P, world, dev, args.exchange)
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
@@ -881,68 +948,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = P * world * K * args.steps / elapsed / 1e6
-        npx = W * H
-        ab = algorithmic_bytes(P, V, D, npx, deg)
-        stage_ms = {k: (ms / n if n else None) for k, (ms, n) in stats.items()}
-        groups = {"preprocess": ["preprocess"], "binning": ["depth_sort", "scan", "expand_x", "expand_y", "ranges"],
-                  "blend_fwd": ["blend_fwd"], "blend_bwd": ["blend_bwd"], "preprocess_bwd": ["preprocess_bwd"]}
-        group_ms = {k: sum(stage_ms[s] or 0.0 for s in v) for k, v in groups.items()}
-        dominant = max(("blend_fwd", "blend_bwd"), key=lambda k: group_ms[k])  # the north-star kernels
-        ach = ab[dominant] / (group_ms[dominant] * 1e-3) / 1e9 if group_ms[dominant] else None
-        blend_ms = group_ms["blend_fwd"] + group_ms["blend_bwd"]
-        blend_gbs = (ab["blend_fwd"] + ab["blend_bwd"]) / (blend_ms * 1e-3) / 1e9 if blend_ms else None
-        kernels_ms = sum(group_ms.values())
-        dom_kernel = "render_backward_kernel" if dominant == "blend_bwd" else "render_forward_kernel"
-        traffic, traffic_src = pmc_traffic(dom_kernel, args)
-        # the streaming kernels against what streaming kernels reach on this pool's boxes (read 6.5, copy 5.0-5.9 TB/s measured; 8 is the vendor peak)
-        ceiling = measured_ceiling()
-        hbm_bound = {}
-        for stage, kern in (("preprocess", "preprocess_forward_kernel"), ("preprocess_bwd", "preprocess_backward_kernel")):
-            t, _ = pmc_traffic(kern, args)
-            if t and group_ms[stage]:
-                gbs = t / (group_ms[stage] * 1e-3) / 1e9
-                hbm_bound[kern] = {"traffic_bytes_per_launch": int(t), "ms": round(group_ms[stage], 4), "achieved_GBs": round(gbs, 1), "frac_of_peak": round(gbs / HBM_PEAK_GBS, 4),
-                                   "frac_of_measured_copy_ceiling": None if not ceiling else round(gbs / 1e3 / ceiling["copy"], 4)}
-        # FP32-VALU view of the same two kernels (SURVEY 8d "algorithmic flops": 60 fwd + 200 bwd per tested pair).  K7 walks
-        # exactly the (entry, quadrant) pairs K6 recorded, so one set of counters serves both.
-        lane_tests = blend_counts["quadrant_tests"] * 64
-        useful = blend_counts["contributing_pairs"] * 260 / (blend_ms * 1e-3) / 1e12 if blend_ms else None
-        issued = lane_tests * 260 / (blend_ms * 1e-3) / 1e12 if blend_ms else None
-        # which mapping the forward blend ran (the device's rule, csrc/render.hip render_forward_auto_kernel: rows below 6.5 duplicates per
-        # visible Gaussian; the A/B switches force one) and the lanes IT issued: 64 per wave step of the row mapping (counted with the
-        # octagon-vs-cell culling the kernel uses), 64 per quadrant test otherwise.  K7 always walks quadrants.
-        rows_run = True if args.row_mapped else (False if args.quadrant_mapped else 2 * D < 13 * V)
-        fwd_lane_tests = (blend_counts["row_mapping_steps_octagon_culling"] if rows_run else blend_counts["quadrant_tests"]) * 64
-        valu = {"peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s", "flop_per_pair": 260, **blend_counts, "lane_tests": lane_tests,
-                "lane_utilisation": round(blend_counts["contributing_pairs"] / lane_tests, 4) if lane_tests else None,
-                "forward_mapping": "16-lane rows on independent entries" if rows_run else "one entry on 64 lanes (8x8 quadrants)",
-                "forward_lane_utilisation": round(blend_counts["contributing_pairs"] / fwd_lane_tests, 4) if fwd_lane_tests else None,
-                "backward_lane_utilisation": round(blend_counts["contributing_pairs"] / (blend_counts["quadrant_tests_with_a_hit"] * 64), 4) if blend_counts["quadrant_tests_with_a_hit"] else None,
-                "issued": None if issued is None else round(issued, 2), "issued_frac": None if issued is None else round(issued / FP32_VALU_PEAK_TFLOPS, 4),
-                "useful": None if useful is None else round(useful, 2), "useful_frac": None if useful is None else round(useful / FP32_VALU_PEAK_TFLOPS, 4),
-                "issue_roof": {"render_forward_kernel": valu_issue_roof("render_forward_kernel", group_ms["blend_fwd"], args),
-                               "render_backward_kernel": valu_issue_roof("render_backward_kernel", group_ms["blend_bwd"], args, blend_counts["entries_with_a_hit"])},
-                "note": "issued = 64 lanes x quadrant tests, useful = pairs that contribute.  Neither memory (traffic ~ algorithmic bytes at a fifth "
-                        "of the HBM rate) nor the number of resident waves bounds the blend kernels (a fourth wave per SIMD, built for the two-pixel K7, "
-                        "changes nothing): they run at issue_roof.*.datasheet_issue_frac of the rate the vector unit would reach if every instruction "
-                        "were a two-cycle VOP2 and at issue_roof.*.fitted_issue_cost_frac of the rate their actual instruction forms allow (DPP, "
-                        "transcendentals, lane swaps, three-source / SGPR-source VOP3 at their measured throughput costs) -- the second binds (DESIGN.md 4)",
-                "D_eff_blend_bytes": blend_counts["staged_entries_D_eff"] * 296 + npx * 160}
-        # The same fractions with the list entries the blend kernels actually stage (D_eff: what lies behind a tile's saturation
-        # point is never loaded) in place of all D duplicates: the D-based figures count bytes no kernel touches -- a factor of two
-        # on the 4K scene.
-        d_eff = blend_counts["staged_entries_D_eff"]
-        ab_eff = {"blend_fwd": d_eff * 76 + npx * 60, "blend_bwd": d_eff * 76 + d_eff * 72 * 2 + npx * (60 + 40)}
-        frac_eff = ab_eff[dominant] / (group_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS if group_ms[dominant] else None
-        blend_frac_eff = (ab_eff["blend_fwd"] + ab_eff["blend_bwd"]) / (blend_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if blend_ms else None
-        # counter traffic of BOTH blend kernels against the algorithmic bytes -- the D-based figure of SURVEY 8(d) and the one computed on
-        # the entries the kernels actually stage (D_eff): the second is the honest "how many bytes per byte needed" ratio
-        traffic_ratios = {}
-        for stage, kern in (("blend_fwd", "render_forward_kernel"), ("blend_bwd", "render_backward_kernel")):
-            t, _ = pmc_traffic(kern, args)
-            if t:
-                traffic_ratios[kern] = {"traffic_bytes_per_launch": int(t), "traffic_over_D_bytes": round(t / ab[stage], 3),
-                                        "traffic_over_D_eff_bytes": round(t / ab_eff[stage], 3)}
         out = {
             "metric": f"Msplats/s fwd+bwd @{W}x{H}, {P / 1e6:g}M Gaussians", "value": round(value, 3), "unit": "Msplats/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -950,7 +955,7 @@ def main():
             "step_ms_percentiles": {"p10": pct(0.1), "p50": pct(0.5), "p90": pct(0.9), "max": round(per_step[-1], 4)},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": args.label, "baseline_config": args.tag,
-                       "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": V, "duplicates_D": D, "visible_per_P": round(V / P, 4), "D_per_P": round(D / P, 3),
+                       "gaussians": P, "width": W, "height": H, "sh_degree": deg,
                        "frames_per_step": world * K, "frames_per_rank": K,
                        "parallelism": (f"frame-sharded dp{world}" if multi else "single GPU") + (f", {K} frames accumulated per exchange" if K > 1 else ""),
                        "camera_rig": args.rig,
@@ -966,42 +971,106 @@ def main():
                            "exchange_selfcheck": exchange_check, "backend": dist.get_backend(),
                            "world_size_seen_by_each_rank": worlds_seen, "rccl": rccl_info,
                            "exchange": exchange_report(exchange_detail, P, world, K, ms_per_step, args.exchange)} if multi else {})},
-            "roofline": {"bound": "hbm", "kernel": dom_kernel,
-                         "achieved": None if ach is None else round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": None if ach is None else round(ach / HBM_PEAK_GBS, 5),
-                         "frac_D_eff": None if frac_eff is None else round(frac_eff, 5),
-                         "algorithmic_bytes_per_launch": ab[dominant], "algorithmic_bytes_per_launch_D_eff": ab_eff[dominant],
-                         "avg_launch_ms": round(group_ms[dominant], 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_over_D_eff_bytes": traffic_ratios.get(dom_kernel, {}).get("traffic_over_D_eff_bytes"), "blend_traffic_ratios": traffic_ratios,
-                         "measured_streaming_ceiling": ceiling, "hbm_bound_kernels": hbm_bound,
-                         "note": "HBM fraction as BASELINE.json defines it; the blend kernels are instruction-issue / latency-bound, not HBM-bound (valu.issue_roof, DESIGN.md 4)",
-                         "north_star_blend_fwd_bwd": {"algorithmic_bytes": ab["blend_fwd"] + ab["blend_bwd"], "ms": round(blend_ms, 4),
-                                                      "achieved": None if blend_gbs is None else round(blend_gbs, 2),
-                                                      "frac": None if blend_gbs is None else round(blend_gbs / HBM_PEAK_GBS, 5),
-                                                      "frac_D_eff": None if blend_frac_eff is None else round(blend_frac_eff, 5)},
-                         "valu": valu,
-                         "whole_op": {"algorithmic_bytes": sum(ab.values()), "kernel_ms": round(kernels_ms, 4),
-                                      "frac": round(sum(ab.values()) / (kernels_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if kernels_ms else None}},
-            "stage_ms": {k: (None if v is None else round(v, 4)) for k, v in stage_ms.items()},
         }
-        if world == 1 and not multi and not args.no_train_step:
-            try:
-                out["train_step"] = train_step_section(args, params, cam, dev, D, V)
-            except Exception as e:   # an untimed extra must never cost the line
-                out["train_step"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not multi and not args.no_train_step and args.tag == "c3":
-            try:
-                out["camera_inside_scene"] = camera_inside_scene_section(P, W, H, deg, dc, da, dev)
-            except Exception as e:   # an untimed extra must never cost the line
-                out["camera_inside_scene"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not multi and not args.no_train_step and args.tag == "c3":
-            try:   # the reference's documented operating point (`-r 4`: 480x320 frames) and the forward's launch floor
-                out["reference_operating_point_r4"] = reference_operating_point_section(deg, dev)
-            except Exception as e:   # an untimed extra must never cost the line
-                out["reference_operating_point_r4"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args, g_cpu, cam, dc_cpu, da_cpu)
+        if args.full:
+            npx = W * H
+            ab = algorithmic_bytes(P, V, D, npx, deg)
+            stage_ms = {k: (ms / n if n else None) for k, (ms, n) in stats.items()}
+            groups = {"preprocess": ["preprocess"], "binning": ["depth_sort", "scan", "expand_x", "expand_y", "ranges"],
+                      "blend_fwd": ["blend_fwd"], "blend_bwd": ["blend_bwd"], "preprocess_bwd": ["preprocess_bwd"]}
+            group_ms = {k: sum(stage_ms[s] or 0.0 for s in v) for k, v in groups.items()}
+            dominant = max(("blend_fwd", "blend_bwd"), key=lambda k: group_ms[k])  # the north-star kernels
+            ach = ab[dominant] / (group_ms[dominant] * 1e-3) / 1e9 if group_ms[dominant] else None
+            blend_ms = group_ms["blend_fwd"] + group_ms["blend_bwd"]
+            blend_gbs = (ab["blend_fwd"] + ab["blend_bwd"]) / (blend_ms * 1e-3) / 1e9 if blend_ms else None
+            kernels_ms = sum(group_ms.values())
+            dom_kernel = "render_backward_kernel" if dominant == "blend_bwd" else "render_forward_kernel"
+            traffic, traffic_src = pmc_traffic(dom_kernel, args)
+            # the streaming kernels against what streaming kernels reach on an MI355X (read 6.5, copy 5.0-5.9 TB/s measured; 8 is the vendor peak)
+            ceiling = measured_ceiling()
+            hbm_bound = {}
+            for stage, kern in (("preprocess", "preprocess_forward_kernel"), ("preprocess_bwd", "preprocess_backward_kernel")):
+                t, _ = pmc_traffic(kern, args)
+                if t and group_ms[stage]:
+                    gbs = t / (group_ms[stage] * 1e-3) / 1e9
+                    hbm_bound[kern] = {"traffic_bytes_per_launch": int(t), "ms": round(group_ms[stage], 4), "achieved_GBs": round(gbs, 1), "frac_of_peak": round(gbs / HBM_PEAK_GBS, 4),
+                                       "frac_of_measured_copy_ceiling": None if not ceiling else round(gbs / 1e3 / ceiling["copy"], 4)}
+            # FP32-VALU view of the same two kernels (SURVEY 8d "algorithmic flops": 60 fwd + 200 bwd per tested pair).  K7 walks
+            # exactly the (entry, quadrant) pairs K6 recorded, so one set of counters serves both.
+            lane_tests = blend_counts["quadrant_tests"] * 64
+            useful = blend_counts["contributing_pairs"] * 260 / (blend_ms * 1e-3) / 1e12 if blend_ms else None
+            issued = lane_tests * 260 / (blend_ms * 1e-3) / 1e12 if blend_ms else None
+            # which mapping the forward blend ran (the device's rule, csrc/render.hip render_forward_auto_kernel: rows below 6.5 duplicates per
+            # visible Gaussian; the A/B switches force one) and the lanes IT issued: 64 per wave step of the row mapping (counted with the
+            # octagon-vs-cell culling the kernel uses), 64 per quadrant test otherwise.  K7 always walks quadrants.
+            rows_run = True if args.row_mapped else (False if args.quadrant_mapped else 2 * D < 13 * V)
+            fwd_lane_tests = (blend_counts["row_mapping_steps_octagon_culling"] if rows_run else blend_counts["quadrant_tests"]) * 64
+            valu = {"peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s", "flop_per_pair": 260, **blend_counts, "lane_tests": lane_tests,
+                    "lane_utilisation": round(blend_counts["contributing_pairs"] / lane_tests, 4) if lane_tests else None,
+                    "forward_mapping": "16-lane rows on independent entries" if rows_run else "one entry on 64 lanes (8x8 quadrants)",
+                    "forward_lane_utilisation": round(blend_counts["contributing_pairs"] / fwd_lane_tests, 4) if fwd_lane_tests else None,
+                    "backward_lane_utilisation": round(blend_counts["contributing_pairs"] / (blend_counts["quadrant_tests_with_a_hit"] * 64), 4) if blend_counts["quadrant_tests_with_a_hit"] else None,
+                    "issued": None if issued is None else round(issued, 2), "issued_frac": None if issued is None else round(issued / FP32_VALU_PEAK_TFLOPS, 4),
+                    "useful": None if useful is None else round(useful, 2), "useful_frac": None if useful is None else round(useful / FP32_VALU_PEAK_TFLOPS, 4),
+                    "issue_roof": {"render_forward_kernel": valu_issue_roof("render_forward_kernel", group_ms["blend_fwd"], args),
+                                   "render_backward_kernel": valu_issue_roof("render_backward_kernel", group_ms["blend_bwd"], args, blend_counts["entries_with_a_hit"])},
+                    "note": "issued = 64 lanes x quadrant tests, useful = pairs that contribute.  Neither memory (traffic ~ algorithmic bytes at a fifth "
+                            "of the HBM rate) nor the number of resident waves bounds the blend kernels (a fourth wave per SIMD, built for the two-pixel K7, "
+                            "changes nothing): they run at issue_roof.*.datasheet_issue_frac of the rate the vector unit would reach if every instruction "
+                            "were a two-cycle VOP2 and at issue_roof.*.fitted_issue_cost_frac of the rate their actual instruction forms allow (DPP, "
+                            "transcendentals, lane swaps, three-source / SGPR-source VOP3 at their measured throughput costs) -- the second binds (DESIGN.md 4)",
+                    "D_eff_blend_bytes": blend_counts["staged_entries_D_eff"] * 296 + npx * 160}
+            # The same fractions with the list entries the blend kernels actually stage (D_eff: what lies behind a tile's saturation
+            # point is never loaded) in place of all D duplicates: the D-based figures count bytes no kernel touches -- a factor of two
+            # on the 4K scene.
+            d_eff = blend_counts["staged_entries_D_eff"]
+            ab_eff = {"blend_fwd": d_eff * 76 + npx * 60, "blend_bwd": d_eff * 76 + d_eff * 72 * 2 + npx * (60 + 40)}
+            frac_eff = ab_eff[dominant] / (group_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS if group_ms[dominant] else None
+            blend_frac_eff = (ab_eff["blend_fwd"] + ab_eff["blend_bwd"]) / (blend_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if blend_ms else None
+            # counter traffic of BOTH blend kernels against the algorithmic bytes -- the D-based figure of SURVEY 8(d) and the one computed on
+            # the entries the kernels actually stage (D_eff): the second is the honest "how many bytes per byte needed" ratio
+            traffic_ratios = {}
+            for stage, kern in (("blend_fwd", "render_forward_kernel"), ("blend_bwd", "render_backward_kernel")):
+                t, _ = pmc_traffic(kern, args)
+                if t:
+                    traffic_ratios[kern] = {"traffic_bytes_per_launch": int(t), "traffic_over_D_bytes": round(t / ab[stage], 3),
+                                            "traffic_over_D_eff_bytes": round(t / ab_eff[stage], 3)}
+            out["config"].update(visible=V, duplicates_D=D, visible_per_P=round(V / P, 4), D_per_P=round(D / P, 3))
+            out["roofline"] = {"bound": "hbm", "kernel": dom_kernel,
+                               "achieved": None if ach is None else round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": None if ach is None else round(ach / HBM_PEAK_GBS, 5),
+                               "frac_D_eff": None if frac_eff is None else round(frac_eff, 5),
+                               "algorithmic_bytes_per_launch": ab[dominant], "algorithmic_bytes_per_launch_D_eff": ab_eff[dominant],
+                               "avg_launch_ms": round(group_ms[dominant], 4),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "traffic_over_D_eff_bytes": traffic_ratios.get(dom_kernel, {}).get("traffic_over_D_eff_bytes"), "blend_traffic_ratios": traffic_ratios,
+                               "measured_streaming_ceiling": ceiling, "hbm_bound_kernels": hbm_bound,
+                               "note": "HBM fraction as BASELINE.json defines it; the blend kernels are instruction-issue / latency-bound, not HBM-bound (valu.issue_roof, DESIGN.md 4)",
+                               "north_star_blend_fwd_bwd": {"algorithmic_bytes": ab["blend_fwd"] + ab["blend_bwd"], "ms": round(blend_ms, 4),
+                                                            "achieved": None if blend_gbs is None else round(blend_gbs, 2),
+                                                            "frac": None if blend_gbs is None else round(blend_gbs / HBM_PEAK_GBS, 5),
+                                                            "frac_D_eff": None if blend_frac_eff is None else round(blend_frac_eff, 5)},
+                               "valu": valu,
+                               "whole_op": {"algorithmic_bytes": sum(ab.values()), "kernel_ms": round(kernels_ms, 4),
+                                            "frac": round(sum(ab.values()) / (kernels_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if kernels_ms else None}}
+            out["stage_ms"] = {k: (None if v is None else round(v, 4)) for k, v in stage_ms.items()}
+            if world == 1 and not multi and not args.no_train_step:
+                try:
+                    out["train_step"] = train_step_section(args, params, cam, dev, D, V)
+                except Exception as e:   # an untimed extra must never cost the line
+                    out["train_step"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if world == 1 and not multi and not args.no_train_step and args.tag == "c3":
+                try:
+                    out["camera_inside_scene"] = camera_inside_scene_section(P, W, H, deg, dc, da, dev)
+                except Exception as e:   # an untimed extra must never cost the line
+                    out["camera_inside_scene"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if world == 1 and not multi and not args.no_train_step and args.tag == "c3":
+                try:   # the reference's documented operating point (`-r 4`: 480x320 frames) and the forward's launch floor
+                    out["reference_operating_point_r4"] = reference_operating_point_section(deg, dev)
+                except Exception as e:   # an untimed extra must never cost the line
+                    out["reference_operating_point_r4"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args, g_cpu, cam, dc_cpu, da_cpu)
     # The JSON line is the LAST thing on stdout.  With NCCL_DEBUG set RCCL printf()s a version banner into libc's stdout buffer at init, which
     # a pipe only sees when the process exits -- i.e. after the line, and once per rank.  So: every rank flushes libc's buffers now, the ranks
     # meet, rank 0 prints, and everybody points fd 1 at /dev/null for whatever else gets flushed at exit.

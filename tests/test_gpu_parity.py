@@ -727,7 +727,7 @@ def test_bench_one_rank_rccl_reports_the_exchange():
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.pop("NCCL_DEBUG", None); env.pop("NCCL_DEBUG_FILE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--gaussians", "300000",
-                        "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c = d["config"]
@@ -761,6 +761,40 @@ def test_bench_gpus_8_ranks_on_one_gpu():
     assert d["n_gpus"] == 8 and d["config"]["world_size_seen_by_each_rank"] == [8] * 8 and d["config"]["frames_per_step"] == 8
     assert d["config"]["exchange_selfcheck"]["ok"] and d["config"]["parallelism"].startswith("frame-sharded dp8")
     assert d["scaling"] == "weak" and d["value"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` prints the headline only (the extras are --full's), times exactly N steps, and
+    --dump-outputs writes the last step's maps, radii and parameter gradients as float32 .npy files (< 64 MB): two runs with the same
+    arguments see the same inputs, so their outputs agree (radii exactly; the rest up to the order of the gradient atomics)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ["color", "allmap", "radii"] + ["grad_" + n for n in ("means3D", "shs", "opacities", "scales", "rotations", "means2D")]
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--gaussians", "200000",
+                            "--width", "640", "--height", "360", "--dump-outputs", str(out)], cwd=root, env=_bare_env(), capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "Msplats/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["metric"].startswith("Msplats/s fwd+bwd")
+        assert abs(d["timed_region_ms"] - 4 * d["ms_per_step"]) < 1e-2 * d["timed_region_ms"] + 1e-3
+        assert not {"roofline", "stage_ms", "cpu_baseline", "train_step", "camera_inside_scene", "reference_operating_point_r4"} & set(d)
+        assert sorted(p.name for p in out.iterdir()) == sorted(n + ".npy" for n in names)
+        arrays = {n: np.load(out / (n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["color"].shape == (3, 640 * 360) and arrays["allmap"].shape == (7, 640 * 360)
+        assert arrays["radii"].shape == (1 << 16,) and arrays["grad_shs"].shape == (1 << 16, 16, 3) and arrays["grad_scales"].shape == (1 << 16, 2)
+        assert (arrays["radii"] > 0).any() and np.abs(arrays["grad_means3D"]).max() > 0 and np.isfinite(arrays["grad_shs"]).all()
+        dumps.append(arrays)
+    np.testing.assert_array_equal(dumps[0]["radii"], dumps[1]["radii"])
+    for n in names:
+        a, b = dumps[0][n], dumps[1][n]
+        assert np.abs(a - b).max() <= 1e-4 * np.abs(a).max() + 1e-12, n
 
 
 @pytest.mark.parametrize("tile", [(8, 8), (16, 8), (32, 8), (32, 16)])

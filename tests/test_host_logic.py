@@ -451,6 +451,34 @@ def test_bench_measurement_helpers(tmp_path, monkeypatch):
     assert bench.pmc_traffic("render_backward_kernel", argparse.Namespace(tag="custom", sh_degree=3)) == (None, None)
 
 
+def test_bench_dump_outputs_samples(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files, maps cut to a seeded pixel sample and per-Gaussian arrays to a seeded row sample that are
+    the same in every run, small arrays whole, and no more than DUMP_MAX_BYTES written."""
+    import importlib, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    P, W, H = 70_000, 640, 480
+    g = torch.Generator().manual_seed(3)
+    maps = {"color": torch.randn(3, H, W, generator=g)}
+    rows = {"radii": torch.randint(0, 40, (P,), generator=g, dtype=torch.int32), "grad_shs": torch.randn(P, 16, 3, generator=g)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), W * H, P, maps, rows, whole={"loss": torch.tensor(1.5, dtype=torch.float64)})
+    pix, row = bench._dump_index(W * H, bench.DUMP_PIXELS, seed=0), bench._dump_index(P, bench.DUMP_ROWS, seed=1)
+    assert len(set(pix.tolist())) == bench.DUMP_PIXELS and len(set(row.tolist())) == bench.DUMP_ROWS
+    for run in ("a", "b"):
+        got = {n: np.load(tmp_path / run / (n + ".npy")) for n in ("color", "radii", "grad_shs", "loss")}
+        assert all(a.dtype == np.float32 for a in got.values())
+        np.testing.assert_array_equal(got["color"], maps["color"].reshape(3, -1)[:, pix].numpy())
+        np.testing.assert_array_equal(got["radii"], rows["radii"][row].float().numpy())
+        np.testing.assert_array_equal(got["grad_shs"], rows["grad_shs"][row].numpy())
+        assert got["loss"].tolist() == [1.5]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 20)
+    with pytest.raises(SystemExit, match="--dump-outputs would write"):
+        bench.dump_outputs(str(tmp_path / "c"), W * H, P, maps, rows)
+    assert not (tmp_path / "c").exists()
+
+
 def test_posed_scene_and_rig_are_what_they_say():
     """The general-position scenes the parity tests rely on (streetunveiler_amd.synthetic.posed_scene / posed_rig): the camera has its own
     centre, a proper rotation and unrelated FoVs; the Gaussians sit in front of it in ITS frame with the benchmark scene's statistics;

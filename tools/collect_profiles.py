@@ -3,10 +3,10 @@
 <tag>_kernel_stats.csv, <tag>_hbm_traffic.json, <tag>_sq_counters.json, <tag>_bench.json (tag = round + workload, e.g. r02_c3).
     python tools/collect_profiles.py gpurun_out/r02_c3 r02_c3 [output dir, default profiles/]
 The profiling call itself (on the GPU box):
-    rocprofv3 --kernel-trace --stats --output-format csv -d D -o trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D -o fetch -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d D -o write -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU ... --kernel-trace --output-format csv -d D -o sq -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --stats --output-format csv -d D -o trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D -o fetch -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d D -o write -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU ... --kernel-trace --output-format csv -d D -o sq -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 """
 import collections, csv, json, os, re, sys
 

@@ -6,7 +6,7 @@ port=29611
 for n in 2 8; do for rig in benchmark inside; do for ex in allreduce compacted; do
   port=$((port+1))
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 2 --warmup 1 \
-      --no-cpu-baseline --no-train-step --exchange $ex --rig $rig 2>/dev/null | tail -1 | python -c "
+      --full --no-cpu-baseline --no-train-step --exchange $ex --rig $rig 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']
 print(json.dumps({'n_ranks': d['n_gpus'], 'rig': c['camera_rig'], 'exchange': '$ex', 'gaussians': c['gaussians'], 'visible_per_P_rank0': c['visible_per_P'],

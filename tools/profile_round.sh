@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 D=$R/gpurun_out/${TAG}_${CFG}${SUF}
 mkdir -p $D
 cd $R
-B="python bench.py --config $CFG --no-cpu-baseline --no-train-step $EXTRA"
+B="python bench.py --full --config $CFG --no-cpu-baseline --no-train-step $EXTRA"
 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o trace -- $B --steps 20 --warmup 5 > $D/trace_bench.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $D -o fetch -- $B --steps 3 --warmup 1 > $D/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $D -o write -- $B --steps 3 --warmup 1 > $D/write.log 2>&1
@@ -21,7 +21,7 @@ rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum --kernel-trace --o
 # current one, so the fresh counter files go into the box's profiles/ BEFORE the run whose line is kept (it used to quote the previous profile)
 python tools/collect_profiles.py $D ${TAG}_${CFG}${SUF} $D/out
 if [ -z "$SUF" ]; then cp $D/out/${TAG}_${CFG}_hbm_traffic.json $D/out/${TAG}_${CFG}_sq_counters.json profiles/; fi
-python bench.py --config $CFG $EXTRA 2>$D/bench.err | tail -1 > $D/bench.json
+python bench.py --full --config $CFG $EXTRA 2>$D/bench.err | tail -1 > $D/bench.json
 python tools/collect_profiles.py $D ${TAG}_${CFG}${SUF} $D/out
 ls $D/out
 # the raw CSVs stay on the box (gpurun merges at most 64 MiB back): the condensed files in out/ and the logs are what is kept
