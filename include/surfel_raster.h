@@ -144,14 +144,20 @@ typedef struct SrFrame {
                                       * only runs with this flag).  Set in sr_forward_render and in the backward.  Without either
                                       * flag the library picks by the frame's tile count: cooperative below 2 600 tiles of 16x16 (the reference's `-r 4` frames:
                                       * 600 tiles cannot fill the GPU with one wave each), one wave per tile above.  Same tile lists either way; gradients
-                                      * agree up to the order of a four-term sum.  The flags exist for the A/B and the tests */
+                                      * agree up to the order of a four-term sum.  The flags exist for the A/B and the tests.
+                                      * At most ONE of SR_FLAG_ONE_WAVE_BACKWARD, SR_FLAG_COOP_BACKWARD and SR_FLAG_ROW_BACKWARD per call: sr_forward_render,
+                                      * sr_backward_blend, sr_backward_geometry and sr_backward return SR_ERR_INVALID_ARGUMENT for two or three of them.  The
+                                      * backward of a frame must carry the same one of them as its forward (or none in both): the library keeps no per-frame
+                                      * record of which forward ran, so a mismatch across the two calls is NOT detected */
 
 #define SR_FLAG_ROW_BACKWARD 1024u     /* 16x16 tile, three colour channels, culling on: the ROW-MAPPED blend pair -- the forward (row-mapped kernel) writes its hit masks
                                       * per (entry, 4x4 cell) instead of per (entry, 8x8 quadrant), and the backward's four 16-lane rows each walk their own cell's
                                       * list (render_backward_rows_kernel).  Must be set in sr_forward_render AND in the backward of the same frame (the hit-mask
                                       * format differs).  Images bit-identical; gradients agree with the one-wave kernel's up to the order of additions.
                                       * MEASURED SLOWER (C3: K7 2.55 ms against 1.65: the per-entry sums are scattered into LDS with float atomics, ~100 LDS cycles
-                                      * per wave instruction -- csrc/render_bwd.hip): built and kept as the measured answer, picked nowhere */
+                                      * per wave instruction -- csrc/render_bwd.hip): built and kept as the measured answer, picked nowhere.  The backward checks the
+                                      * same preconditions as the forward (16x16, three channels, no SR_FLAG_NO_QUADRANT_CULL: else SR_ERR_UNSUPPORTED) and, like it,
+                                      * refuses SR_FLAG_ONE_WAVE_BACKWARD / SR_FLAG_COOP_BACKWARD beside this flag */
 
 /* Per-Gaussian inputs == the keyword arguments of GaussianRasterizer.forward
  * (/root/reference/gaussian_renderer/__init__.py:129-138).  Exactly one of shs / colors_precomp

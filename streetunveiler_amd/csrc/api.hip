@@ -310,6 +310,16 @@ int check_backward_frame(const SrFrame* frame) {
     return SR_OK;
 }
 
+// SR_FLAG_ONE_WAVE_BACKWARD / SR_FLAG_COOP_BACKWARD / SR_FLAG_ROW_BACKWARD each pick the blend PAIR of a frame (forward and backward): the forward
+// tests them in one order, the backward in another, and the row-mapped backward reads cell-granular hit masks that only its own forward writes --
+// so at most one of them per call.  (Forward and backward of one frame must carry the same one: include/surfel_raster.h.)
+int check_blend_pair_flags(const SrFrame* frame) {
+    const uint32_t pair = frame->flags & (SR_FLAG_ONE_WAVE_BACKWARD | SR_FLAG_COOP_BACKWARD | SR_FLAG_ROW_BACKWARD);
+    if (pair & (pair - 1))
+        return fail(SR_ERR_INVALID_ARGUMENT, "SR_FLAG_ONE_WAVE_BACKWARD, SR_FLAG_COOP_BACKWARD and SR_FLAG_ROW_BACKWARD exclude each other (flags 0x%x)", pair);
+    return SR_OK;
+}
+
 FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
     FrameDev f{};
     f.W = frame->image_width; f.H = frame->image_height;
@@ -540,6 +550,7 @@ int sr_forward_render(const SrFrame* frame, const SrGaussians* g, void* geom, si
                       size_t binning_bytes, void* image, size_t image_bytes, uint32_t D, float* out_color,
                       float* out_allmap, void* stream) {
     if (int rc = check_common(frame, g)) return rc;
+    if (int rc = check_blend_pair_flags(frame)) return rc;
     const bool fwd_only = (frame->flags & SR_FLAG_FORWARD_ONLY) != 0;   // no backward follows: its state (image buffer, hit masks) is not written
     if (!binning || (!image && !fwd_only) || !out_color || !out_allmap) return fail(SR_ERR_INVALID_ARGUMENT, "binning / image / out_color / out_allmap is NULL");
     const int W = frame->image_width, H = frame->image_height;
@@ -736,6 +747,10 @@ int backward_ctx(const SrFrame* frame, const SrGaussians* g, void* geom, size_t 
                  void* image, size_t image_bytes, uint32_t D, void* workspace, size_t workspace_bytes, void* stream, BackwardCtx* c) {
     if (int rc = check_common(frame, g)) return rc;
     if (int rc = check_backward_frame(frame)) return rc;
+    if (int rc = check_blend_pair_flags(frame)) return rc;
+    const FrameDev shape = make_frame(frame, g);   // (the forward's preconditions of the row-mapped pair, on the same derived tile / channels)
+    if ((frame->flags & SR_FLAG_ROW_BACKWARD) && (!(shape.tile_w == 16 && shape.tile_h == 16 && shape.colors == 3) || (frame->flags & SR_FLAG_NO_QUADRANT_CULL)))
+        return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_BACKWARD: 16x16 tile, three colour channels, culling on (as in the forward of the frame)");
     c->P = g->P;
     if (c->P == 0) return SR_OK;
     if (!geom || !binning || !image || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");

@@ -8,6 +8,7 @@ import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
 from oracle import surfel_oracle as so
 from tests.bars import BARS as _BAR_TABLE, bar
+from tools.blend_pairs import COOP_BELOW_TILES, assert_blend_variants, blend_variants  # noqa: F401  (the two blend pairs of the 16x16 tile; shared with tools/fuzz_parity.py)
 
 DEV = "cuda:0"
 BARS = {k: v[0] for k, v in _BAR_TABLE.items()}   # name -> value: THE tolerances (tests/bars.py: frozen, one table, a changelog rule)
@@ -35,8 +36,9 @@ def run_oracle(g, cam, bg, deg, dc=None, da=None, mode="sh", colors=None, Tpre=N
     return fwd, bwd
 
 
-def run_hip(g, cam, bg, deg, dc=None, da=None, colors=None, Tpre=None, debug=False, tile=None, quadrant_cull=True, row_mapped=None):
-    """Returns dict with outputs, internal state views and (if dc given) input gradients, all numpy."""
+def run_hip(g, cam, bg, deg, dc=None, da=None, colors=None, Tpre=None, debug=False, tile=None, quadrant_cull=True, row_mapped=None, backward_kernel=None):
+    """Returns dict with outputs, internal state views and (if dc given) input gradients, all numpy.  `backward_kernel` = None / "one_wave" /
+    "coop": the blend pair the library picks by the tile count / forced (GaussianRasterizer(backward_kernel=))."""
     dev = DEV
     s = settings_for(cam, bg, deg, debug)
     P = g["means3D"].shape[0]
@@ -51,7 +53,7 @@ def run_hip(g, cam, bg, deg, dc=None, da=None, colors=None, Tpre=None, debug=Fal
         t["Tpre"] = torch.as_tensor(Tpre).to(dev).requires_grad_(); kw["cov3D_precomp"] = t["Tpre"]
     else:
         kw["scales"] = t["scales"]; kw["rotations"] = t["rotations"]
-    color, radii, allmap = GaussianRasterizer(s, tile=tile, quadrant_cull=quadrant_cull, row_mapped=row_mapped)(**kw)
+    color, radii, allmap = GaussianRasterizer(s, tile=tile, quadrant_cull=quadrant_cull, row_mapped=row_mapped, backward_kernel=backward_kernel)(**kw)
     out = dict(color=color.detach().cpu().numpy(), radii=radii.cpu().numpy(), allmap=allmap.detach().cpu().numpy())
     if dc is not None:
         ((color * dc.to(dev)).sum() + (allmap * da.to(dev)).sum()).backward()
@@ -65,7 +67,7 @@ def run_hip(g, cam, bg, deg, dc=None, da=None, colors=None, Tpre=None, debug=Fal
     return out
 
 
-def run_hip_raw(g, cam, bg, deg, colors=None, Tpre=None, tile=None, quadrant_cull=True, decisions=False, row_mapped=None):
+def run_hip_raw(g, cam, bg, deg, colors=None, Tpre=None, tile=None, quadrant_cull=True, decisions=False, row_mapped=None, backward_kernel=None):
     """Calls _C.rasterize_gaussians directly and returns the state-buffer views as numpy (for bit-exact checks)."""
     dev = DEV
     s = settings_for(cam, bg, deg)
@@ -78,7 +80,8 @@ def run_hip_raw(g, cam, bg, deg, colors=None, Tpre=None, tile=None, quadrant_cul
     tp = e if Tpre is None else torch.as_tensor(Tpre).to(dev)
     D, color, allmap, radii, geom, binning, img = _C.rasterize_gaussians(
         s.bg, d("means3D"), col, d("opacities"), sc, ro, 1.0, tp, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-        s.image_height, s.image_width, sh, deg, s.campos, False, False, tile=tile, quadrant_cull=quadrant_cull, row_mapped=row_mapped)
+        s.image_height, s.image_width, sh, deg, s.campos, False, False, tile=tile, quadrant_cull=quadrant_cull, row_mapped=row_mapped,
+        backward_kernel=backward_kernel)
     dec = None
     if decisions:   # the hard decisions the blend kernels act on, per (list entry, pixel) pair (sr_debug_pair_decisions)
         valid, use3d = _C.pair_decisions(s.bg, d("means3D"), 1.0, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,

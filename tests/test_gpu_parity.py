@@ -73,8 +73,8 @@ def _check_grads(out, bwd, names, tag, rel=2e-3):
 
 
 def test_golden_small_scene(golden_dir):
-    """The committed oracle fixture (64 Gaussians, 32x32, SH3): every stage."""
-    from tests.gpu_util import run_hip, run_hip_raw, run_oracle
+    """The committed oracle fixture (64 Gaussians, 32x32, SH3): every stage -- the gradients of both blend pairs (tests/gpu_util.py blend_variants)."""
+    from tests.gpu_util import blend_variants, run_hip_raw
     from streetunveiler_amd.camera import SimpleCamera
     z = np.load(os.path.join(golden_dir, "oracle_small.npz"))
     g = {k: torch.tensor(z["in_" + k]) for k in ["means3D", "scales", "rotations", "opacities", "shs"]}
@@ -87,11 +87,11 @@ def test_golden_small_scene(golden_dir):
     _check_binning(raw, fwd)
     np.testing.assert_array_equal(raw["img"]["n_contrib"].view(np.uint32), fwd["n_contrib"])
     np.testing.assert_allclose(raw["img"]["final_T"], fwd["final_T"], rtol=1e-4, atol=1e-5)
-    out = run_hip(g, cam, z["in_bg"], 3, dc, da)
-    np.testing.assert_allclose(out["color"], fwd["color"], atol=1e-4)
-    np.testing.assert_allclose(out["allmap"], fwd["allmap"], rtol=1e-4, atol=1e-4)
     bwd = {k[4:]: z[k] for k in z.files if k.startswith("bwd_")}
-    _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], "golden")
+    for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, z["in_bg"], 3, dc, da)):
+        np.testing.assert_allclose(out["color"], fwd["color"], atol=1e-4)
+        np.testing.assert_allclose(out["allmap"], fwd["allmap"], rtol=1e-4, atol=1e-4)
+        _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], "golden " + kernel)
 
 
 @pytest.mark.parametrize("P,W,H,deg,lo,hi,cam_index", [
@@ -105,8 +105,9 @@ def test_forward_backward_vs_oracle(P, W, H, deg, lo, hi, cam_index):
 
 
 def _full_check(cam, g, deg, bg, upstream, tag, **budgets):
-    """Every stage against the float32 oracle, then the free-running float64 reference."""
-    from tests.gpu_util import run_hip, run_hip_raw, run_oracle
+    """Every stage against the float32 oracle, then the free-running float64 reference -- the gradients of BOTH blend pairs (the one-wave
+    kernel of the large frames and the cooperative one the default picks here: tests/gpu_util.py blend_variants), references computed once."""
+    from tests.gpu_util import blend_variants, run_hip_raw, run_oracle
     P = g["means3D"].shape[0]
     dc, da = upstream
     fwd, bwd = run_oracle(g, cam, bg, deg, dc, da)
@@ -117,18 +118,19 @@ def _full_check(cam, g, deg, bg, upstream, tag, **budgets):
     assert raw["geom"]["frame_counts"].view(np.uint32).tolist() == [fwd["num_rendered"], int((fwd["tiles_touched"] > 0).sum())]
     nc = raw["img"]["n_contrib"].view(np.uint32)
     assert (nc != fwd["n_contrib"]).mean() < 1e-3   # contributor counts: equal up to rare threshold flips
-    out = run_hip(g, cam, bg, deg, dc, da)
-    _check_images(out, fwd, tag)
-    _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], tag)
-    # invisible Gaussians get exactly zero gradient
-    inv = fwd["radii"] == 0
-    for k in ["dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D", "dL_dopacity"]:
-        assert not np.asarray(out[k])[inv].any(), k
-    # ... and against the free-running float64 reference (its own decisions): 1e-4 and identical stop / median positions at EVERY
-    # robust pixel, strict rows on every robust Gaussian, the non-robust remainder counted (tests/gpu_util.py)
     from tests.gpu_util import assert_free_parity, free_f64_reference
     xfwd, xbwd, margins = free_f64_reference(g, cam, bg, deg, dc, da, base=fwd, kernel_decisions=raw["decisions"])
-    assert_free_parity(out, nc, xfwd, xbwd, margins, tag=tag + " ", scene=(g, cam), **budgets)
+    inv = fwd["radii"] == 0
+    for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, deg, dc, da)):
+        ktag = f"{tag} {kernel}"
+        _check_images(out, fwd, ktag)
+        _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], ktag)
+        # invisible Gaussians get exactly zero gradient
+        for k in ["dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D", "dL_dopacity"]:
+            assert not np.asarray(out[k])[inv].any(), (kernel, k)
+        # ... and against the free-running float64 reference (its own decisions): 1e-4 and identical stop / median positions at EVERY
+        # robust pixel, strict rows on every robust Gaussian, the non-robust remainder counted (tests/gpu_util.py)
+        assert_free_parity(out, nc, xfwd, xbwd, margins, tag=ktag + " ", scene=(g, cam), **budgets)
 
 
 @pytest.mark.parametrize("seed,P,W,H,deg,lo,hi,spread", [
@@ -174,25 +176,26 @@ def test_cloned_gaussians_and_depth_ties():
 
 
 def test_colors_precomp_and_transmat_precomp():
-    from tests.gpu_util import run_hip, run_oracle
+    """Both halves on both blend pairs (tests/gpu_util.py blend_variants)."""
+    from tests.gpu_util import blend_variants, run_oracle
     P, W, H = 3000, 200, 120
     cam, g = _scene(P, W, H, 11, 5e-3, 6e-2, 5)
     bg = np.array([0.0, 1.0, 0.0], np.float32)   # render_semantic-style one-hot background
     dc, da = synthetic_upstream_grads(W, H, seed=3)
     colors = np.random.default_rng(0).random((P, 3)).astype(np.float32)
     fwd, bwd = run_oracle(g, cam, bg, 0, dc, da, colors=colors)
-    out = run_hip(g, cam, bg, 0, dc, da, colors=colors)
-    np.testing.assert_array_equal(out["radii"], fwd["radii"])
-    _check_images(out, fwd, "colors_precomp")
-    _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dcolors", "dL_dmeans2D"], "colors_precomp")
+    for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 0, dc, da, colors=colors)):
+        np.testing.assert_array_equal(out["radii"], fwd["radii"])
+        _check_images(out, fwd, "colors_precomp " + kernel)
+        _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dcolors", "dL_dmeans2D"], "colors_precomp " + kernel)
     # precomputed transMat (the reference's cov3D_precomp slot)
     Tpre = fwd["transMat"].copy()
     Tpre[fwd["radii"] == 0] = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
     fwd2, bwd2 = run_oracle(g, cam, bg, 2, dc, da, Tpre=Tpre)
-    out2 = run_hip(g, cam, bg, 2, dc, da, Tpre=Tpre)
-    np.testing.assert_array_equal(out2["radii"], fwd2["radii"])
-    _check_images(out2, fwd2, "transMat_precomp")
-    _check_grads(out2, bwd2, ["dL_dmeans3D", "dL_dopacity", "dL_dsh", "dL_dtransMat", "dL_dmeans2D"], "transMat_precomp")
+    for kernel, out2 in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 2, dc, da, Tpre=Tpre)):
+        np.testing.assert_array_equal(out2["radii"], fwd2["radii"])
+        _check_images(out2, fwd2, "transMat_precomp " + kernel)
+        _check_grads(out2, bwd2, ["dL_dmeans3D", "dL_dopacity", "dL_dsh", "dL_dtransMat", "dL_dmeans2D"], "transMat_precomp " + kernel)
 
 
 def test_empty_and_all_culled_inputs():
@@ -405,11 +408,11 @@ def C_void(x):
 
 def test_sh_layout_fallbacks_and_scale_modifier():
     """Paths the bench never takes: SH tensors with M != 16 or a 4-byte-aligned base (no LDS row staging), SH degree 2,
-    and scale_modifier != 1 (forward honours it; the backward keeps upstream's modifier-free scale gradient, A.6)."""
+    and scale_modifier != 1 (forward honours it; the backward keeps upstream's modifier-free scale gradient, A.6) -- on both blend pairs."""
     import math
     from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
     from oracle import surfel_oracle as so
-    from tests.gpu_util import DEV, assert_close_frac, assert_grads_close
+    from tests.gpu_util import DEV, assert_blend_variants, assert_close_frac, assert_grads_close
     P, W, H = 3000, 160, 96
     cam, g = _scene(P, W, H, 17, 4e-3, 5e-2, 3)
     bg = np.array([0.1, 0.0, 0.2], np.float32)
@@ -421,26 +424,33 @@ def test_sh_layout_fallbacks_and_scale_modifier():
                                    campos=cam.camera_center.numpy(), bg=bg, image_width=W, image_height=H, sh_degree=deg, scale_modifier=modifier,
                                    tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2))
         bwd = so.rasterize_backward(fwd, dc.numpy(), da.numpy())
-        if misalign:   # a view that starts 4 bytes into its storage: contiguous but not 16-byte aligned
-            buf = torch.zeros(P * M * 3 + 1, device=DEV)
-            shs = buf[1:].view(P, M, 3)
-            shs.copy_(shs_cpu.to(DEV))
-            assert shs.data_ptr() % 16 != 0
-            shs.requires_grad_()
-        else:
-            shs = shs_cpu.to(DEV).requires_grad_()
-        t = {k: g[k].to(DEV).requires_grad_() for k in ["means3D", "opacities", "scales", "rotations"]}
-        s = GaussianRasterizationSettings(H, W, math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), torch.tensor(bg).to(DEV), modifier,
-                                          cam.world_view_transform.to(DEV), cam.full_proj_transform.to(DEV), deg, cam.camera_center.to(DEV), False, False)
-        m2d = torch.zeros(P, 3, device=DEV, requires_grad=True)
-        color, radii, allmap = GaussianRasterizer(s)(means3D=t["means3D"], means2D=m2d, shs=shs, opacities=t["opacities"], scales=t["scales"], rotations=t["rotations"])
-        torch.autograd.backward([color, allmap], [dc.to(DEV), da.to(DEV)])
+
+        def run(backward_kernel=None, row_mapped=None):
+            if misalign:   # a view that starts 4 bytes into its storage: contiguous but not 16-byte aligned
+                buf = torch.zeros(P * M * 3 + 1, device=DEV)
+                shs = buf[1:].view(P, M, 3)
+                shs.copy_(shs_cpu.to(DEV))
+                assert shs.data_ptr() % 16 != 0
+                shs.requires_grad_()
+            else:
+                shs = shs_cpu.to(DEV).requires_grad_()
+            t = {k: g[k].to(DEV).requires_grad_() for k in ["means3D", "opacities", "scales", "rotations"]}
+            s = GaussianRasterizationSettings(H, W, math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), torch.tensor(bg).to(DEV), modifier,
+                                              cam.world_view_transform.to(DEV), cam.full_proj_transform.to(DEV), deg, cam.camera_center.to(DEV), False, False)
+            m2d = torch.zeros(P, 3, device=DEV, requires_grad=True)
+            color, radii, allmap = GaussianRasterizer(s, row_mapped=row_mapped, backward_kernel=backward_kernel)(
+                means3D=t["means3D"], means2D=m2d, shs=shs, opacities=t["opacities"], scales=t["scales"], rotations=t["rotations"])
+            torch.autograd.backward([color, allmap], [dc.to(DEV), da.to(DEV)])
+            grads = [("dL_dmeans3D", t["means3D"].grad), ("dL_dopacity", t["opacities"].grad), ("dL_dscales", t["scales"].grad),
+                     ("dL_drotations", t["rotations"].grad), ("dL_dsh", shs.grad), ("dL_dmeans2D", m2d.grad)]
+            return dict(color=color.detach().cpu().numpy(), allmap=allmap.detach().cpu().numpy(), radii=radii.cpu().numpy(),
+                        **{name: got.cpu().numpy() for name, got in grads})
         tag = f"M{M} deg{deg} misalign{misalign} mod{modifier}"
-        np.testing.assert_array_equal(radii.cpu().numpy(), fwd["radii"], err_msg=tag)
-        assert_close_frac(color.detach().cpu().numpy(), fwd["color"], 1e-4, 1e-4, 2e-4, 2e-2, tag)
-        for name, got in [("dL_dmeans3D", t["means3D"].grad), ("dL_dopacity", t["opacities"].grad), ("dL_dscales", t["scales"].grad),
-                          ("dL_drotations", t["rotations"].grad), ("dL_dsh", shs.grad), ("dL_dmeans2D", m2d.grad)]:
-            assert_grads_close(got.cpu().numpy(), bwd[name], 2e-3, tag + " " + name)
+        for kernel, out in zip(("one_wave", "coop"), assert_blend_variants(run, ((W + 15) // 16) * ((H + 15) // 16), tag=tag)):
+            np.testing.assert_array_equal(out["radii"], fwd["radii"], err_msg=tag)
+            assert_close_frac(out["color"], fwd["color"], 1e-4, 1e-4, 2e-4, 2e-2, tag + " " + kernel)
+            for name in ("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"):
+                assert_grads_close(out[name], bwd[name], 2e-3, f"{tag} {kernel} {name}")
 
 
 @pytest.mark.gpu
@@ -829,8 +839,8 @@ def test_tile_shape_sweep(tile):
 
 def test_very_long_tile_lists_and_tiny_images():
     """One tile with a list far longer than a staging round can see (40 k translucent splats over a 24x20 image: > 600 rounds of
-    64, 16-bit contributor counts exceeded), and images smaller than a tile / a single pixel."""
-    from tests.gpu_util import run_hip, run_hip_raw, run_oracle
+    64, 16-bit contributor counts exceeded), and images smaller than a tile / a single pixel -- on both blend pairs (blend_variants)."""
+    from tests.gpu_util import blend_variants, run_hip_raw, run_oracle
     P, W, H = 40000, 24, 20
     cam, g = _scene(P, W, H, 41, 2e-2, 2e-1, 0)
     g["opacities"] = g["opacities"] * 0.02          # nothing saturates: every pixel walks (almost) the whole list
@@ -840,32 +850,36 @@ def test_very_long_tile_lists_and_tiny_images():
     assert (fwd["ranges"][:, 1] - fwd["ranges"][:, 0]).max() > 20000
     assert fwd["n_contrib"][0].max() > 5000
     _check_binning(run_hip_raw(g, cam, bg, 2), fwd)
-    out = run_hip(g, cam, bg, 2, dc, da)
-    _check_images(out, fwd, "long lists")
-    _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], "long lists")
+    for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 2, dc, da)):
+        _check_images(out, fwd, "long lists " + kernel)
+        _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], "long lists " + kernel)
     for (w, h) in ((5, 3), (1, 1), (17, 1)):
         cam2, g2 = _scene(300, w, h, 42, 5e-2, 5e-1, 1)
         dc2, da2 = synthetic_upstream_grads(w, h, seed=6)
         f2, b2 = run_oracle(g2, cam2, bg, 1, dc2, da2)
-        o2 = run_hip(g2, cam2, bg, 1, dc2, da2)
-        np.testing.assert_array_equal(o2["radii"], f2["radii"])
-        np.testing.assert_allclose(o2["color"], f2["color"], atol=2e-4)
-        np.testing.assert_allclose(o2["allmap"][[0, 1, 2, 3, 4, 6]], f2["allmap"][[0, 1, 2, 3, 4, 6]], atol=2e-3, rtol=2e-3)
-        for k in ("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh"):
-            sc = np.abs(b2[k]).max() + 1e-20
-            assert np.abs(o2[k].reshape(b2[k].shape) - b2[k]).max() <= 2e-2 * sc, (w, h, k)
+        for kernel, o2 in zip(("one_wave", "coop"), blend_variants(g2, cam2, bg, 1, dc2, da2)):
+            np.testing.assert_array_equal(o2["radii"], f2["radii"])
+            np.testing.assert_allclose(o2["color"], f2["color"], atol=2e-4)
+            np.testing.assert_allclose(o2["allmap"][[0, 1, 2, 3, 4, 6]], f2["allmap"][[0, 1, 2, 3, 4, 6]], atol=2e-3, rtol=2e-3)
+            for k in ("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh"):
+                sc = np.abs(b2[k]).max() + 1e-20
+                assert np.abs(o2[k].reshape(b2[k].shape) - b2[k]).max() <= 2e-2 * sc, (w, h, kernel, k)
 
 
 def test_randomised_scenes_short_sweep():
     """tools/fuzz_parity.py on a dozen random scenes (sizes, SH degree, tile shape, opacity / scale regimes, precomputed
     colours): bit-exact binning, images within one flipped contributor, at most max(3, 0.1 %) Gaussians with an
-    out-of-tolerance gradient."""
+    out-of-tolerance gradient -- on the 16x16 scenes for the one-wave and the cooperative blend backward alike."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_parity.py"), "12", "2000"], cwd=root, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "12/12 scenes within the parity bars" in r.stdout
+    # ... the 16x16 scenes among them on both blend pairs (the one-wave kernel and the cooperative one the default picks at these sizes)
+    import re
+    m = re.search(r"one-wave and cooperative K7 both checked on (\d+) scenes", r.stdout)
+    assert m and int(m.group(1)) > 0, r.stdout[-2000:]
     # scenes a 250-scene sweep found in round 3: splats hundreds of pixels wide whose centre projects far off-screen -- the moments of dL/dp
     # were taken about that centre and cancelled (dL_dscales rows 2.6e-2 off with identical decisions, the float32 oracle 7e-6); the
     # reference point is now the centre clamped into the image, and the kernels are the more accurate of the two there
@@ -902,8 +916,8 @@ def test_extensions_short_sweep():
 
 def test_degenerate_parameters():
     """Zero / sub-denormal / gigantic scales, zero quaternions, opacity exactly 0 and 1: same radii, no NaN or Inf on either
-    side, images and gradients within the usual bars (scales underflow in training; nothing here may poison a frame)."""
-    from tests.gpu_util import run_hip, run_oracle
+    side, images and gradients within the usual bars (scales underflow in training; nothing here may poison a frame) -- on both blend pairs."""
+    from tests.gpu_util import blend_variants, run_oracle
     P, W, H = 6000, 240, 136
     cam, g = _scene(P, W, H, 77, 3e-3, 5e-2, 2)
     idx = np.random.default_rng(0).permutation(P)
@@ -914,21 +928,21 @@ def test_degenerate_parameters():
     bg = np.zeros(3, np.float32)
     dc, da = synthetic_upstream_grads(W, H, seed=3)
     fwd, bwd = run_oracle(g, cam, bg, 3, dc, da)
-    out = run_hip(g, cam, bg, 3, dc, da)
-    np.testing.assert_array_equal(out["radii"], fwd["radii"])
     names = ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"]
-    for a in [out["color"], out["allmap"], fwd["color"], fwd["allmap"]] + [out[n] for n in names] + [bwd[n] for n in names]:
-        assert np.isfinite(np.asarray(a)).all()
-    _check_images(out, fwd, "degenerate")
-    _check_grads(out, bwd, names, "degenerate")
+    for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 3, dc, da)):
+        np.testing.assert_array_equal(out["radii"], fwd["radii"])
+        for a in [out["color"], out["allmap"], fwd["color"], fwd["allmap"]] + [out[n] for n in names] + [bwd[n] for n in names]:
+            assert np.isfinite(np.asarray(a)).all(), kernel
+        _check_images(out, fwd, "degenerate " + kernel)
+        _check_grads(out, bwd, names, "degenerate " + kernel)
 
 
 def test_non_finite_parameters_do_not_spread():
     """A diverging training run hands the operator NaN / Inf parameters.  A Gaussian whose centre, scales or rotation are not finite is culled
     (radius 0, no gradient); one whose opacity or SH coefficients are not finite still renders (`min(0.99, NaN)` is 0.99 here as in the
     reference's CUDA) and may carry non-finite gradients in ITS OWN rows -- in every case the images stay finite and no other Gaussian's
-    gradient row is touched."""
-    from tests.gpu_util import run_hip
+    gradient row is touched.  Both blend pairs (blend_variants: their non-finite elements must coincide, the finite ones agree)."""
+    from tests.gpu_util import blend_variants
     P, W, H = 6000, 240, 136
     cam, g = _scene(P, W, H, 3, 3e-3, 5e-2, 2)
     dc, da = synthetic_upstream_grads(W, H, seed=3)
@@ -941,15 +955,15 @@ def test_non_finite_parameters_do_not_spread():
         if field == "means3D": gg[field][idx, 2] = val
         elif field == "shs": gg[field][idx, 0, 0] = val
         else: gg[field][idx, 0] = val
-        out = run_hip(gg, cam, [0.1, 0.2, 0.3], 3, dc, da)
-        tag = f"{field} = {val}"
-        assert np.isfinite(out["color"]).all() and np.isfinite(out["allmap"]).all(), tag
-        bad = {k: ~np.isfinite(np.asarray(out[k]).reshape(P, -1)).all(1) for k in names}
-        assert not any(b[healthy].any() for b in bad.values()), f"{tag}: a healthy Gaussian has a non-finite gradient row"
-        if field in ("means3D", "scales", "rotations"):
-            assert not out["radii"][idx.numpy()].any() and not any(b.any() for b in bad.values()), f"{tag}: the poisoned Gaussians must be culled"
-            for k in names:
-                assert not np.asarray(out[k]).reshape(P, -1)[idx.numpy()].any(), f"{tag}: {k} of a culled Gaussian is not zero"
+        for kernel, out in zip(("one_wave", "coop"), blend_variants(gg, cam, [0.1, 0.2, 0.3], 3, dc, da)):
+            tag = f"{field} = {val} {kernel}"
+            assert np.isfinite(out["color"]).all() and np.isfinite(out["allmap"]).all(), tag
+            bad = {k: ~np.isfinite(np.asarray(out[k]).reshape(P, -1)).all(1) for k in names}
+            assert not any(b[healthy].any() for b in bad.values()), f"{tag}: a healthy Gaussian has a non-finite gradient row"
+            if field in ("means3D", "scales", "rotations"):
+                assert not out["radii"][idx.numpy()].any() and not any(b.any() for b in bad.values()), f"{tag}: the poisoned Gaussians must be culled"
+                for k in names:
+                    assert not np.asarray(out[k]).reshape(P, -1)[idx.numpy()].any(), f"{tag}: {k} of a culled Gaussian is not zero"
 
 
 def test_wide_frame_with_few_gaussians_and_counter_variant_errors():
@@ -1196,3 +1210,77 @@ def test_row_mapped_backward_equals_the_one_wave_backward(size, kernel="rows"):
         scale = np.abs(one[k]).max() + 1e-30
         assert np.abs(rows[k] - one[k]).max() <= bar("class_grads_vs_operator") * scale, f"{k}: row-mapped vs one-wave differ by {np.abs(rows[k] - one[k]).max() / scale:.2e} of the tensor scale"
         assert_grads_close(rows[k], bwd[k], bar("oracle32_grad_rel"), kernel + " " + k)
+
+
+@pytest.mark.parametrize("W,H,picked", [(1808, 368, "coop"), (1800, 360, "coop"), (1664, 400, "one_wave"), (1657, 393, "one_wave")])
+def test_blend_pair_selection_at_the_tile_count_threshold(W, H, picked):
+    """The default blend pair on frames just either side of kCoopBelowTiles (csrc/render_bwd.hip): 2 599 tiles of 16x16 (113 x 23, even and
+    ragged) take the cooperative pair, 2 600 (104 x 25, even and ragged) the one-wave pair -- the default's gradients bit for bit those of
+    the forced kernel.  On the even 2 600-tile frame both kernels also meet the float32 oracle's bars."""
+    from tests.bars import bar
+    from tests.gpu_util import COOP_BELOW_TILES, blend_variants, run_hip, run_oracle
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    assert tiles == (COOP_BELOW_TILES - 1 if picked == "coop" else COOP_BELOW_TILES)
+    P = 30_000
+    cam = synthetic_camera(W, H, index=2)
+    g = synthetic_gaussians(P, W, H, seed=W + H, scale_lo=1e-3, scale_hi=8e-3)
+    dc, da = synthetic_upstream_grads(W, H, seed=W)
+    bg = np.array([0.2, 0.3, 0.1], np.float32)
+    one, coop = blend_variants(g, cam, bg, 3, dc, da)   # (holds the default to the kernel the rule picks, among the rest)
+    default, forced = run_hip(g, cam, bg, 3, dc, da), run_hip(g, cam, bg, 3, dc, da, backward_kernel=picked)   # (GaussianRasterizer(backward_kernel=))
+    names = ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"]
+    for k in names:
+        assert np.array_equal(default[k], (coop if picked == "coop" else one)[k]), f"{W}x{H} ({tiles} tiles) {k}: the default is not the {picked} kernel"
+        assert np.array_equal(forced[k], default[k]), f"{W}x{H} {k}: backward_kernel={picked!r} differs from the default"
+    if (W, H) == (1664, 400):
+        fwd, bwd = run_oracle(g, cam, bg, 3, dc, da)
+        for kernel, out in (("one_wave", one), ("coop", coop)):
+            _check_images(out, fwd, f"{W}x{H} {kernel}")
+            _check_grads(out, bwd, names, f"{W}x{H} {kernel}", rel=bar("oracle32_grad_rel"))
+
+
+def test_conflicting_blend_pair_flags_are_refused(monkeypatch):
+    """SR_FLAG_ONE_WAVE_BACKWARD, SR_FLAG_COOP_BACKWARD and SR_FLAG_ROW_BACKWARD pick the blend pair of a frame; two or three of them in one call
+    used to run a forward and a backward that disagree on the hit-mask format (ROW + COOP: quadrant masks written, 4x4-cell masks read --
+    silently wrong gradients).  Now the forward and the backward refuse every such combination by name, and the backward checks the
+    row-mapped pair's preconditions as the forward does."""
+    from diff_surfel_rasterization import _C
+    from streetunveiler_amd import _lib
+    from tests.gpu_util import DEV, settings_for
+    W, H, P = 96, 64, 500
+    cam, g = _scene(P, W, H, 5, 5e-3, 5e-2)
+    dc, da = synthetic_upstream_grads(W, H, seed=1)
+    s = settings_for(cam, [0.1, 0.2, 0.3], 3)
+    e = torch.empty(0, device=DEV)
+    d = {k: v.to(DEV) for k, v in g.items()}
+    flag = {"one_wave": _lib.SR_FLAG_ONE_WAVE_BACKWARD, "coop": _lib.SR_FLAG_COOP_BACKWARD, "rows": _lib.SR_FLAG_ROW_BACKWARD}
+
+    def forward(kernel, tile=None):
+        return _C.rasterize_gaussians(s.bg, d["means3D"], e, d["opacities"], d["scales"], d["rotations"], 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx,
+                                      s.tanfovy, H, W, d["shs"], 3, s.campos, False, False, tile=tile, backward_kernel=kernel)
+
+    def backward(state, kernel, tile=None):
+        D, _, _, radii, geom, binning, img = state
+        out = _C.rasterize_gaussians_backward(s.bg, d["means3D"], radii, e, d["scales"], d["rotations"], 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx,
+                                              s.tanfovy, dc.to(DEV), da.to(DEV), d["shs"], 3, s.campos, geom, D, binning, img, False, tile=tile,
+                                              backward_kernel=kernel)
+        torch.cuda.synchronize()
+        return out
+
+    for kernel, extra in [("coop", ["rows"]), ("rows", ["coop"]), ("one_wave", ["coop"]), ("one_wave", ["rows"]), ("coop", ["one_wave", "rows"])]:
+        state = forward(kernel)   # (one flag: a frame like any other)
+        assert float(backward(state, kernel)[3].abs().max()) > 0, kernel
+        monkeypatch.setattr(_C, "_EXTRA_FLAGS", sum(flag[x] for x in extra))   # (read at call time: OR-ed into SrFrame.flags)
+        with pytest.raises(_lib.SurfelRasterError, match="exclude each other"):
+            forward(kernel)
+        with pytest.raises(_lib.SurfelRasterError, match="exclude each other"):
+            backward(state, kernel)
+        monkeypatch.setattr(_C, "_EXTRA_FLAGS", 0)
+    # the row-mapped pair's preconditions in the backward: the 16x16 tile, culling on
+    state8 = forward(None, tile=(8, 8))
+    with pytest.raises(_lib.SurfelRasterError, match="SR_FLAG_ROW_BACKWARD"):
+        backward(state8, "rows", tile=(8, 8))
+    state = forward("rows")
+    monkeypatch.setattr(_C, "_EXTRA_FLAGS", _lib.SR_FLAG_NO_QUADRANT_CULL)
+    with pytest.raises(_lib.SurfelRasterError, match="SR_FLAG_ROW_BACKWARD"):
+        backward(state, "rows")

@@ -27,20 +27,29 @@ SCENES = [  # P, W, H, seed, scale_lo, scale_hi, camera index, SH degree, tile
 
 @pytest.mark.parametrize("scene", SCENES)
 def test_strict_parity_with_identical_decisions(scene):
-    from tests.gpu_util import assert_strict_parity, forced_f64_reference, run_hip
+    from tests.gpu_util import assert_strict_parity, blend_variants, forced_f64_reference, run_hip
     P, W, H, seed, lo, hi, idx, deg, tile = scene
     cam = synthetic_camera(W, H) if idx is None else synthetic_camera(W, H, index=idx)
     g = synthetic_gaussians(P, W, H, seed=seed, scale_lo=lo, scale_hi=hi)
     g["opacities"][::9] = 1.0
     dc, da = synthetic_upstream_grads(W, H, seed=seed + 1)
     bg = [0.3, 0.1, 0.6]
-    hip = run_hip(g, cam, bg, deg, dc, da, tile=tile)
+    if tile is None:   # the 16x16 tile: both blend pairs against the same forced-decision reference (the forward is identical: blend_variants)
+        runs = list(zip(("one_wave ", "coop "), blend_variants(g, cam, bg, deg, dc, da)))
+    else:              # the flags that force a pair are documented for 16x16 only: on other shapes they change nothing
+        hip = run_hip(g, cam, bg, deg, dc, da, tile=tile)
+        for kernel in ("one_wave", "coop"):
+            forced = run_hip(g, cam, bg, deg, dc, da, tile=tile, backward_kernel=kernel)
+            for k, v in hip.items():
+                assert np.array_equal(forced[k], v), f"tile {tile}: backward_kernel={kernel!r} changes {k}"
+        runs = [("", hip)]
     raw, fwd64, bwd64 = forced_f64_reference(g, cam, bg, deg, dc, da, tile=tile)
-    np.testing.assert_array_equal(hip["radii"], fwd64["radii"])
-    np.testing.assert_array_equal(raw["color"], hip["color"])          # the decision dump describes this very forward
     report = {}
     try:
-        assert_strict_parity(hip, fwd64, bwd64, report=report, scene=(g, cam))
+        for tag, hip in runs:
+            np.testing.assert_array_equal(hip["radii"], fwd64["radii"])
+            np.testing.assert_array_equal(raw["color"], hip["color"])          # the decision dump describes this very forward
+            assert_strict_parity(hip, fwd64, bwd64, tag=tag, report=report, scene=(g, cam))
     finally:
         out = os.environ.get("SR_PARITY_REPORT")
         if out:
@@ -50,7 +59,7 @@ def test_strict_parity_with_identical_decisions(scene):
 
 def test_strict_parity_precomputed_colours_and_empty_tiles():
     """colors_precomp as the colour source; a scene that leaves most tiles empty and one that ends lists early (opaque wall)."""
-    from tests.gpu_util import assert_strict_parity, forced_f64_reference, run_hip
+    from tests.gpu_util import assert_strict_parity, blend_variants, forced_f64_reference
     W, H, P = 176, 112, 2500
     cam = synthetic_camera(W, H, index=4)
     g = synthetic_gaussians(P, W, H, seed=21, scale_lo=4e-3, scale_hi=4e-2)
@@ -58,6 +67,7 @@ def test_strict_parity_precomputed_colours_and_empty_tiles():
     g["opacities"][:400] = 0.995                                   # saturating front layer
     colors = torch.rand(P, 3, generator=torch.Generator().manual_seed(2)).numpy()
     dc, da = synthetic_upstream_grads(W, H, seed=5)
-    hip = run_hip(g, cam, [0, 0, 0], 0, dc, da, colors=colors)
+    one, coop = blend_variants(g, cam, [0, 0, 0], 0, dc, da, colors=colors)
     raw, fwd64, bwd64 = forced_f64_reference(g, cam, [0, 0, 0], 0, dc, da, colors=colors)
-    assert_strict_parity(hip, fwd64, bwd64, scene=(g, cam))
+    for tag, hip in (("one_wave ", one), ("coop ", coop)):
+        assert_strict_parity(hip, fwd64, bwd64, tag=tag, scene=(g, cam))
