@@ -121,7 +121,9 @@ def _mask(mask, P, dev):
 
 def _channels(colors_precomp):
     """3 as in the reference, or 6: two 3-channel passes over the same geometry folded into one."""
-    if colors_precomp is None or colors_precomp.numel() == 0:
+    # (not given: None or the reference's empty placeholder.  A [0, 3] / [0, 6] array -- a frame with no Gaussians -- still says how many
+    # channels the caller renders: it used to count as "not given", and a 6- / 9-channel call with P == 0 was refused for its 6- / 9-entry bg)
+    if colors_precomp is None or (colors_precomp.numel() == 0 and not (colors_precomp.ndim == 2 and colors_precomp.shape[0] == 0 and colors_precomp.shape[1] in (3, 6))):
         return 3
     nc = int(colors_precomp.shape[-1])
     if colors_precomp.ndim != 2 or nc not in (3, 6):
@@ -131,7 +133,7 @@ def _channels(colors_precomp):
 
 def _gaussians(means3D, opacities, scales, rotations, sh, colors_precomp, transMat_precomp, activations=0, mask=None):
     P = int(means3D.shape[0])
-    M = int(sh.shape[1]) if sh is not None and sh.numel() else 0
+    M = int(sh.shape[1]) if sh is not None and (sh.numel() or (P == 0 and sh.ndim == 3)) else 0   # (sh[0, M, 3]: no Gaussians, SH colour all the same)
     NC = _channels(colors_precomp)
     if M and NC == 6:
         NC = 9   # SH colour + six precomputed channels in one pass

@@ -21,9 +21,9 @@ from diff_surfel_rasterization import GaussianRasterizer
 from streetunveiler_amd.synthetic import posed_scene, synthetic_camera, synthetic_gaussians
 from tests import gpu_util as gu
 from tests.bars import bar
+from tests.gpu_util import KEYS, _Sum, _check_rows   # noqa: F401  (shared with tests/test_gpu_blend_matrix.py)
 
 pytestmark = pytest.mark.gpu
-KEYS = dict(means3D="dL_dmeans3D", opacities="dL_dopacity", scales="dL_dscales", rotations="dL_drotations", means2D="dL_dmeans2D")
 W, H, P, N_CLS = 352, 208, 24_000, 5
 
 
@@ -36,30 +36,6 @@ def _scene(tile):
     cls = torch.randint(-1, N_CLS + 1, (P,), generator=gen)   # -1 and N_CLS: in no class
     gd = torch.rand(N_CLS, H, W, generator=gen) + 0.5
     return cam, g, cls, gd
-
-
-class _Sum:
-    """Float64 gradients of several renders, scattered to the full set of Gaussians and summed; robust = robust in every render."""
-
-    def __init__(self, g):
-        self.P = g["means3D"].shape[0]
-        self.acc, self.acc32, self.robust, self.visible = {}, {}, np.ones(self.P, bool), np.zeros(self.P, bool)
-
-    def add(self, idx, fwd64, bwd64, margins, bwd32=None):
-        """bwd32 = the float32 oracle's backward of the same render: the restatement of the reference's own float32 formulation, summed the
-        same way -- what "no worse than the reference's arithmetic" is measured against (gpu_util.assert_free_parity's oracle32 rule)."""
-        idx = np.arange(self.P) if idx is None else np.nonzero(idx)[0]
-        for src, dst in ((bwd64, self.acc), (bwd32 or {}, self.acc32)):
-            for key, v in src.items():
-                if not key.startswith("dL_") or key in ("dL_dcolors", "dL_dcolors64", "dL_dsh", "dL_dsh64"):   # (colour-side gradients: one render each)
-                    continue
-                v = np.asarray(v, np.float64).reshape(len(idx), -1)
-                if key not in dst:
-                    dst[key] = np.zeros((self.P, v.shape[1]))
-                dst[key][idx] += v
-        vis = fwd64["radii"] > 0
-        self.visible[idx] |= vis
-        self.robust[idx] &= (margins["gaussian"] > 1.0) | ~vis
 
 
 def _class_references(g, cam, tile, cls, gd, total):
@@ -88,34 +64,6 @@ def _check_maps(dist, radii, refs, tag):
         assert err[rob].max(initial=0.0) <= bar("robust_pixel"), f"{tag} class {k}: distortion map off by {err[rob].max():.3e} of (1 + |v|) at a robust pixel"
         assert err[~rob].max(initial=0.0) <= bar("nonrobust_pixel_cap"), f"{tag} class {k}: distortion map off by {err[~rob].max():.3e} at a non-robust pixel"
         assert (~rob).mean() <= bar("nonrobust_pixel_budget"), f"{tag} class {k}: {(~rob).mean():.3f} of the pixels non-robust"
-
-
-def _check_rows(grads, total, g, cam, tag, skip=(), oracle32_factor=0.5):
-    hip = {KEYS[n]: v for n, v in grads.items() if n in KEYS}
-    ref = {k: v for k, v in total.acc.items()}
-    errs = gu.gradient_row_errors(hip, ref, np.ones(total.P, bool), scene=(g, cam))
-    # the float32 oracle's sums against the same float64 arbiter: a distortion-only loss is the variance of the depth metric along the ray,
-    # a difference of cancelling sums -- the reference's own float32 arithmetic sits well above the bars calibrated on the benchmark's
-    # all-channel gradients there, and the rule of the randomised sweeps applies: within the bar, OR at least twice as accurate as the
-    # float32 restatement of the reference on the same rows (gpu_util.assert_free_parity, `oracle32`)
-    errs32 = gu.gradient_row_errors({k: total.acc32[k] for k in hip if k in total.acc32}, ref, np.ones(total.P, bool), scene=(g, cam)) if total.acc32 else {}
-    rob = total.visible & total.robust
-    assert rob.sum() > 0.4 * total.visible.sum(), f"{tag}: only {rob.sum()} of {total.visible.sum()} visible Gaussians are robust in every render"
-    for key, e in errs.items():
-        if key in skip:
-            continue
-        p999_bar, max_bar = gu.STRICT_ROW_BARS[key]
-        er = e[rob]
-        o = errs32[key][rob] if key in errs32 else None
-        if o is not None and o.size:
-            p999_bar, max_bar = max(p999_bar, oracle32_factor * float(np.quantile(o, 0.999))), max(max_bar, float(o.max()))
-        print(f"{tag} {key}: robust rows p99.9 {np.quantile(er, 0.999):.2e} max {er.max():.2e}" + ("" if o is None else f" | float32 oracle p99.9 {np.quantile(o, 0.999):.2e} max {o.max():.2e}"))
-        assert gu.rows_within(er, p999_bar, max_bar, e32=o), \
-            f"{tag} {key}: robust rows p99.9 {np.quantile(er, 0.999):.2e} (bar {p999_bar:.1e}), max {er.max():.2e} (bar {max_bar:.1e})"
-        r = ref.get(key + "64", ref.get(key)); a = np.asarray(hip[key], np.float64).reshape(total.P, -1)
-        loose = np.abs(a - r).max(1) / (np.abs(r).max() + 1e-30)
-        assert loose[total.visible & ~rob].max(initial=0.0) <= bar("nonrobust_row_cap"), f"{tag} {key}: a non-robust row is off by {loose[total.visible & ~rob].max():.2e} of the tensor scale"
-        assert not np.abs(a[~total.visible]).any(), f"{tag} {key}: gradient on an invisible Gaussian"
 
 
 def _leaves(g, extra=()):

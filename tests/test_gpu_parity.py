@@ -155,24 +155,15 @@ def test_cloned_gaussians_and_depth_ties():
     in every tile they touch -- the list order among them is the stable sort's (ascending index), and the blend is order-dependent.  Here
     every position is shared by 8 Gaussians with their own scales / rotations / colours, and a third of the scene sits on four depth
     planes (thousands of equal keys per tile): lists bit-exact against the oracle's 64-bit stable sort, images and gradients as usual."""
-    P, W, H = 24000, 320, 200
-    cam, g = _scene(P, W, H, 77, 3e-3, 4e-2, 4)
-    base = g["means3D"][: P // 8].clone()
-    g["means3D"] = base.repeat(8, 1).contiguous()                       # Gaussian i and i + k P/8 share a position
-    third = P // 3
-    planes = torch.tensor([2.0, 5.0, 11.0, 23.0])[torch.arange(third) % 4]
-    world_z_axis = cam.world_view_transform[:3, 2]                      # view depth = p . column 2 (camera at the origin)
-    p = g["means3D"][:third]
-    depth = p @ world_z_axis
-    g["means3D"][:third] = p * (planes / depth)[:, None]                 # along the ray: same pixel, new depth ...
-    g["scales"][:third] = g["scales"][:third] * (planes / depth)[:, None]   # ... and the same footprint
-    from tests.gpu_util import run_oracle
+    from tests.gpu_util import edge_scenes, run_oracle
+    cam, g, bg, deg, upstream, budgets = edge_scenes.ties()   # (tools/edge_scenes.py: the scene, shared with tests/test_gpu_blend_matrix.py)
     fwd, _ = run_oracle(g, cam, np.zeros(3, np.float32), 3)
     keys = fwd["depths"][fwd["radii"] > 0].view(np.uint32)
     assert np.unique(keys).size < 0.5 * keys.size, "the scene was meant to be full of equal depth keys"
     # (eight co-located Gaussians per position make every pixel's list eight times as dense in near-threshold decisions: 2.8 % of the
-    # pixels are non-robust here against ~1 % on the plain small scenes -- a classification, not an error; the robust ones hold the usual bars)
-    _full_check(cam, g, 3, np.array([0.1, 0.5, 0.2], np.float32), synthetic_upstream_grads(W, H, seed=77), "ties", pixel_budget=5e-2, gaussian_budget=0.6)
+    # pixels are non-robust here against ~1 % on the plain small scenes -- a classification, not an error; the robust ones hold the usual bars:
+    # budgets = pixel_budget 5e-2, gaussian_budget 0.6)
+    _full_check(cam, g, deg, bg, upstream, "ties", **budgets)
 
 
 def test_colors_precomp_and_transmat_precomp():
@@ -199,20 +190,16 @@ def test_colors_precomp_and_transmat_precomp():
 
 
 def test_empty_and_all_culled_inputs():
-    from tests.gpu_util import run_hip
-    W, H = 64, 48
-    cam = synthetic_camera(W, H)
-    bg = np.array([0.1, 0.2, 0.3], np.float32)
-    dc, da = synthetic_upstream_grads(W, H)
+    from tests.gpu_util import edge_scenes, run_hip
     # P == 0
-    g0 = {k: v[:0] for k, v in synthetic_gaussians(4, W, H).items()}
-    out = run_hip(g0, cam, bg, 3, dc, da)
+    cam, g0, bg, deg, (dc, da), _ = edge_scenes.no_gaussians()
+    W, H = cam.image_width, cam.image_height
+    out = run_hip(g0, cam, bg, deg, dc, da)
     np.testing.assert_allclose(out["color"], np.broadcast_to(bg[:, None, None], (3, H, W)))
     assert not out["allmap"].any() and out["radii"].shape == (0,)
     # everything behind the camera: D == 0
-    g = synthetic_gaussians(100, W, H)
-    g["means3D"][:, 2] *= -1
-    out = run_hip(g, cam, bg, 3, dc, da)
+    cam, g, bg, deg, (dc, da), _ = edge_scenes.all_culled()
+    out = run_hip(g, cam, bg, deg, dc, da)
     assert not out["radii"].any()
     np.testing.assert_allclose(out["color"], np.broadcast_to(bg[:, None, None], (3, H, W)))
     for k in ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"]:
@@ -248,16 +235,13 @@ def test_quadrant_culling_is_exact():
     """The per-quadrant culling only drops entries the per-pixel test would skip: images, per-pixel state and
     gradients with culling ON must equal culling OFF (images/state bit for bit; gradients up to the
     order of the 4-wave LDS combine)."""
-    from tests.gpu_util import run_hip, run_hip_raw
-    for (P, W, H, lo, hi, idx) in [(30000, 384, 216, 5e-4, 5e-3, None), (8000, 200, 150, 5e-3, 8e-2, 6), (3000, 160, 96, 2e-2, 3e-1, 1)]:
-        cam, g = _scene(P, W, H, P + 1, lo, hi, idx)
-        g["opacities"][::7] = 0.003   # below 1/255: can never contribute
-        g["opacities"][::11] = 1.0
-        dc, da = synthetic_upstream_grads(W, H, seed=P)
+    from tests.gpu_util import edge_scenes, run_hip, run_hip_raw
+    for which in range(len(edge_scenes.OPACITY_EXTREME_SIZES)):   # thin, medium and huge splats; opacity 0.003 (below 1/255) and 1.0 sprinkled in
+        cam, g, bg, deg, (dc, da), _ = edge_scenes.opacity_extremes(which)
         res = {}
         for cull in (1, 0):   # per call: SrFrame.flags & SR_FLAG_NO_QUADRANT_CULL
-            res[cull] = (run_hip_raw(g, cam, [0.2, 0.4, 0.6], 3, quadrant_cull=bool(cull)),
-                         run_hip(g, cam, [0.2, 0.4, 0.6], 3, dc, da, quadrant_cull=bool(cull)))
+            res[cull] = (run_hip_raw(g, cam, bg, deg, quadrant_cull=bool(cull)),
+                         run_hip(g, cam, bg, deg, dc, da, quadrant_cull=bool(cull)))
         (raw1, out1), (raw0, out0) = res[1], res[0]
         np.testing.assert_array_equal(raw1["color"], raw0["color"])
         np.testing.assert_array_equal(raw1["allmap"], raw0["allmap"])
@@ -840,12 +824,8 @@ def test_tile_shape_sweep(tile):
 def test_very_long_tile_lists_and_tiny_images():
     """One tile with a list far longer than a staging round can see (40 k translucent splats over a 24x20 image: > 600 rounds of
     64, 16-bit contributor counts exceeded), and images smaller than a tile / a single pixel -- on both blend pairs (blend_variants)."""
-    from tests.gpu_util import blend_variants, run_hip_raw, run_oracle
-    P, W, H = 40000, 24, 20
-    cam, g = _scene(P, W, H, 41, 2e-2, 2e-1, 0)
-    g["opacities"] = g["opacities"] * 0.02          # nothing saturates: every pixel walks (almost) the whole list
-    bg = np.array([0.3, 0.6, 0.9], np.float32)
-    dc, da = synthetic_upstream_grads(W, H, seed=5)
+    from tests.gpu_util import blend_variants, edge_scenes, run_hip_raw, run_oracle
+    cam, g, bg, _, (dc, da), _ = edge_scenes.long_list()   # (translucent: nothing saturates, every pixel walks (almost) the whole list)
     fwd, bwd = run_oracle(g, cam, bg, 2, dc, da)
     assert (fwd["ranges"][:, 1] - fwd["ranges"][:, 0]).max() > 20000
     assert fwd["n_contrib"][0].max() > 5000
@@ -853,9 +833,8 @@ def test_very_long_tile_lists_and_tiny_images():
     for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 2, dc, da)):
         _check_images(out, fwd, "long lists " + kernel)
         _check_grads(out, bwd, ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"], "long lists " + kernel)
-    for (w, h) in ((5, 3), (1, 1), (17, 1)):
-        cam2, g2 = _scene(300, w, h, 42, 5e-2, 5e-1, 1)
-        dc2, da2 = synthetic_upstream_grads(w, h, seed=6)
+    for (w, h) in edge_scenes.TINY_FRAMES:   # (5, 3), (1, 1), (17, 1)
+        cam2, g2, bg, _, (dc2, da2), _ = edge_scenes.tiny(w, h)
         f2, b2 = run_oracle(g2, cam2, bg, 1, dc2, da2)
         for kernel, o2 in zip(("one_wave", "coop"), blend_variants(g2, cam2, bg, 1, dc2, da2)):
             np.testing.assert_array_equal(o2["radii"], f2["radii"])
@@ -917,16 +896,8 @@ def test_extensions_short_sweep():
 def test_degenerate_parameters():
     """Zero / sub-denormal / gigantic scales, zero quaternions, opacity exactly 0 and 1: same radii, no NaN or Inf on either
     side, images and gradients within the usual bars (scales underflow in training; nothing here may poison a frame) -- on both blend pairs."""
-    from tests.gpu_util import blend_variants, run_oracle
-    P, W, H = 6000, 240, 136
-    cam, g = _scene(P, W, H, 77, 3e-3, 5e-2, 2)
-    idx = np.random.default_rng(0).permutation(P)
-    g["scales"][idx[:60], 0] = 0.0; g["scales"][idx[60:120]] = 0.0
-    g["opacities"][idx[120:180]] = 0.0; g["opacities"][idx[180:240]] = 1.0
-    g["rotations"][idx[240:300]] = 0.0
-    g["scales"][idx[300:360]] = 1e-12; g["scales"][idx[360:420]] = 50.0
-    bg = np.zeros(3, np.float32)
-    dc, da = synthetic_upstream_grads(W, H, seed=3)
+    from tests.gpu_util import blend_variants, edge_scenes, run_oracle
+    cam, g, bg, _, (dc, da), _ = edge_scenes.degenerate()
     fwd, bwd = run_oracle(g, cam, bg, 3, dc, da)
     names = ["dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"]
     for kernel, out in zip(("one_wave", "coop"), blend_variants(g, cam, bg, 3, dc, da)):
@@ -942,20 +913,15 @@ def test_non_finite_parameters_do_not_spread():
     (radius 0, no gradient); one whose opacity or SH coefficients are not finite still renders (`min(0.99, NaN)` is 0.99 here as in the
     reference's CUDA) and may carry non-finite gradients in ITS OWN rows -- in every case the images stay finite and no other Gaussian's
     gradient row is touched.  Both blend pairs (blend_variants: their non-finite elements must coincide, the finite ones agree)."""
-    from tests.gpu_util import blend_variants
-    P, W, H = 6000, 240, 136
-    cam, g = _scene(P, W, H, 3, 3e-3, 5e-2, 2)
-    dc, da = synthetic_upstream_grads(W, H, seed=3)
-    idx = torch.arange(0, P, 50)
-    healthy = np.ones(P, bool); healthy[idx.numpy()] = False
+    from tests.gpu_util import blend_variants, edge_scenes
     names = ("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D")
-    for field, val in [("means3D", float("nan")), ("means3D", float("inf")), ("scales", float("nan")), ("scales", float("inf")), ("rotations", float("nan")),
-                       ("opacities", float("nan")), ("opacities", float("inf")), ("shs", float("nan"))]:
-        gg = {k: v.clone() for k, v in g.items()}
-        if field == "means3D": gg[field][idx, 2] = val
-        elif field == "shs": gg[field][idx, 0, 0] = val
-        else: gg[field][idx, 0] = val
-        for kernel, out in zip(("one_wave", "coop"), blend_variants(gg, cam, [0.1, 0.2, 0.3], 3, dc, da)):
+    for field, val in edge_scenes.NON_FINITE_VARIANTS:   # NaN / Inf in means3D, scales, rotations, opacities, shs: eight variants
+        sc = edge_scenes.non_finite(field, val)
+        cam, gg, bg, _, (dc, da), _ = sc
+        P = gg["means3D"].shape[0]
+        idx = torch.as_tensor(sc.poisoned)   # every 50th Gaussian
+        healthy = np.ones(P, bool); healthy[idx.numpy()] = False
+        for kernel, out in zip(("one_wave", "coop"), blend_variants(gg, cam, bg, 3, dc, da)):
             tag = f"{field} = {val} {kernel}"
             assert np.isfinite(out["color"]).all() and np.isfinite(out["allmap"]).all(), tag
             bad = {k: ~np.isfinite(np.asarray(out[k]).reshape(P, -1)).all(1) for k in names}
