@@ -275,6 +275,11 @@ __device__ __forceinline__ void load_record(const float4* __restrict__ recs, uin
 #pragma unroll
     for (int k = 0; k < kRecQuads; ++k) q[k] = r[k];
 }
+// the three record quads the class pass stages (transform rows, centre, opacity); the others keep what they hold
+__device__ __forceinline__ void load_record_geometry(const float4* __restrict__ recs, uint32_t gid, float4 (&q)[kRecQuads]) {
+    const float4* r = recs + (size_t)gid * kRecQuads;
+    q[0] = r[0]; q[1] = r[1]; q[2] = r[2];
+}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -541,6 +546,196 @@ __device__ __forceinline__ uint32_t decode_hits(uint16_t h) {   // see the hit_m
     // two-band tiles (16x16, 32x16): low byte = the QX quadrant bits of the upper band, high byte = those of the lower band
     return QY == 2 ? (((uint32_t)h & ((1u << QX) - 1u)) | ((((uint32_t)h >> 8) & ((1u << QX) - 1u)) << QX)) : (uint32_t)h;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The blend backward, written once: what the three K7 kernels (render_bwd.hip: one wave per tile, cooperative, row-mapped) and the
+// per-class distortion backward (render_class.hip) have in common.  Everything here is inlined into its callers.
+// ---------------------------------------------------------------------------------------------
+// A per-entry sum takes its term by accumulation (several pixels of a lane add into registers that start from zeros) or, kAccumulate =
+// false, by assignment (the cooperative K7: one pixel per lane, so there is nothing to add to -- an accumulate into its LDS-loaded zeros
+// would cost the VALU-bound kernel ~21 vector instructions per pair, and `0 + x` is not `x` in the sign of a zero).
+template <bool kAccumulate> __device__ __forceinline__ void sum_term(float& s, float x) { s = kAccumulate ? s + x : x; }
+template <bool kAccumulate> __device__ __forceinline__ void sum_term(float& s, float a, float b) { s = kAccumulate ? fmaf(a, b, s) : a * b; }
+
+// The geometry sums of one (pixel, entry) pair, v[0..13]: on the ray-splat path the moments of dL/dp in tile-local pixel coordinates
+// (shifted to the Gaussian's own centre when the record is written: moment_shift; the cross products happen once per Gaussian in K8),
+// on the screen-space filter path dL/d(means2D).  (xq, yq): the pixel, tile-local; Twx, Twy: the staged e2.y, e2.z.
+template <bool kAccumulate, bool kFuseSx, int kLen>
+__device__ __forceinline__ void geometry_sums(const Hit& h, float xq, float yq, float Twx, float Twy, float dL_dG, float dL_dz, float (&v)[kLen]) {
+    if (h.use3d) {
+        const float gG = -dL_dG * h.G;
+        // gG s + dL_dz Tw is ONE fma and one rounded product.  Written as a plain sum, contraction fuses whichever product the optimiser
+        // leaves on the left, and that differed from instantiation to instantiation; kFuseSx pins what each kernel has always computed
+        // (true: the sx / sy product is the fused one) -- the gradients differ in the last bit between the two.
+        const float tx = kFuseSx ? fmaf(gG, h.sx, dL_dz * Twx) : fmaf(dL_dz, Twx, gG * h.sx);
+        const float ty = kFuseSx ? fmaf(gG, h.sy, dL_dz * Twy) : fmaf(dL_dz, Twy, gG * h.sy);
+        const float dpx = tx * h.pz_inv, dpy = ty * h.pz_inv;
+        const float dpz = -(dpx * h.sx + dpy * h.sy);
+        sum_term<kAccumulate>(v[0], dpx); sum_term<kAccumulate>(v[1], dpy); sum_term<kAccumulate>(v[2], dpz);
+        sum_term<kAccumulate>(v[3], xq, dpx); sum_term<kAccumulate>(v[4], xq, dpy); sum_term<kAccumulate>(v[5], xq, dpz);
+        sum_term<kAccumulate>(v[6], yq, dpx); sum_term<kAccumulate>(v[7], yq, dpy); sum_term<kAccumulate>(v[8], yq, dpz);
+        sum_term<kAccumulate>(v[9], dL_dz, h.sx); sum_term<kAccumulate>(v[10], dL_dz, h.sy);
+    } else {
+        const float gG = -dL_dG * h.G * kFilterInvSquare;
+        sum_term<kAccumulate>(v[12], gG, h.dx);
+        sum_term<kAccumulate>(v[13], gG, h.dy);
+    }
+    sum_term<kAccumulate>(v[11], dL_dz);   // (both paths)
+}
+
+// One pixel of K7: the upstream gradients folded with the forward's final accumulators, and the state of the back-to-front walk.
+struct BackwardPixel {
+    float gr, gg, gb, gn0, gn1, gn2, g_depth, g_median, a0, a1, a2;
+    float gc[6];             // upstream gradients of colour channels 3..8 (6- / 9-channel variants)
+    uint32_t lastc, medc;    // last / median contributor of the forward
+    float T, Z;              // transmittance in front of the entry the walk is at; the suffix sum (render.hip)
+};
+template <int NC>
+__device__ __forceinline__ void load_backward_pixel(const FrameDev& f, int px, int py, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                                    const float* __restrict__ dL_dcolor, const float* __restrict__ dL_dallmap, BackwardPixel& p) {
+    const size_t HW = (size_t)f.H * f.W;
+    const bool inside = px < f.W && py < f.H;
+    const size_t pix = inside ? (size_t)py * f.W + px : 0;
+    const float T_final = inside ? final_T[pix] : 0.f;
+    const float fin_D = inside ? final_T[HW + pix] : 0.f, fin_D2 = inside ? final_T[2 * HW + pix] : 0.f;
+    p.lastc = inside ? n_contrib[pix] : 0u;
+    p.medc = inside ? n_contrib[HW + pix] : 0u;
+    p.gr = inside ? dL_dcolor[pix] : 0.f; p.gg = inside ? dL_dcolor[HW + pix] : 0.f; p.gb = inside ? dL_dcolor[2 * HW + pix] : 0.f;
+    p.g_depth = inside ? dL_dallmap[pix] : 0.f;
+    const float g_accum = inside ? dL_dallmap[HW + pix] : 0.f;
+    p.gn0 = inside ? dL_dallmap[2 * HW + pix] : 0.f; p.gn1 = inside ? dL_dallmap[3 * HW + pix] : 0.f; p.gn2 = inside ? dL_dallmap[4 * HW + pix] : 0.f;
+    p.g_median = inside ? dL_dallmap[5 * HW + pix] : 0.f;
+    const float g_reg = inside ? dL_dallmap[6 * HW + pix] : 0.f;
+    float bg_dot = f.bg[0] * p.gr + f.bg[1] * p.gg + f.bg[2] * p.gb;
+    p.gc[0] = p.gc[1] = p.gc[2] = p.gc[3] = p.gc[4] = p.gc[5] = 0.f;
+    if (NC >= 6) {
+        p.gc[0] = inside ? dL_dcolor[3 * HW + pix] : 0.f; p.gc[1] = inside ? dL_dcolor[4 * HW + pix] : 0.f; p.gc[2] = inside ? dL_dcolor[5 * HW + pix] : 0.f;
+        bg_dot += f.bg[3] * p.gc[0] + f.bg[4] * p.gc[1] + f.bg[5] * p.gc[2];
+    }
+    if (NC == 9) {
+        p.gc[3] = inside ? dL_dcolor[6 * HW + pix] : 0.f; p.gc[4] = inside ? dL_dcolor[7 * HW + pix] : 0.f; p.gc[5] = inside ? dL_dcolor[8 * HW + pix] : 0.f;
+        bg_dot += f.bg[6] * p.gc[3] + f.bg[7] * p.gc[4] + f.bg[8] * p.gc[5];
+    }
+    p.a0 = (1.f - T_final) * g_reg; p.a1 = fin_D * g_reg; p.a2 = fin_D2 * g_reg;
+    p.T = T_final; p.Z = -T_final * (g_accum - bg_dot);   // the background / alpha term rides in the suffix sum
+}
+
+// The per-pair arithmetic of K7 for a pair that passed `intersect`: steps the pixel's T and Z, adds the pair's terms to the entry's sums
+// v[0..23] and returns the blend weight w (the 9-channel kernel forms three more sums from it).  e2..e6: the staged entry (e6: colour
+// channels 6..8, read with NC = 9 only).
+//   psi = rgb.g + depth g_depth + n.gn + (a2 + m (m a0 - 2 a1)), m = the depth metric; dL/dz = w (2 (m a0 - a1) dm/dz + g_depth),
+//   dm/dz = kFN kNear / depth^2.  t1 = m a0 - a1 serves both: 8 instructions where the literal transcription took 11.  (The three
+//   distortion terms cancel to the variance of m along the ray: they are combined in ONE fma before anything else is added -- seeding
+//   the colour chain with a2 saves another instruction and costs a digit under a distortion-weighted loss.)
+// kXG = false: the sums of dL/dcolors_precomp are not formed (render_bwd.hip).  kFuseSx: see geometry_sums.
+template <int NC, bool kXG, bool kAccumulate, bool kFuseSx>
+__device__ __forceinline__ float blend_backward_pair(const float4 e2, const float4 e3, const float4 e4, const float4 e5, const float4 e6, const Hit& h,
+                                                     float xq, float yq, uint32_t cidx, BackwardPixel& p, float (&v)[24]) {
+    const float one_m_inv = fast_rcp(1.f - h.alpha);
+    p.T *= one_m_inv;                 // transmittance in front of this entry
+    const float w = h.alpha * p.T;
+    float phi = fmaf(e4.w, p.gr, fmaf(e5.x, p.gg, fmaf(e5.y, p.gb, fmaf(h.depth, p.g_depth,
+                fmaf(e4.x, p.gn0, fmaf(e4.y, p.gn1, e4.z * p.gn2))))));
+    if (NC >= 6) phi = fmaf(e5.z, p.gc[0], fmaf(e5.w, p.gc[1], fmaf(e3.w, p.gc[2], phi)));
+    if (NC == 9) phi = fmaf(e6.x, p.gc[3], fmaf(e6.y, p.gc[4], fmaf(e6.z, p.gc[5], phi)));
+    const float inv_depth = fast_rcp(h.depth);
+    const float m_d = fmaf(inv_depth, -kFN * kNear, kFN);
+    const float t1 = fmaf(m_d, p.a0, -p.a1);
+#if SR_DETACH_WEIGHT
+    const float psi = phi;   // upstream DETACH_WEIGHT: the distortion does not differentiate through the blend weights
+#else
+    const float psi = phi + fmaf(m_d, t1 - p.a1, p.a2);
+#endif
+    const float dL_dalpha = p.T * psi - one_m_inv * p.Z;
+    p.Z = fmaf(w, psi, p.Z);
+    const float med_add = (cidx == p.medc - (SR_MEDIAN_CONTRIBUTOR_MINUS_ONE ? 1u : 0u)) ? p.g_median : 0.f;
+    const float dL_dz = fmaf(w, fmaf(t1 * (inv_depth * inv_depth), 2.f * kFN * kNear, p.g_depth), med_add);
+    const float dL_dG = e3.z * dL_dalpha;
+    if (NC != 6 || kXG) { sum_term<kAccumulate>(v[18], w * p.gr); sum_term<kAccumulate>(v[19], w * p.gg); sum_term<kAccumulate>(v[20], w * p.gb); }   // (6 channels: all of them precomputed)
+    if (NC >= 6 && kXG) { sum_term<kAccumulate>(v[21], w * p.gc[0]); sum_term<kAccumulate>(v[22], w * p.gc[1]); sum_term<kAccumulate>(v[23], w * p.gc[2]); }
+    sum_term<kAccumulate>(v[15], w * p.gn0); sum_term<kAccumulate>(v[16], w * p.gn1); sum_term<kAccumulate>(v[17], w * p.gn2);
+    sum_term<kAccumulate>(v[14], h.G * dL_dalpha);
+    geometry_sums<kAccumulate, kFuseSx>(h, xq, yq, e2.y, e2.z, dL_dG, dL_dz, v);
+    return w;
+}
+
+// The shift of the moments Sx, Sy from tile-local coordinates to coordinates relative to the Gaussian's OWN centre (cx, cy): sum (xl - mx) dp
+// = sum xl dp - mx S0 with mx = cx - Xc.  K8 sums these over the Gaussian's tiles and works with Tu - cx Tw, Tv - cy Tw: the same dL/dT as
+// with moments about the image origin, without the cancellation of pixel coordinates ~1000 against extents of a few pixels (clamped into the
+// image: the moments of a splat whose centre projects far off-screen are taken about the nearest image point).
+__device__ __forceinline__ void moment_shift(const float4 (&q)[kRecQuads], float Xc, float Yc, const FrameDev& f, float& ox, float& oy) {
+    const float mx = q[2].y - Xc, my = q[2].z - Yc;   // (the staged centre: same expression, same bits as stage_entry's)
+    ox = -fminf(fmaxf(mx, -Xc), (float)(f.W - 1) - Xc); oy = -fminf(fmaxf(my, -Yc), (float)(f.H - 1) - Yc);
+}
+// Clears the lane's row of s_out for the round that begins; kShiftInLds: the shift waits for the flush in slots 22, 23 of the row
+template <int kGQ, bool kShiftInLds>
+__device__ __forceinline__ void reset_record_row(float* row, float ox, float oy) {
+    float4* z = reinterpret_cast<float4*>(row);
+#pragma unroll
+    for (int k = 0; k < kGQ; ++k) z[k] = (kShiftInLds && k == 5) ? make_float4(0.f, 0.f, ox, oy) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// The memory pipeline of the backward walk.  Nothing that comes back from memory is touched in the round that asks for it:
+//   * the list entry (gid) of round r - 2 is requested during round r, the record of round r - 1 (address = that gid, which arrived a
+//     round ago) too, RAW -- first[] and first_base[] stay two registers and the hit mask stays undecoded until round r - 1 stages them;
+//   * the records of round r are STORED at the top of round r - 1, behind its staging and behind this prefetch: the wave's vector-memory
+//     counter retires in issue order, so the wait at the top of the round (wait_vector_memory, on every path) has the same number of
+//     younger memory operations behind the last load on every path: none.
+// A dependent `gid = list[pos]; record(gid); first[gid] + first_base[..]` inside the round made the wave wait for two memory round trips
+// (and for the stores of the previous flush in front of them) in EVERY round: SQ_WAIT_INST_ANY was 26 % of the wave cycles
+// (profiles/r05_c3_sq_counters.json).
+// NC: the colour channels of the caller (6 / 9: channels 3.. come from `extra`, see stage_entry); 0 = geometry only (the class pass: the
+// three geometry quads and the radius word that emission_index reads).  `idx`: the entry of a round this lane stages.
+template <int NC>
+struct WalkPrefetch {
+    float4 nr[kRecQuads], nx = make_float4(0.f, 0.f, 0.f, 0.f), ny = nx;   // the record; colour channels 3.. (NC = 6 / 9)
+    uint32_t nfirst = 0, nfbase = 0, nhraw = 0, gid_ahead = 0;
+    __device__ __forceinline__ void fetch(const FrameDev& f, const float4* __restrict__ recs, const float* __restrict__ extra, const uint16_t* __restrict__ hit_mask,
+                                          uint32_t gid, uint32_t pos) {
+        if (NC == 0) {
+            load_record_geometry(recs, gid, nr);
+            nr[4].w = reinterpret_cast<const float*>(recs + (size_t)gid * kRecQuads + 4)[3];
+        } else {
+            load_record(recs, gid, nr);
+        }
+        nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
+        if (NC == 6) nx = load_extra(extra, gid, 3);
+        if (NC == 9) { nx = load_extra(extra, gid, 0); ny = load_extra(extra, gid, 3); }
+        nhraw = hit_mask[pos];
+    }
+    // before the walk: the deepest round's record, the list entry of the round in front of it (every round but the last one is full);
+    // stages: this lane stages entries at all (the cooperative K7: sixteen lanes per wave)
+    __device__ __forceinline__ void begin(const FrameDev& f, const float4* __restrict__ recs, const float* __restrict__ extra, const uint16_t* __restrict__ hit_mask,
+                                          const uint32_t* __restrict__ list, uint32_t list_begin, int rounds, uint32_t total, int idx, bool stages = true) {
+        if (NC == 0) {   // (geometry only: the quads fetch() does not load are zeros)
+#pragma unroll
+            for (int i = 0; i < kRecQuads; ++i) nr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (stages && rounds > 0 && (uint32_t)((rounds - 1) * kWave + idx) < total) {
+            const uint32_t pos = list_begin + (rounds - 1) * kWave + idx;
+            fetch(f, recs, extra, hit_mask, list[pos], pos);
+        }
+        if (stages && rounds > 1) gid_ahead = list[list_begin + (rounds - 2) * kWave + idx];
+    }
+    // in round rd (entries rbase ..), behind its staging and in front of its flush
+    __device__ __forceinline__ void advance(const FrameDev& f, const float4* __restrict__ recs, const float* __restrict__ extra, const uint16_t* __restrict__ hit_mask,
+                                            const uint32_t* __restrict__ list, uint32_t list_begin, int rd, uint32_t rbase, int idx) {
+        if (rd > 0) {   // (the next round is always full)
+            fetch(f, recs, extra, hit_mask, gid_ahead, list_begin + rbase - kWave + idx);
+            if (rd > 1) gid_ahead = list[list_begin + rbase - 2 * kWave + idx];
+        }
+    }
+};
+
+// Tile shapes (BASELINE config 5's sweep): the reference's 16x16 plus 8x8, 16x8, 32x8, 32x16 = QX x QY quadrants of 8x8
+// pixels, i.e. 1 / 2 / 4 / 8 pixels per lane.  (In a launcher: `f` is its FrameDev, an unknown shape returns from it.)
+#define SR_FOR_TILE_SHAPE(F)                                                    \
+    if (f.tile_w == 16 && f.tile_h == 16) { F(2, 2); }                          \
+    else if (f.tile_w == 8 && f.tile_h == 8) { F(1, 1); }                       \
+    else if (f.tile_w == 16 && f.tile_h == 8) { F(2, 1); }                      \
+    else if (f.tile_w == 32 && f.tile_h == 8) { F(4, 1); }                      \
+    else if (f.tile_w == 32 && f.tile_h == 16) { F(4, 2); }                     \
+    else return hipErrorInvalidValue;
 
 
 }  // namespace sr

@@ -660,15 +660,7 @@ __global__ __launch_bounds__(kWave) void pair_decisions_kernel(FrameDev f, const
 }
 
 // launchers ---------------------------------------------------------------------------------------
-// Tile shapes (BASELINE config 5's sweep): the reference's 16x16 plus 8x8, 16x8, 32x8, 32x16 = QX x QY quadrants of 8x8
-// pixels, i.e. 1 / 2 / 4 / 8 pixels per lane.  Every shape carries the 6- / 9-channel passes; only the reference shape the counter variant.
-#define SR_FOR_TILE_SHAPE(F)                                                    \
-    if (f.tile_w == 16 && f.tile_h == 16) { F(2, 2); }                          \
-    else if (f.tile_w == 8 && f.tile_h == 8) { F(1, 1); }                       \
-    else if (f.tile_w == 16 && f.tile_h == 8) { F(2, 1); }                      \
-    else if (f.tile_w == 32 && f.tile_h == 8) { F(4, 1); }                      \
-    else if (f.tile_w == 32 && f.tile_h == 16) { F(4, 2); }                     \
-    else return hipErrorInvalidValue;
+// Tile shapes: SR_FOR_TILE_SHAPE (blend_common.h).  Every shape carries the 6- / 9-channel passes; only the reference shape the counter variant.
 
 // (bit 5 of `flags`: the cooperative forward -- measured and NOT picked by itself: see render_forward_coop_kernel;
 //  bit 6: the row-mapped kernel writing CELL-granular hit masks -- what render_backward_rows_kernel reads; 16x16, three channels, culling on)

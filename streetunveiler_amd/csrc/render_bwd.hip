@@ -73,78 +73,30 @@ void render_backward_kernel(FrameDev f, const uint2* __restrict__ ranges, const 
     const float Xc = (float)(tx0 + QX * 4), Yc = (float)(tile_y0 + QY * 4 * BANDS);   // the TILE's centre: the local origin of staging and moments
     const int lx = lane & 7, ly = lane >> 3;
     const uint2 range = ranges[tile];
-    const uint32_t count = range.y - range.x;
-    const size_t HW = (size_t)f.H * f.W;
-    const float bg0 = f.bg[0], bg1 = f.bg[1], bg2 = f.bg[2];
   for (int band = 0; band < BANDS; ++band) {
     const int ty0 = tile_y0 + band * (QY * 8);
     if (BANDS > 1 && band > 0) __threadfence();   // the first walk's records and `written` flags, visible to this wave's loads
 
-    // per-pixel constants (upstream gradients folded with the forward's final accumulators) and state
     const float xl0 = (float)(lx - QX * 4), yl0 = (float)(ly - QY * 4 * BANDS + band * (QY * 8));   // tile-local pixel of quadrant 0; quadrant q adds 8*(q%QX, q/QX)
-    float gr[NQ], gg[NQ], gb[NQ], gn0[NQ], gn1[NQ], gn2[NQ], g_depth[NQ], g_median[NQ], a0[NQ], a1[NQ], a2[NQ];
-    float gc3[NQ], gc4[NQ], gc5[NQ], gc6[NQ], gc7[NQ], gc8[NQ];   // only live in the 6- / 9-channel variants
-    uint32_t lastc[NQ], medc[NQ], quad_last[NQ];
-    float T[NQ], Z[NQ];
+    BackwardPixel px[NQ];
+    uint32_t quad_last[NQ];
     uint32_t total = 0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        const int px = tx0 + (q % QX) * 8 + lx, py = ty0 + (q / QX) * 8 + ly;
-        const bool inside = px < f.W && py < f.H;
-        const size_t pix = inside ? (size_t)py * f.W + px : 0;
-        const float T_final = inside ? final_T[pix] : 0.f;
-        const float fin_D = inside ? final_T[HW + pix] : 0.f, fin_D2 = inside ? final_T[2 * HW + pix] : 0.f;
-        lastc[q] = inside ? n_contrib[pix] : 0u;
-        medc[q] = inside ? n_contrib[HW + pix] : 0u;
-        gr[q] = inside ? dL_dcolor[pix] : 0.f; gg[q] = inside ? dL_dcolor[HW + pix] : 0.f; gb[q] = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-        g_depth[q] = inside ? dL_dallmap[pix] : 0.f;
-        const float g_accum = inside ? dL_dallmap[HW + pix] : 0.f;
-        gn0[q] = inside ? dL_dallmap[2 * HW + pix] : 0.f; gn1[q] = inside ? dL_dallmap[3 * HW + pix] : 0.f; gn2[q] = inside ? dL_dallmap[4 * HW + pix] : 0.f;
-        g_median[q] = inside ? dL_dallmap[5 * HW + pix] : 0.f;
-        const float g_reg = inside ? dL_dallmap[6 * HW + pix] : 0.f;
-        float bg_dot = bg0 * gr[q] + bg1 * gg[q] + bg2 * gb[q];
-        gc3[q] = gc4[q] = gc5[q] = gc6[q] = gc7[q] = gc8[q] = 0.f;
-        if (NC >= 6) {
-            gc3[q] = inside ? dL_dcolor[3 * HW + pix] : 0.f; gc4[q] = inside ? dL_dcolor[4 * HW + pix] : 0.f; gc5[q] = inside ? dL_dcolor[5 * HW + pix] : 0.f;
-            bg_dot += f.bg[3] * gc3[q] + f.bg[4] * gc4[q] + f.bg[5] * gc5[q];
-        }
-        if (NC == 9) {
-            gc6[q] = inside ? dL_dcolor[6 * HW + pix] : 0.f; gc7[q] = inside ? dL_dcolor[7 * HW + pix] : 0.f; gc8[q] = inside ? dL_dcolor[8 * HW + pix] : 0.f;
-            bg_dot += f.bg[6] * gc6[q] + f.bg[7] * gc7[q] + f.bg[8] * gc8[q];
-        }
-        a0[q] = (1.f - T_final) * g_reg; a1[q] = fin_D * g_reg; a2[q] = fin_D2 * g_reg;
-        T[q] = T_final; Z[q] = -T_final * (g_accum - bg_dot);   // the background / alpha term rides in the suffix sum
-        quad_last[q] = wave_max_u32(lastc[q]);  // deepest entry any pixel of quadrant q needs (uniform)
+        load_backward_pixel<NC>(f, tx0 + (q % QX) * 8 + lx, ty0 + (q / QX) * 8 + ly, final_T, n_contrib, dL_dcolor, dL_dallmap, px[q]);
+        quad_last[q] = wave_max_u32(px[q].lastc);  // deepest entry any pixel of quadrant q needs (uniform)
         total = max(total, quad_last[q]);
     }
 
     // entries behind the deepest contributor of the tile are never looked at: they get no record and keep a clear `written` flag
-    //
-    // Memory pipeline of the walk (round 6).  Nothing that comes back from memory is touched in the round that asks for it:
-    //   * the list entry (gid) of round r - 2 is requested during round r, the record of round r - 1 (address = that gid, which arrived a
-    //     round ago) too, RAW -- first[] and first_base[] stay two registers and the hit mask stays undecoded until round r - 1 stages them;
-    //   * the records of round r are STORED at the top of round r - 1, behind its staging: the wave's vector-memory counter retires in
-    //     issue order, so the wait for round r - 1's record loads -- issued before those stores -- never waits for a store.
-    // Before: `gid = point_list[pos]; load_record(recs, gid, ...)` and `first[gid] + first_base[..]` inside the prefetch made the wave wait
-    // for two dependent memory round trips (and for the stores of the previous flush in front of them) in EVERY round -- SQ_WAIT_INST_ANY was
-    // 26 % of the wave cycles (profiles/r05_c3_sq_counters.json).
     const int rounds = (int)((total + kWave - 1) / kWave);
-    float4 nr[kRecQuads], nx = make_float4(0.f, 0.f, 0.f, 0.f), ny = nx;
-    uint32_t nfirst = 0, nfbase = 0, nhraw = 0, gid_ahead = 0;
-    if (rounds > 0 && (uint32_t)((rounds - 1) * kWave + lane) < total) {
-        const uint32_t pos = range.x + (rounds - 1) * kWave + lane;
-        const uint32_t gid = point_list[pos];
-        load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-        if (NC == 6) nx = load_extra(extra, gid, 3);
-        if (NC == 9) { nx = load_extra(extra, gid, 0); ny = load_extra(extra, gid, 3); }
-        nhraw = hit_mask[pos];
-    }
-    if (rounds > 1) gid_ahead = point_list[range.x + (rounds - 2) * kWave + lane];   // (every round but the last one is full)
+    WalkPrefetch<NC> pf;
+    pf.begin(f, recs, extra, hit_mask, point_list, range.x, rounds, total, lane);
     // (with 21 values the lanes of value slots 21..23 hold copies of other totals: they must not reach s_out, whose slots 22, 23 are in use)
     const bool holds_total = reduce24_holds_total(lane) && (NC != 3 || reduce24_index(lane) < 21);
     bool pend = false;             // this lane holds a record of the previous round that is not stored yet
     uint32_t pslot = 0;
-    // the shift of the moments to the Gaussian's own centre (see the staging below) waits for the flush in the lane's own row of s_out, in
+    // the shift of the moments to the Gaussian's own centre (moment_shift) waits for the flush in the lane's own row of s_out, in
     // the two slots a 21-value record leaves unused (three channels: no registers across the entry loop); in registers otherwise
     constexpr bool kShiftInLds = NC == 3;
     float pox = 0.f, poy = 0.f;
@@ -155,37 +107,19 @@ void render_backward_kernel(FrameDev f, const uint2* __restrict__ ranges, const 
         float ox = 0.f, oy = 0.f;
         wait_vector_memory();   // (loads and stores of the previous round: see blend_common.h)
         if ((uint32_t)lane < n) {
-            (void)stage_entry<QX, QY, NC>(nr, nx, ny, Xc, Yc, 0, s_e, lane);
+            (void)stage_entry<QX, QY, NC>(pf.nr, pf.nx, pf.ny, Xc, Yc, 0, s_e, lane);
             // (entry, quadrant) pairs that reached a pixel in the forward: exact, no culling test needed here
-            m = (decode_hits<QX, QY * BANDS>((uint16_t)nhraw) >> (band * QX * QY)) & ((1u << (QX * QY)) - 1u);
-            slot = emission_index(nr, nfirst + nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
+            m = (decode_hits<QX, QY * BANDS>((uint16_t)pf.nhraw) >> (band * QX * QY)) & ((1u << (QX * QY)) - 1u);
+            slot = emission_index(pf.nr, pf.nfirst + pf.nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
             uint32_t need = 0;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) need |= (rbase + lane < quad_last[q]) ? (1u << q) : 0u;
             m &= need;
-            // Sx, Sy from tile-local coordinates to coordinates relative to the Gaussian's OWN centre (cx, cy): sum (xl - mx) dp = sum xl dp -
-            // mx S0 with mx = cx - Xc.  K8 sums these over the Gaussian's tiles and works with Tu - cx Tw, Tv - cy Tw: the same dL/dT as
-            // with moments about the image origin, without the cancellation of pixel coordinates ~1000 against extents of a few pixels
-            // (clamped into the image: the moments of a splat whose centre projects far off-screen are taken about the nearest image point)
-            const float mx = nr[2].y - Xc, my = nr[2].z - Yc;   // (the staged centre: same expression, same bits as stage_entry's)
-            ox = -fminf(fmaxf(mx, -Xc), (float)(f.W - 1) - Xc); oy = -fminf(fmaxf(my, -Yc), (float)(f.H - 1) - Yc);
+            moment_shift(pf.nr, Xc, Yc, f, ox, oy);
         }
-        // (the prefetch comes BEFORE the stores of the flush: the wait for `gid_ahead` -- the last load of the previous round -- then has
-        // the same number of younger memory operations behind it on every path, none, instead of "seven stores or none")
-        if (rd > 0) {  // next round is always full
-            const uint32_t gid = gid_ahead;
-            load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-            if (NC == 6) nx = load_extra(extra, gid, 3);
-            if (NC == 9) { nx = load_extra(extra, gid, 0); ny = load_extra(extra, gid, 3); }
-            nhraw = hit_mask[range.x + rbase - kWave + lane];
-            if (rd > 1) gid_ahead = point_list[range.x + rbase - 2 * kWave + lane];
-        }
+        pf.advance(f, recs, extra, hit_mask, point_list, range.x, rd, rbase, lane);   // (in front of the stores of the flush)
         if (pend) flush_record<kGQ, kShiftInLds>(&s_out[lane][0], inst_grads, written, pslot, pox, poy, BANDS > 1 && band > 0);   // one 96-B store per lane whose entry of the previous round got a contribution
-        {
-            float4* z = reinterpret_cast<float4*>(&s_out[lane][0]);
-#pragma unroll
-            for (int k = 0; k < kGQ; ++k) z[k] = (kShiftInLds && k == 5) ? make_float4(0.f, 0.f, ox, oy) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        reset_record_row<kGQ, kShiftInLds>(&s_out[lane][0], ox, oy);
         unsigned long long bits = ballot64(m != 0);
         // entries of this round that get a record: those with an (entry, quadrant) pair that reached a pixel in the forward.  (Such a
         // pair has a valid lane here too -- same decisions, bit for bit -- unless every pixel it reached stopped at the transmittance
@@ -200,10 +134,9 @@ void render_backward_kernel(FrameDev f, const uint2* __restrict__ ranges, const 
             // quadrant test, as the 6- / 9-channel instantiations at their register limit still do) every test waited for its own LDS round trip.
             // 162 -> 168 registers: exactly the three-waves budget.  K7 1.605 -> 1.560 ms at C3, bit-identical (same-box A/B).
             constexpr bool kEntryColoursUpFront = NC == 3 || QX * QY >= 4;   // (6 / 9 channels on four or more pixels per lane run two waves per SIMD: registers to spare)
-            float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f), e5 = e4;
+            float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f), e5 = e4, e6 = e4;
             if (kEntryColoursUpFront) { e4 = s_e[4][j]; e5 = s_e[5][j]; }
-            float4 e6_up = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (NC == 9 && kEntryColoursUpFront) e6_up = s_e[6][j];
+            if (NC == 9 && kEntryColoursUpFront) e6 = s_e[6][j];
             const uint32_t cidx = rbase + (uint32_t)j;  // 0-based contributor index
             constexpr int NV = (NC == 3 || !kXG) ? 21 : 24;   // slots 21..23 carry colour channels 3..5 only
             float v[24];
@@ -214,55 +147,11 @@ void render_backward_kernel(FrameDev f, const uint2* __restrict__ ranges, const 
                 if (!(mj & (1u << q))) continue;  // wave-uniform
                 Hit h;
                 const float xq = xl0 + (float)((q % QX) * 8), yq = yl0 + (float)((q / QX) * 8);
-                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < lastc[q]);
+                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < px[q].lastc);
                 if (valid) {
-                    if (!kEntryColoursUpFront) { e4 = s_e[4][j]; e5 = s_e[5][j]; }
-                    const float Twx = e2.y, Twy = e2.z;
-                    const float one_m_inv = fast_rcp(1.f - h.alpha);
-                    T[q] *= one_m_inv;                 // transmittance in front of this entry
-                    const float w = h.alpha * T[q];
-                    // psi = rgb.g + depth g_depth + n.gn + (a2 + m (m a0 - 2 a1)), m = the depth metric; dL/dz = w (2 (m a0 - a1) dm/dz + g_depth),
-                    // dm/dz = kFN kNear / depth^2.  t1 = m a0 - a1 serves both: 8 instructions where the literal transcription took 11.  (The
-                    // three distortion terms cancel to the variance of m along the ray: they are combined in ONE fma before anything else is
-                    // added -- seeding the colour chain with a2 saves another instruction and costs a digit under a distortion-weighted loss.)
-                    float phi = fmaf(e4.w, gr[q], fmaf(e5.x, gg[q], fmaf(e5.y, gb[q], fmaf(h.depth, g_depth[q],
-                                fmaf(e4.x, gn0[q], fmaf(e4.y, gn1[q], e4.z * gn2[q]))))));
-                    if (NC >= 6) phi = fmaf(e5.z, gc3[q], fmaf(e5.w, gc4[q], fmaf(e3.w, gc5[q], phi)));
-                    if (NC == 9) { const float4 e6 = kEntryColoursUpFront ? e6_up : s_e[6][j]; phi = fmaf(e6.x, gc6[q], fmaf(e6.y, gc7[q], fmaf(e6.z, gc8[q], phi))); }
-                    const float inv_depth = fast_rcp(h.depth);
-                    const float m_d = fmaf(inv_depth, -kFN * kNear, kFN);
-                    const float t1 = fmaf(m_d, a0[q], -a1[q]);
-#if SR_DETACH_WEIGHT
-                    const float psi = phi;   // upstream DETACH_WEIGHT: the distortion does not differentiate through the blend weights
-#else
-                    const float psi = phi + fmaf(m_d, t1 - a1[q], a2[q]);
-#endif
-                    const float dL_dalpha = T[q] * psi - one_m_inv * Z[q];
-                    Z[q] = fmaf(w, psi, Z[q]);
-                    const float med_add = (cidx == medc[q] - (SR_MEDIAN_CONTRIBUTOR_MINUS_ONE ? 1u : 0u)) ? g_median[q] : 0.f;
-                    const float dL_dz = fmaf(w, fmaf(t1 * (inv_depth * inv_depth), 2.f * kFN * kNear, g_depth[q]), med_add);
-                    const float dL_dG = e3.z * dL_dalpha;
-                    if (NC != 6 || kXG) { v[18] += w * gr[q]; v[19] += w * gg[q]; v[20] += w * gb[q]; }   // (6 channels: all of them precomputed)
-                    if (NC >= 6 && kXG) { v[21] += w * gc3[q]; v[22] += w * gc4[q]; v[23] += w * gc5[q]; }
-                    if (NC == 9 && kXG) { w6 += w * gc6[q]; w7 += w * gc7[q]; w8 += w * gc8[q]; }
-                    v[15] += w * gn0[q]; v[16] += w * gn1[q]; v[17] += w * gn2[q];
-                    v[14] += h.G * dL_dalpha;
-                    v[11] += dL_dz;   // (both paths)
-                    if (h.use3d) {
-                        const float gG = -dL_dG * h.G;
-                        const float dpx = (gG * h.sx + dL_dz * Twx) * h.pz_inv, dpy = (gG * h.sy + dL_dz * Twy) * h.pz_inv;
-                        const float dpz = -(dpx * h.sx + dpy * h.sy);
-                        // moments of dL/dp in tile-local pixel coordinates (shifted to global ones when the record is written);
-                        // the cross products happen once per Gaussian in K8
-                        v[0] += dpx; v[1] += dpy; v[2] += dpz;
-                        v[3] = fmaf(xq, dpx, v[3]); v[4] = fmaf(xq, dpy, v[4]); v[5] = fmaf(xq, dpz, v[5]);
-                        v[6] = fmaf(yq, dpx, v[6]); v[7] = fmaf(yq, dpy, v[7]); v[8] = fmaf(yq, dpz, v[8]);
-                        v[9] = fmaf(dL_dz, h.sx, v[9]); v[10] = fmaf(dL_dz, h.sy, v[10]);
-                    } else {
-                        const float gG = -dL_dG * h.G * kFilterInvSquare;
-                        v[12] = fmaf(gG, h.dx, v[12]);
-                        v[13] = fmaf(gG, h.dy, v[13]);
-                    }
+                    if (!kEntryColoursUpFront) { e4 = s_e[4][j]; e5 = s_e[5][j]; if (NC == 9) e6 = s_e[6][j]; }
+                    const float w = blend_backward_pair<NC, kXG, true, (NQ > 1)>(e2, e3, e4, e5, e6, h, xq, yq, cidx, px[q], v);
+                    if (NC == 9 && kXG) { w6 += w * px[q].gc[3]; w7 += w * px[q].gc[4]; w8 += w * px[q].gc[5]; }
                 }
             }
             {
@@ -313,22 +202,11 @@ void render_backward_coop_kernel(FrameDev f, const uint2* __restrict__ ranges, c
     const float Xc = (float)(tx0 + 8), Yc = (float)(ty0 + 8);
     const int lx = lane & 7, ly = lane >> 3, qx = w & 1, qy = w >> 1;   // wave w = quadrant (w % 2, w / 2) = bit w of the hit masks
     const uint2 range = ranges[tile];
-    const size_t HW = (size_t)f.H * f.W;
-    const int px = tx0 + qx * 8 + lx, py = ty0 + qy * 8 + ly;
-    const bool inside = px < f.W && py < f.H;
-    const size_t pix = inside ? (size_t)py * f.W + px : 0;
     const float xq = (float)(qx * 8 + lx - 8), yq = (float)(qy * 8 + ly - 8);
-    const float T_final = inside ? final_T[pix] : 0.f;
-    const float fin_D = inside ? final_T[HW + pix] : 0.f, fin_D2 = inside ? final_T[2 * HW + pix] : 0.f;
-    const uint32_t lastc = inside ? n_contrib[pix] : 0u, medc = inside ? n_contrib[HW + pix] : 0u;
-    const float gr = inside ? dL_dcolor[pix] : 0.f, gg = inside ? dL_dcolor[HW + pix] : 0.f, gb = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-    const float g_depth = inside ? dL_dallmap[pix] : 0.f, g_accum = inside ? dL_dallmap[HW + pix] : 0.f;
-    const float gn0 = inside ? dL_dallmap[2 * HW + pix] : 0.f, gn1 = inside ? dL_dallmap[3 * HW + pix] : 0.f, gn2 = inside ? dL_dallmap[4 * HW + pix] : 0.f;
-    const float g_median = inside ? dL_dallmap[5 * HW + pix] : 0.f, g_reg = inside ? dL_dallmap[6 * HW + pix] : 0.f;
-    const float a0 = (1.f - T_final) * g_reg, a1 = fin_D * g_reg, a2 = fin_D2 * g_reg;
-    float T = T_final, Z = -T_final * (g_accum - (f.bg[0] * gr + f.bg[1] * gg + f.bg[2] * gb));
+    BackwardPixel px;
+    load_backward_pixel<NC>(f, tx0 + qx * 8 + lx, ty0 + qy * 8 + ly, final_T, n_contrib, dL_dcolor, dL_dallmap, px);
     {
-        const uint32_t ql = wave_max_u32(lastc);   // deepest entry any pixel of this wave's quadrant needs
+        const uint32_t ql = wave_max_u32(px.lastc);   // deepest entry any pixel of this wave's quadrant needs
         if (lane == 0) s_ql[w] = ql;
     }
     __syncthreads();
@@ -338,17 +216,9 @@ void render_backward_coop_kernel(FrameDev f, const uint2* __restrict__ ranges, c
     const bool stager = lane < kStage;
     const int se = w * kStage + lane;          // the entry of the round this lane stages (lanes < 16 of each wave)
     const bool holds_total = reduce24_holds_total(lane) && reduce24_index(lane) < 21;
-    // the walk's memory pipeline as in the one-wave kernel: list entries two rounds ahead, records one, raw
-    float4 nr[kRecQuads];
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t nfirst = 0, nfbase = 0, nhraw = 0, gid_ahead = 0;
-    if (stager && rounds > 0 && (uint32_t)((rounds - 1) * kWave + se) < total) {
-        const uint32_t pos = range.x + (rounds - 1) * kWave + se;
-        const uint32_t gid = point_list[pos];
-        load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-        nhraw = hit_mask[pos];
-    }
-    if (stager && rounds > 1) gid_ahead = point_list[range.x + (rounds - 2) * kWave + se];
+    WalkPrefetch<NC> pf;
+    pf.begin(f, recs, nullptr, hit_mask, point_list, range.x, rounds, total, se, stager);
     for (int rd = rounds - 1; rd >= 0; --rd) {
         const uint32_t rbase = (uint32_t)rd * kWave;
         const uint32_t n = min((uint32_t)kWave, total - rbase);
@@ -356,21 +226,15 @@ void render_backward_coop_kernel(FrameDev f, const uint2* __restrict__ ranges, c
         if (stager) {
             uint32_t m = 0;
             if ((uint32_t)se < n) {
-                (void)stage_entry<2, 2, NC>(nr, zero4, zero4, Xc, Yc, 0, s_e, se);
+                (void)stage_entry<2, 2, NC>(pf.nr, zero4, zero4, Xc, Yc, 0, s_e, se);
                 const uint32_t at = rbase + (uint32_t)se;
                 const uint32_t need = (at < ql0 ? 1u : 0u) | (at < ql1 ? 2u : 0u) | (at < ql2 ? 4u : 0u) | (at < ql3 ? 8u : 0u);
-                m = decode_hits<2, 2>((uint16_t)nhraw) & need;
-                s_slot[se] = emission_index(nr, nfirst + nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
-                const float mx = nr[2].y - Xc, my = nr[2].z - Yc;
-                s_ox[se] = -fminf(fmaxf(mx, -Xc), (float)(f.W - 1) - Xc); s_oy[se] = -fminf(fmaxf(my, -Yc), (float)(f.H - 1) - Yc);
+                m = decode_hits<2, 2>((uint16_t)pf.nhraw) & need;
+                s_slot[se] = emission_index(pf.nr, pf.nfirst + pf.nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
+                moment_shift(pf.nr, Xc, Yc, f, s_ox[se], s_oy[se]);
             }
             s_m[se] = m;
-            if (rd > 0) {   // (the next round is always full)
-                const uint32_t gid = gid_ahead;
-                load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-                nhraw = hit_mask[range.x + rbase - kWave + se];
-                if (rd > 1) gid_ahead = point_list[range.x + rbase - 2 * kWave + se];
-            }
+            pf.advance(f, recs, nullptr, hit_mask, point_list, range.x, rd, rbase, se);
         }
         __syncthreads();
         const uint32_t mine = s_m[lane];
@@ -384,43 +248,8 @@ void render_backward_coop_kernel(FrameDev f, const uint2* __restrict__ ranges, c
             float v[24];
             lds_zeros_load<21>(s_zero, j, v);
             Hit h;
-            const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < lastc);
-            if (valid) {   // (the per-pair arithmetic of render_backward_kernel, one quadrant)
-                const float Twx = e2.y, Twy = e2.z;
-                const float one_m_inv = fast_rcp(1.f - h.alpha);
-                T *= one_m_inv;
-                const float wgt = h.alpha * T;
-                const float phi = fmaf(e4.w, gr, fmaf(e5.x, gg, fmaf(e5.y, gb, fmaf(h.depth, g_depth, fmaf(e4.x, gn0, fmaf(e4.y, gn1, e4.z * gn2))))));
-                const float inv_depth = fast_rcp(h.depth);
-                const float m_d = fmaf(inv_depth, -kFN * kNear, kFN);
-                const float t1 = fmaf(m_d, a0, -a1);
-#if SR_DETACH_WEIGHT
-                const float psi = phi;
-#else
-                const float psi = phi + fmaf(m_d, t1 - a1, a2);
-#endif
-                const float dL_dalpha = T * psi - one_m_inv * Z;
-                Z = fmaf(wgt, psi, Z);
-                const float med_add = (cidx == medc - (SR_MEDIAN_CONTRIBUTOR_MINUS_ONE ? 1u : 0u)) ? g_median : 0.f;
-                const float dL_dz = fmaf(wgt, fmaf(t1 * (inv_depth * inv_depth), 2.f * kFN * kNear, g_depth), med_add);
-                const float dL_dG = e3.z * dL_dalpha;
-                v[18] = wgt * gr; v[19] = wgt * gg; v[20] = wgt * gb;
-                v[15] = wgt * gn0; v[16] = wgt * gn1; v[17] = wgt * gn2;
-                v[14] = h.G * dL_dalpha;
-                v[11] = dL_dz;
-                if (h.use3d) {
-                    const float gG = -dL_dG * h.G;
-                    const float dpx = (gG * h.sx + dL_dz * Twx) * h.pz_inv, dpy = (gG * h.sy + dL_dz * Twy) * h.pz_inv;
-                    const float dpz = -(dpx * h.sx + dpy * h.sy);
-                    v[0] = dpx; v[1] = dpy; v[2] = dpz;
-                    v[3] = xq * dpx; v[4] = xq * dpy; v[5] = xq * dpz;
-                    v[6] = yq * dpx; v[7] = yq * dpy; v[8] = yq * dpz;
-                    v[9] = dL_dz * h.sx; v[10] = dL_dz * h.sy;
-                } else {
-                    const float gG = -dL_dG * h.G * kFilterInvSquare;
-                    v[12] = gG * h.dx; v[13] = gG * h.dy;
-                }
-            }
+            const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < px.lastc);
+            if (valid) (void)blend_backward_pair<NC, true, false, false>(e2, e3, e4, e5, zero4, h, xq, yq, cidx, px, v);   // (one pixel per lane: the terms are assigned)
             const float tot = wave_reduce24<21>(v, lane);
             if (holds_total) s_part[w][j][reduce24_index(lane)] = tot;
         }
@@ -497,45 +326,20 @@ void render_backward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, c
     const int row = lane >> 4;
     const int lx = (row & 1) * 4 + (lane & 3), ly = (row >> 1) * 4 + ((lane >> 2) & 3);
     const uint2 range = ranges[tile];
-    const size_t HW = (size_t)f.H * f.W;
-    const float bg0 = f.bg[0], bg1 = f.bg[1], bg2 = f.bg[2];
     const float xl0 = (float)(lx - 8), yl0 = (float)(ly - 8);
-    float gr[NQ], gg[NQ], gb[NQ], gn0[NQ], gn1[NQ], gn2[NQ], g_depth[NQ], g_median[NQ], a0[NQ], a1[NQ], a2[NQ];
-    uint32_t lastc[NQ], medc[NQ], quad_last[NQ];
-    float T[NQ], Z[NQ];
+    BackwardPixel px[NQ];
+    uint32_t quad_last[NQ];
     uint32_t total = 0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        const int px = tx0 + (q % QX) * 8 + lx, py = ty0 + (q / QX) * 8 + ly;
-        const bool inside = px < f.W && py < f.H;
-        const size_t pix = inside ? (size_t)py * f.W + px : 0;
-        const float T_final = inside ? final_T[pix] : 0.f;
-        const float fin_D = inside ? final_T[HW + pix] : 0.f, fin_D2 = inside ? final_T[2 * HW + pix] : 0.f;
-        lastc[q] = inside ? n_contrib[pix] : 0u;
-        medc[q] = inside ? n_contrib[HW + pix] : 0u;
-        gr[q] = inside ? dL_dcolor[pix] : 0.f; gg[q] = inside ? dL_dcolor[HW + pix] : 0.f; gb[q] = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-        g_depth[q] = inside ? dL_dallmap[pix] : 0.f;
-        const float g_accum = inside ? dL_dallmap[HW + pix] : 0.f;
-        gn0[q] = inside ? dL_dallmap[2 * HW + pix] : 0.f; gn1[q] = inside ? dL_dallmap[3 * HW + pix] : 0.f; gn2[q] = inside ? dL_dallmap[4 * HW + pix] : 0.f;
-        g_median[q] = inside ? dL_dallmap[5 * HW + pix] : 0.f;
-        const float g_reg = inside ? dL_dallmap[6 * HW + pix] : 0.f;
-        const float bg_dot = bg0 * gr[q] + bg1 * gg[q] + bg2 * gb[q];
-        a0[q] = (1.f - T_final) * g_reg; a1[q] = fin_D * g_reg; a2[q] = fin_D2 * g_reg;
-        T[q] = T_final; Z[q] = -T_final * (g_accum - bg_dot);
-        quad_last[q] = wave_max_u32(lastc[q]);
+        load_backward_pixel<NC>(f, tx0 + (q % QX) * 8 + lx, ty0 + (q / QX) * 8 + ly, final_T, n_contrib, dL_dcolor, dL_dallmap, px[q]);
+        quad_last[q] = wave_max_u32(px[q].lastc);
         total = max(total, quad_last[q]);
     }
     const int rounds = (int)((total + kWave - 1) / kWave);
-    float4 nr[kRecQuads];
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t nfirst = 0, nfbase = 0, nhraw = 0, gid_ahead = 0;
-    if (rounds > 0 && (uint32_t)((rounds - 1) * kWave + lane) < total) {
-        const uint32_t pos = range.x + (rounds - 1) * kWave + lane;
-        const uint32_t gid = point_list[pos];
-        load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-        nhraw = hit_mask[pos];
-    }
-    if (rounds > 1) gid_ahead = point_list[range.x + (rounds - 2) * kWave + lane];
+    WalkPrefetch<NC> pf;
+    pf.begin(f, recs, nullptr, hit_mask, point_list, range.x, rounds, total, lane);
     // after the in-row reduction the lanes of quad (bit 2, bit 3 of the lane) hold the row's totals of values k + 6 bit2 + 12 bit3, k = 0..5
     const int vbase = 6 * ((lane >> 2) & 1) + 12 * ((lane >> 3) & 1);
     bool pend = false;
@@ -547,27 +351,17 @@ void render_backward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, c
         float ox = 0.f, oy = 0.f;
         wait_vector_memory();
         if ((uint32_t)lane < n) {
-            (void)stage_entry<QX, QY, NC>(nr, zero4, zero4, Xc, Yc, 0, s_e, lane);
-            slot = emission_index(nr, nfirst + nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
+            (void)stage_entry<QX, QY, NC>(pf.nr, zero4, zero4, Xc, Yc, 0, s_e, lane);
+            slot = emission_index(pf.nr, pf.nfirst + pf.nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
             uint32_t need = 0;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) need |= (rbase + lane < quad_last[q]) ? (15u << (4 * q)) : 0u;
-            cm = nhraw & need;
-            const float mx = nr[2].y - Xc, my = nr[2].z - Yc;
-            ox = -fminf(fmaxf(mx, -Xc), (float)(f.W - 1) - Xc); oy = -fminf(fmaxf(my, -Yc), (float)(f.H - 1) - Yc);
+            cm = pf.nhraw & need;
+            moment_shift(pf.nr, Xc, Yc, f, ox, oy);
         }
-        if (rd > 0) {
-            const uint32_t gid = gid_ahead;
-            load_record(recs, gid, nr); nfirst = f.first[gid]; nfbase = f.first_base[gid / kScanTile];
-            nhraw = hit_mask[range.x + rbase - kWave + lane];
-            if (rd > 1) gid_ahead = point_list[range.x + rbase - 2 * kWave + lane];
-        }
+        pf.advance(f, recs, nullptr, hit_mask, point_list, range.x, rd, rbase, lane);
         if (pend) flush_record<kGQ, true>(&s_out[lane][0], inst_grads, written, pslot, 0.f, 0.f, false);
-        {
-            float4* z = reinterpret_cast<float4*>(&s_out[lane][0]);
-#pragma unroll
-            for (int k = 0; k < kGQ; ++k) z[k] = (k == 5) ? make_float4(0.f, 0.f, ox, oy) : zero4;
-        }
+        reset_record_row<kGQ, true>(&s_out[lane][0], ox, oy);
         const unsigned long long wrote = ballot64(cm != 0);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -589,46 +383,8 @@ void render_backward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, c
                     if (k < 21) asm volatile("" : "+v"(v[k]));
                 }
                 Hit h;
-                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < lastc[q]) & act;
-                if (valid) {   // (the per-pair arithmetic of render_backward_kernel)
-                    const float4 e4 = s_e[4][j], e5 = s_e[5][j];
-                    const float Twx = e2.y, Twy = e2.z;
-                    const float one_m_inv = fast_rcp(1.f - h.alpha);
-                    T[q] *= one_m_inv;
-                    const float w = h.alpha * T[q];
-                    const float phi = fmaf(e4.w, gr[q], fmaf(e5.x, gg[q], fmaf(e5.y, gb[q], fmaf(h.depth, g_depth[q],
-                                      fmaf(e4.x, gn0[q], fmaf(e4.y, gn1[q], e4.z * gn2[q]))))));
-                    const float inv_depth = fast_rcp(h.depth);
-                    const float m_d = fmaf(inv_depth, -kFN * kNear, kFN);
-                    const float t1 = fmaf(m_d, a0[q], -a1[q]);
-#if SR_DETACH_WEIGHT
-                    const float psi = phi;
-#else
-                    const float psi = phi + fmaf(m_d, t1 - a1[q], a2[q]);
-#endif
-                    const float dL_dalpha = T[q] * psi - one_m_inv * Z[q];
-                    Z[q] = fmaf(w, psi, Z[q]);
-                    const float med_add = (cidx == medc[q] - (SR_MEDIAN_CONTRIBUTOR_MINUS_ONE ? 1u : 0u)) ? g_median[q] : 0.f;
-                    const float dL_dz = fmaf(w, fmaf(t1 * (inv_depth * inv_depth), 2.f * kFN * kNear, g_depth[q]), med_add);
-                    const float dL_dG = e3.z * dL_dalpha;
-                    v[18] += w * gr[q]; v[19] += w * gg[q]; v[20] += w * gb[q];
-                    v[15] += w * gn0[q]; v[16] += w * gn1[q]; v[17] += w * gn2[q];
-                    v[14] += h.G * dL_dalpha;
-                    v[11] += dL_dz;
-                    if (h.use3d) {
-                        const float gG = -dL_dG * h.G;
-                        const float dpx = (gG * h.sx + dL_dz * Twx) * h.pz_inv, dpy = (gG * h.sy + dL_dz * Twy) * h.pz_inv;
-                        const float dpz = -(dpx * h.sx + dpy * h.sy);
-                        v[0] += dpx; v[1] += dpy; v[2] += dpz;
-                        v[3] = fmaf(xq, dpx, v[3]); v[4] = fmaf(xq, dpy, v[4]); v[5] = fmaf(xq, dpz, v[5]);
-                        v[6] = fmaf(yq, dpx, v[6]); v[7] = fmaf(yq, dpy, v[7]); v[8] = fmaf(yq, dpz, v[8]);
-                        v[9] = fmaf(dL_dz, h.sx, v[9]); v[10] = fmaf(dL_dz, h.sy, v[10]);
-                    } else {
-                        const float gG = -dL_dG * h.G * kFilterInvSquare;
-                        v[12] = fmaf(gG, h.dx, v[12]);
-                        v[13] = fmaf(gG, h.dy, v[13]);
-                    }
-                }
+                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < px[q].lastc) & act;
+                if (valid) (void)blend_backward_pair<NC, true, true, true>(e2, e3, s_e[4][j], s_e[5][j], zero4, h, xq, yq, cidx, px[q], v);
                 dpp_fold_rows<21>(v);   // v[0..5]: value k + vbase, summed over the lanes {l, l^4, l^8, l^12} of the row
                 float* orow = &s_out[j][vbase];
 #pragma unroll
@@ -646,14 +402,6 @@ void render_backward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, c
     }
     if (pend) flush_record<kGQ, true>(&s_out[lane][0], inst_grads, written, pslot, 0.f, 0.f, false);
 }
-
-#define SR_FOR_TILE_SHAPE(F)                                                    \
-    if (f.tile_w == 16 && f.tile_h == 16) { F(2, 2); }                          \
-    else if (f.tile_w == 8 && f.tile_h == 8) { F(1, 1); }                       \
-    else if (f.tile_w == 16 && f.tile_h == 8) { F(2, 1); }                      \
-    else if (f.tile_w == 32 && f.tile_h == 8) { F(4, 1); }                      \
-    else if (f.tile_w == 32 && f.tile_h == 16) { F(4, 2); }                     \
-    else return hipErrorInvalidValue;
 
 // coop_mode: 0 = by tile count (the cooperative kernel below kCoopBelowTiles tiles of 16x16 with three colour channels), 1 = never, 2 = always (A/B, tests),
 // 3 = the row-mapped kernel: the forward must have written CELL-granular hit masks (launch_render_forward flags bit 6)

@@ -108,12 +108,6 @@ __global__ __launch_bounds__(kWave) void class_partition_kernel(int n_classes, c
     }
 }
 
-// the three record quads the class pass stages (transform rows, centre, opacity); the others stay zero
-__device__ __forceinline__ void load_record_geometry(const float4* __restrict__ recs, uint32_t gid, float4 (&q)[kRecQuads]) {
-    const float4* r = recs + (size_t)gid * kRecQuads;
-    q[0] = r[0]; q[1] = r[1]; q[2] = r[2];
-}
-
 // One wave per (tile band, class): QX x 1 quadrants per wave; SPLIT = 2: the reference's 16x16 tile as two 16x8 band waves (two pixels per
 // lane), SPLIT = 1: the 8x8 / 16x8 / 32x8 tiles of BASELINE config 5's sweep.  A single transmittance / distortion chain.
 // QY = 2 (SPLIT = 1; round 6): the whole 16x16 tile in ONE wave, four pixels per lane -- a class chain keeps five registers per pixel (the colour
@@ -332,17 +326,8 @@ void class_backward_kernel(FrameDev f, int n_classes, const uint2* __restrict__ 
     }
     const int rounds = (int)((total + kWave - 1) / kWave);
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 nr[kRecQuads];
-#pragma unroll
-    for (int i = 0; i < kRecQuads; ++i) nr[i] = zero4;
-    // Memory pipeline of the walk as in render_bwd.hip's K7 (round 6): the list entry two rounds ahead, the record one round ahead and RAW
-    // (first[] / first_base[] as two registers, the hit mask undecoded), the records of a round stored behind the staging of the next one.
-    uint32_t nfirst = 0, nfbase = 0, nhraw = 0, gid_ahead = 0;
-#define SR_CLASS_FETCH(GID, POS) { const uint32_t gid_ = (GID); load_record_geometry(recs, gid_, nr);                                   \
-        nr[4].w = reinterpret_cast<const float*>(recs + (size_t)gid_ * kRecQuads + 4)[3];   /* the radius (emission_index) */ \
-        nfirst = f.first[gid_]; nfbase = f.first_base[gid_ / kScanTile]; nhraw = hit_mask[(POS)]; }
-    if ((uint32_t)((rounds - 1) * kWave + lane) < total) SR_CLASS_FETCH(cls_list[first_pos + (rounds - 1) * kWave + lane], first_pos + (rounds - 1) * kWave + lane)
-    if (rounds > 1) gid_ahead = cls_list[first_pos + (rounds - 2) * kWave + lane];
+    WalkPrefetch<0> pf;   // (geometry only)
+    pf.begin(f, recs, nullptr, hit_mask, cls_list, first_pos, rounds, total, lane);
     bool pend = false;
     uint32_t pslot = 0;
     float pox = 0.f, poy = 0.f;
@@ -353,26 +338,17 @@ void class_backward_kernel(FrameDev f, int n_classes, const uint2* __restrict__ 
         float ox = 0.f, oy = 0.f;
         wait_vector_memory();
         if ((uint32_t)lane < n) {
-            (void)stage_entry<QX, QY, 0>(nr, zero4, zero4, Xc, Yc, 0, s_e, lane);
-            slot = emission_index(nr, nfirst + nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
+            (void)stage_entry<QX, QY, 0>(pf.nr, zero4, zero4, Xc, Yc, 0, s_e, lane);
+            slot = emission_index(pf.nr, pf.nfirst + pf.nfbase, tile % f.tiles_x, tile / f.tiles_x, f);
             uint32_t need = 0;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) need |= (rbase + lane < quad_last[q]) ? (1u << q) : 0u;
-            m = decode_hits<QX, QY>((uint16_t)nhraw) & need;
-            // (clamped into the image: the moments of a splat whose centre projects far off-screen are taken about the nearest image point)
-            const float mx = nr[2].y - Xc, my = nr[2].z - Yc;   // the staged centre relative to the tile centre: same bits as stage_entry's
-            ox = -fminf(fmaxf(mx, -Xc), (float)(f.W - 1) - Xc); oy = -fminf(fmaxf(my, -Yc), (float)(f.H - 1) - Yc);
+            m = decode_hits<QX, QY>((uint16_t)pf.nhraw) & need;
+            moment_shift(pf.nr, Xc, Yc, f, ox, oy);
         }
-        if (rd > 0) {
-            SR_CLASS_FETCH(gid_ahead, first_pos + rbase - kWave + lane)
-            if (rd > 1) gid_ahead = cls_list[first_pos + rbase - 2 * kWave + lane];
-        }
+        pf.advance(f, recs, nullptr, hit_mask, cls_list, first_pos, rd, rbase, lane);
         if (pend) class_flush<kShared>(&s_out[lane][0], inst_grads, written, pslot, pox, poy, rec_quads);
-        {
-            float4* z = reinterpret_cast<float4*>(&s_out[lane][0]);
-#pragma unroll
-            for (int k = 0; k < kGQ; ++k) z[k] = zero4;
-        }
+        reset_record_row<kGQ, false>(&s_out[lane][0], 0.f, 0.f);
         unsigned long long bits = ballot64(m != 0);
         const unsigned long long wrote = bits;   // every entry with a forward hit gets a record (see K7)
         while (bits) {
@@ -394,7 +370,6 @@ void class_backward_kernel(FrameDev f, int n_classes, const uint2* __restrict__ 
                 const float xq = xl0 + (float)((q % QX) * 8), yq = yl0 + (float)((q / QX) * 8);
                 const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (cidx < lastc[q]);
                 if (valid) {
-                    const float Twx = e2.y, Twy = e2.z;
                     const float one_m_inv = fast_rcp(1.f - h.alpha);
                     T[q] *= one_m_inv;
                     const float w = h.alpha * T[q];
@@ -411,20 +386,7 @@ void class_backward_kernel(FrameDev f, int n_classes, const uint2* __restrict__ 
                     const float dL_dz = 2.f * w * (m_d * a0[q] - a1[q]) * dmd_dd;
                     const float dL_dG = e3.z * dL_dalpha;
                     v[14] += h.G * dL_dalpha;
-                    if (h.use3d) {
-                        const float gG = -dL_dG * h.G;
-                        const float dpx = (gG * h.sx + dL_dz * Twx) * h.pz_inv, dpy = (gG * h.sy + dL_dz * Twy) * h.pz_inv;
-                        const float dpz = -(dpx * h.sx + dpy * h.sy);
-                        v[0] += dpx; v[1] += dpy; v[2] += dpz;
-                        v[3] = fmaf(xq, dpx, v[3]); v[4] = fmaf(xq, dpy, v[4]); v[5] = fmaf(xq, dpz, v[5]);
-                        v[6] = fmaf(yq, dpx, v[6]); v[7] = fmaf(yq, dpy, v[7]); v[8] = fmaf(yq, dpz, v[8]);
-                        v[9] = fmaf(dL_dz, h.sx, v[9]); v[10] = fmaf(dL_dz, h.sy, v[10]); v[11] += dL_dz;
-                    } else {
-                        const float gG = -dL_dG * h.G * kFilterInvSquare;
-                        v[12] = fmaf(gG, h.dx, v[12]);
-                        v[13] = fmaf(gG, h.dy, v[13]);
-                        v[11] += dL_dz;
-                    }
+                    geometry_sums<true, NQ == 1>(h, xq, yq, e2.y, e2.z, dL_dG, dL_dz, v);
                 }
             }
             {
@@ -435,7 +397,6 @@ void class_backward_kernel(FrameDev f, int n_classes, const uint2* __restrict__ 
         pend = ((wrote >> lane) & 1ull) != 0ull; pslot = slot; pox = ox; poy = oy;
     }
     if (pend) class_flush<kShared>(&s_out[lane][0], inst_grads, written, pslot, pox, poy, rec_quads);
-#undef SR_CLASS_FETCH
 }
 
 hipError_t launch_class_partition(int P, int n_tiles, int n_classes, const float* class_cols, const int32_t* class_i32, const uint2* ranges,
