@@ -358,6 +358,24 @@ int sr_postprocess_backward(int32_t image_width, int32_t image_height, float fov
                             const float* viewmatrix, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
                             const float* g_surf_normal, const float* g_surf_point, float* scratch6, float* g_allmap, void* stream);
 
+/* Fused photometric loss of a training iteration == train.py:113-119 + utils/loss_utils.py:18-64 of the reference:
+ *     x = image (+ sky * (1 - alpha));  l1 = mean|x - gt|;  ssim = mean of the SSIM map of (x, gt);
+ *     loss = (1 - lambda_dssim) * l1 + lambda_dssim * (1 - ssim)
+ * SSIM with the reference's 11-tap Gaussian window (sigma 1.5), zero padding of 5 pixels (not renormalised at the border),
+ * C1 = 0.01^2, C2 = 0.03^2.  image, gt, sky are [C,H,W], alpha is [1,H,W]; sky and alpha may be NULL together (no composite).
+ * Forward: writes out3 = {loss, l1, ssim} on the device (no read-back, no float atomics: two calls give the same bits) and keeps
+ * three [C,H,W] planes of SSIM derivatives in the workspace (sr_image_loss_workspace_bytes(W, H, C) bytes, caller-owned).
+ * Backward: from the same inputs, the workspace the forward filled and the upstream scalar g_loss (a DEVICE float), writes
+ * g_image[C,H,W] and, with the composite, g_sky[C,H,W] and g_alpha[1,H,W] (alpha is not detached, as in the reference); gt gets
+ * no gradient.  Bad sizes, a missing pointer, only one of sky / alpha or a short workspace are refused before any launch. */
+size_t sr_image_loss_workspace_bytes(int32_t image_width, int32_t image_height, int32_t channels);
+int sr_image_loss_forward(int32_t image_width, int32_t image_height, int32_t channels, float lambda_dssim, const float* image,
+                          const float* gt, const float* sky, const float* alpha, void* workspace, size_t workspace_bytes,
+                          float* out3, void* stream);
+int sr_image_loss_backward(int32_t image_width, int32_t image_height, int32_t channels, float lambda_dssim, const float* image,
+                           const float* gt, const float* sky, const float* alpha, const void* workspace, size_t workspace_bytes,
+                           const float* g_loss, float* g_image, float* g_sky, float* g_alpha, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

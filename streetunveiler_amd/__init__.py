@@ -5,3 +5,13 @@ the host-side mirror of the reference operator surface, a synthetic scene
 generator for the benchmark, and the frame-sharded multi-GPU helper.
 """
 __version__ = "0.1.0"
+
+_IMAGE_LOSS = ("photometric_loss", "photometric_loss_torch", "image_loss_forward", "image_loss_backward", "image_loss_workspace")
+__all__ = list(_IMAGE_LOSS)
+
+
+def __getattr__(name):   # the fused image loss, imported on first use (this package does not import torch by itself)
+    if name in _IMAGE_LOSS:
+        from . import image_loss
+        return getattr(image_loss, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -74,6 +74,13 @@ hipError_t launch_postprocess_forward(const PostCam& cam, const float* allmap, f
 hipError_t launch_postprocess_backward(const PostCam& cam, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
                                        const float* g_surf_normal, const float* g_surf_point, float* scratch6, float* g_allmap,
                                        hipStream_t s);
+// image_loss.hip
+struct LossImages { int W, H, C; float lambda; const float* image; const float* gt; const float* sky; const float* alpha; };
+bool image_loss_supported(int W, int H, int C);
+size_t image_loss_partial_bytes();
+hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s);
+hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
+                                      float* g_alpha, hipStream_t s);
 }  // namespace sr
 
 using namespace sr;
@@ -919,6 +926,43 @@ int sr_postprocess_backward(int32_t W, int32_t H, float fovx, float fovy, float 
     if (!allmap || !scratch6 || !g_allmap) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     SR_HIP(launch_postprocess_backward(cam, allmap, g_rend_normal, g_surf_depth, g_surf_normal, g_surf_point, scratch6, g_allmap,
                                        static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+size_t sr_image_loss_workspace_bytes(int32_t W, int32_t H, int32_t C) {
+    if (W <= 0 || H <= 0 || C <= 0) return 0;
+    return image_loss_partial_bytes() + 3 * sizeof(float) * (size_t)W * (size_t)H * (size_t)C;
+}
+
+static int image_loss_args(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                           const float* alpha, const void* workspace, size_t workspace_bytes, LossImages* a) {
+    if (W <= 0 || H <= 0 || C <= 0) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d with %d channels", W, H, C);
+    if (!image || !gt || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "image / gt / workspace is NULL");
+    if ((sky != nullptr) != (alpha != nullptr)) return fail(SR_ERR_INVALID_ARGUMENT, "sky and alpha go together: give both or neither");
+    if (!image_loss_supported(W, H, C)) return fail(SR_ERR_UNSUPPORTED, "%dx%d with %d channels is beyond the launch limits", W, H, C);
+    if (workspace_bytes < sr_image_loss_workspace_bytes(W, H, C))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, sr_image_loss_workspace_bytes(W, H, C));
+    *a = LossImages{W, H, C, lambda_dssim, image, gt, sky, alpha};
+    return SR_OK;
+}
+
+int sr_image_loss_forward(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                          const float* alpha, void* workspace, size_t workspace_bytes, float* out3, void* stream) {
+    LossImages a;
+    if (int rc = image_loss_args(W, H, C, lambda_dssim, image, gt, sky, alpha, workspace, workspace_bytes, &a)) return rc;
+    if (!out3) return fail(SR_ERR_INVALID_ARGUMENT, "out3 is NULL");
+    SR_HIP(launch_image_loss_forward(a, workspace, out3, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_image_loss_backward(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                           const float* alpha, const void* workspace, size_t workspace_bytes, const float* g_loss, float* g_image,
+                           float* g_sky, float* g_alpha, void* stream) {
+    LossImages a;
+    if (int rc = image_loss_args(W, H, C, lambda_dssim, image, gt, sky, alpha, workspace, workspace_bytes, &a)) return rc;
+    if (!g_loss || !g_image) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_image is NULL");
+    if (sky && (!g_sky || !g_alpha)) return fail(SR_ERR_INVALID_ARGUMENT, "with sky and alpha, g_sky and g_alpha are required");
+    SR_HIP(launch_image_loss_backward(a, workspace, g_loss, g_image, g_sky, g_alpha, static_cast<hipStream_t>(stream)));
     return SR_OK;
 }
 
