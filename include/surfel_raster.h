@@ -376,6 +376,39 @@ int sr_image_loss_backward(int32_t image_width, int32_t image_height, int32_t ch
                            const float* gt, const float* sky, const float* alpha, const void* workspace, size_t workspace_bytes,
                            const float* g_loss, float* g_image, float* g_sky, float* g_alpha, void* stream);
 
+/* One Adam step over up to SR_ADAM_MAX_SEGMENTS float32 tensors in ONE launch == torch.optim.Adam (no weight decay, no amsgrad, not
+ * maximising) as the reference builds it in scene/gaussian_model.py:171-180 and steps it in train.py:197.  Per element, in float32 and
+ * in the order of torch's single-tensor path, with correctly rounded division and square root and no contraction:
+ *     m = m + (g - m) * (1 - beta1);   v = v * beta2 + ((1 - beta2) * g) * g;
+ *     denom = sqrt(v) / bc2_sqrt + eps;   p = p - step_size * (m / denom)
+ * The caller forms step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) per tensor in double (t = that tensor's step count,
+ * this step included) and stores them rounded to float32.  beta1, beta2 and eps arrive as DOUBLES and are rounded once inside, together
+ * with the complements 1 - beta formed in double: float(1 - float(0.999)) is 1.3e-5 away from float(0.001), which a float32 beta would
+ * make the weight of g*g.  Each tensor is n contiguous floats behind param / grad / exp_avg / exp_avg_sq (4-B aligned; a tensor whose
+ * four pointers are 16-B aligned moves 16 B per lane and access); n = 0 is allowed and skipped.  The work is cut into chunks of
+ * SR_ADAM_CHUNK elements.  No atomics: two calls on equal inputs give equal bits; a NaN / Inf gradient element touches its element only.
+ * The hyper-parameters travel by value in the launch: a captured graph would replay THIS step's step_size. */
+#define SR_ADAM_MAX_SEGMENTS 8
+#define SR_ADAM_CHUNK 4096
+typedef struct SrAdamSegment {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;
+    float step_size;
+    float bc2_sqrt;
+} SrAdamSegment;
+int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream);
+
+/* Densification statistics of one rendered view == train.py:168-169 + scene/gaussian_model.py:555-557 of the reference, with
+ * visibility_filter = radii > 0.  For every i < P with radii[i] > 0:
+ *     xyz_gradient_accum[i] += sqrt(gx^2 + gy^2 + gz^2) of viewspace_grad[i] ([P,3]);   denom[i] += 1;
+ *     max_radii2D[i] = max(max_radii2D[i], (float)radii[i])
+ * Rows with radii <= 0 are neither read nor written.  One kernel, no temporaries, no host synchronisation. */
+int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii, float* xyz_gradient_accum, float* denom,
+                           float* max_radii2D, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

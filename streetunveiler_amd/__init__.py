@@ -7,11 +7,15 @@ generator for the benchmark, and the frame-sharded multi-GPU helper.
 __version__ = "0.1.0"
 
 _IMAGE_LOSS = ("photometric_loss", "photometric_loss_torch", "image_loss_forward", "image_loss_backward", "image_loss_workspace")
-__all__ = list(_IMAGE_LOSS)
+_OPTIM = ("SurfelAdam", "adam_step", "adam_step_float64", "densification_stats", "densification_stats_torch")
+__all__ = list(_IMAGE_LOSS + _OPTIM)
 
 
-def __getattr__(name):   # the fused image loss, imported on first use (this package does not import torch by itself)
+def __getattr__(name):   # the fused image loss and the optimizer step, imported on first use (this package does not import torch by itself)
     if name in _IMAGE_LOSS:
         from . import image_loss
         return getattr(image_loss, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

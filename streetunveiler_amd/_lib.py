@@ -62,11 +62,20 @@ class SrImageView(C.Structure):
     _fields_ = [("final_T", C.c_void_p), ("n_contrib", C.c_void_p)]
 
 
+class SrAdamSegment(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
+
+
+SR_ADAM_MAX_SEGMENTS, SR_ADAM_CHUNK = 8, 4096
+
+
 # every symbol include/surfel_raster.h declares (checked by tests/test_abi.py)
 EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_error", "sr_geom_bytes", "sr_binning_bytes", "sr_image_bytes",
            "sr_backward_workspace_bytes", "sr_geom_view", "sr_binning_view", "sr_image_view", "sr_forward_plan", "sr_sh_gradient_expand", "sr_knn_workspace_bytes", "sr_knn_mean_dist2",
            "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
-           "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward"]
+           "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
+           "sr_adam_step", "sr_densification_stats"]
 
 _lib = None
 
@@ -147,6 +156,8 @@ def load():
     lib.sr_image_loss_workspace_bytes.restype = C.c_size_t
     lib.sr_image_loss_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]
     lib.sr_image_loss_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5
+    lib.sr_adam_step.argtypes = [C.POINTER(SrAdamSegment), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.sr_densification_stats.argtypes = [C.c_int32] + [C.c_void_p] * 6
     lib.sr_debug_radix_sort_temp_bytes.argtypes = [C.c_uint32]
     lib.sr_debug_radix_sort_temp_bytes.restype = C.c_size_t
     lib.sr_debug_radix_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]

@@ -34,6 +34,7 @@ SOURCES = [
     ("render_class.hip", []),
     ("postprocess.hip", []),
     ("image_loss.hip", []),
+    ("optimizer.hip", ["-ffp-contract=off"]),   # the Adam step's operation order is the one torch's single-tensor path states
     ("knn.hip", ["-ffp-contract=off"]),         # squared distances bit-identical to the brute-force oracle
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is

@@ -81,6 +81,11 @@ size_t image_loss_partial_bytes();
 hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s);
 hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
                                       float* g_alpha, hipStream_t s);
+// optimizer.hip
+bool adam_supported(const SrAdamSegment* segments, int n_segments);
+hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t s);
+hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
+                                      float* max_radii2D, hipStream_t s);
 }  // namespace sr
 
 using namespace sr;
@@ -963,6 +968,43 @@ int sr_image_loss_backward(int32_t W, int32_t H, int32_t C, float lambda_dssim, 
     if (!g_loss || !g_image) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_image is NULL");
     if (sky && (!g_sky || !g_alpha)) return fail(SR_ERR_INVALID_ARGUMENT, "with sky and alpha, g_sky and g_alpha are required");
     SR_HIP(launch_image_loss_backward(a, workspace, g_loss, g_image, g_sky, g_alpha, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream) {
+    if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 1..%d", n_segments, SR_ADAM_MAX_SEGMENTS);
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta1 %g not in [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta2 %g not in [0, 1)", beta2);
+    if (!(eps >= 0.0)) return fail(SR_ERR_INVALID_ARGUMENT, "eps %g is negative", eps);
+    for (int k = 0; k < n_segments; ++k) {
+        const SrAdamSegment& a = segments[k];
+        if (a.n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: n %lld is negative", k, (long long)a.n);
+        const void* ptrs[4] = {a.param, a.grad, a.exp_avg, a.exp_avg_sq};
+        const char* names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+        for (int j = 0; j < 4; ++j) {
+            if (!ptrs[j]) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is NULL", k, names[j]);
+            if ((uintptr_t)ptrs[j] & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is not 4-B aligned", k, names[j]);
+        }
+    }
+    if (!adam_supported(segments, n_segments)) return fail(SR_ERR_UNSUPPORTED, "the segments hold more than 2^31 chunks of %d elements", SR_ADAM_CHUNK);
+    SR_HIP(launch_adam_step(segments, n_segments, beta1, beta2, eps, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii, float* xyz_gradient_accum, float* denom,
+                           float* max_radii2D, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P == 0) return SR_OK;
+    if (!viewspace_grad) return fail(SR_ERR_INVALID_ARGUMENT, "viewspace_grad is NULL");
+    if (!radii) return fail(SR_ERR_INVALID_ARGUMENT, "radii is NULL");
+    if (!xyz_gradient_accum) return fail(SR_ERR_INVALID_ARGUMENT, "xyz_gradient_accum is NULL");
+    if (!denom) return fail(SR_ERR_INVALID_ARGUMENT, "denom is NULL");
+    if (!max_radii2D) return fail(SR_ERR_INVALID_ARGUMENT, "max_radii2D is NULL");
+    if (((uintptr_t)viewspace_grad | (uintptr_t)radii | (uintptr_t)xyz_gradient_accum | (uintptr_t)denom | (uintptr_t)max_radii2D) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "viewspace_grad / radii / xyz_gradient_accum / denom / max_radii2D: a pointer is not 4-B aligned");
+    SR_HIP(launch_densification_stats(P, viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D, static_cast<hipStream_t>(stream)));
     return SR_OK;
 }
 
