@@ -39,8 +39,8 @@ SOURCES = [
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blend_common.h"), os.path.join(os.path.dirname(HERE), "include", "surfel_raster.h"),
-           os.path.join(os.path.dirname(HERE), "include", "surfel_switches.h")]
+# every header of csrc/ and include/ (the listing source_digest() hashes): an object file is stale when any of them is newer
+HEADERS = sorted(os.path.join(d, f) for d in (CSRC, os.path.join(os.path.dirname(HERE), "include")) for f in os.listdir(d) if f.endswith(".h"))
 
 # The named switches of include/surfel_switches.h at their non-default values (SURVEY.md Appendix A's (!) items): each is a complete
 # build of the kernels with that -D in lib/variants/<name>/libsurfel_raster.so; a maintainer holding the real CUDA fork ships the one

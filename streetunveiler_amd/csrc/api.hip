@@ -7,86 +7,7 @@
 #include <atomic>
 #include <mutex>
 
-#include "common.h"
-
-namespace sr {
-// preprocess.hip
-hipError_t launch_preprocess_forward(int P, const FrameDev& f, const SrGaussians& g, float4* recs, uint32_t* depth_keys,
-                                     uint32_t* tiles_touched, uint2* rect, uint8_t* clamped, int32_t* radii, hipStream_t s);
-hipError_t launch_preprocess_backward(int P, const FrameDev& f, const SrGaussians& g, const int32_t* radii,
-                                      const uint8_t* clamped, const float4* recs, const float4* inst_grads, const uint8_t* written,
-                                      const uint32_t* tiles_touched, const SrGradients& out, hipStream_t s);
-hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
-hipError_t launch_sh_gradient_expand(int P, int M, int deg, int V, const float* means3D, const float* campos, const float* gc,
-                                     float* dL_dsh, hipStream_t s);
-// binning.hip
-size_t depth_sort_temp_bytes(int P);
-size_t tile_scan_temp_bytes(int P);
-size_t expand_x_hist_bytes(int P, int tiles_x);
-size_t expand_y_hist_bytes(uint32_t D, int tiles_y);
-hipError_t run_depth_sort(int P, const uint32_t* depth_keys, const uint2* rect, uint32_t* sorted_keys,
-                          uint32_t* sorted_gid, uint2* rect_sorted, void* temp, size_t temp_bytes, int rank_mode, int tiles_x, int tiles_y,
-                          const uint32_t* n_visible, hipStream_t s);
-hipError_t run_tile_count_scan(int P, const uint32_t* tiles_touched, uint32_t* first, void* block_base, size_t base_bytes, uint32_t* total_host,
-                               hipStream_t s);
-hipError_t run_expand_columns(int P, int tiles_x, int n_tiles, const uint2* rect_sorted, const uint32_t* sorted_gid, uint2* columns,
-                              uint32_t* n_columns, uint32_t* hist, uint32_t* row_total, uint32_t* tile_counts, int rank_mode, const uint32_t* n_visible,
-                              hipStream_t s);
-hipError_t run_expand_rows(uint32_t D, int tiles_x, int tiles_y, const uint2* columns, const uint32_t* n_columns, uint32_t* hist, uint32_t* row_total,
-                           uint32_t* point_list, uint32_t* tile_counts, int rank_mode, hipStream_t s);
-hipError_t run_tile_ranges_order(int n_tiles, const uint32_t* tile_counts, uint2* ranges, uint32_t* order, hipStream_t s);
-hipError_t run_capacity_guard(uint32_t* counts, uint32_t capacity, hipStream_t s);
-hipError_t launch_zero_bytes(void* p, size_t n, hipStream_t s);
-// render.hip
-hipError_t launch_render_forward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
-                                 const float* extra, float* out_color, float* out_allmap, float* final_T, uint32_t* n_contrib, uint16_t* hit_mask, int flags,
-                                 unsigned long long* counters, const uint32_t* frame_counts, hipStream_t s);
-hipError_t launch_render_backward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
-                                  const float* extra, const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                  const float* dL_dallmap, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, bool precomp_color_grads, hipStream_t s, int coop_mode);
-hipError_t launch_pair_decisions(const FrameDev& f, const uint2* ranges, const uint32_t* point_list, const float4* recs,
-                                 unsigned long long* valid_bits, unsigned long long* use3d_bits, hipStream_t s);
-hipError_t launch_class_partition(int P, int n_tiles, int n_classes, const float* class_cols, const int32_t* class_i32, const uint2* ranges,
-                                  const uint32_t* point_list, uint8_t* ids, uint32_t* cls_list, uint2* cls_ranges, hipStream_t s);
-hipError_t launch_class_forward(const FrameDev& f, int n_classes, const uint2* cls_ranges, const uint32_t* tile_order, const uint32_t* cls_list,
-                                const float4* recs, float* out_dist, float* cls_state, uint32_t* cls_last, uint32_t* tile_total, uint16_t* hit_mask,
-                                int cull, hipStream_t s);
-hipError_t launch_class_backward(const FrameDev& f, int n_classes, const uint2* cls_ranges, const uint32_t* tile_order, const uint32_t* cls_list,
-                                 const float4* recs, const float* cls_state, const uint32_t* cls_last, const uint32_t* tile_total,
-                                 const float* dL_ddist, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, int shared_rec_quads, hipStream_t s);
-hipError_t launch_color_gradients(int P, const FrameDev& f, const int32_t* radii, const uint8_t* clamped, const float4* recs, const float4* inst_grads,
-                                  const uint8_t* written, const uint32_t* tiles_touched, bool mask_clamped, float* dL_dcolors, hipStream_t s);
-// radix_sort.hip
-size_t radix_sort_temp_bytes(uint32_t n);
-hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t n,
-                            int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, int rank_mode,
-                            int rect_bx = 0, int rect_by = 0, const uint32_t* n_live = nullptr);
-hipError_t launch_rank_selfcheck(uint32_t* result, hipStream_t s);
-hipError_t lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, hipStream_t s);
-// knn.hip
-size_t knn_workspace_bytes(int nq, int nr);
-hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
-                          size_t ws_bytes, int rank_mode, hipStream_t s);
-// postprocess.hip
-struct PostCam { int W, H; float fx, fy, depth_ratio; const float* view; };
-hipError_t launch_postprocess_forward(const PostCam& cam, const float* allmap, float* rend_normal, float* surf_depth,
-                                      float* surf_normal, float* surf_point, hipStream_t s);
-hipError_t launch_postprocess_backward(const PostCam& cam, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
-                                       const float* g_surf_normal, const float* g_surf_point, float* scratch6, float* g_allmap,
-                                       hipStream_t s);
-// image_loss.hip
-struct LossImages { int W, H, C; float lambda; const float* image; const float* gt; const float* sky; const float* alpha; };
-bool image_loss_supported(int W, int H, int C);
-size_t image_loss_partial_bytes();
-hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s);
-hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
-                                      float* g_alpha, hipStream_t s);
-// optimizer.hip
-bool adam_supported(const SrAdamSegment* segments, int n_segments);
-hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t s);
-hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
-                                      float* max_radii2D, hipStream_t s);
-}  // namespace sr
+#include "launch.h"
 
 using namespace sr;
 
@@ -179,7 +100,7 @@ int stream_device(hipStream_t s, int* dev) {
 // else nothing this library can sort with (SR_ERR_UNSUPPORTED).  SR_FLAG_BALLOT_RANKING forces the ballots for one call.
 constexpr int kMaxDevices = 64;
 std::atomic<int> g_rank_mode[kMaxDevices];
-int rank_mode(hipStream_t s, bool force_ballot, int* mode) {
+int rank_mode(hipStream_t s, bool force_ballot, RankMode* mode) {
     int dev = 0;
     { const int rc = stream_device(s, &dev); if (rc != SR_OK) return rc; }
     if (dev < 0 || dev >= kMaxDevices) return fail(SR_ERR_UNSUPPORTED, "device index %d beyond %d", dev, kMaxDevices);
@@ -205,34 +126,42 @@ int rank_mode(hipStream_t s, bool force_ballot, int* mode) {
         g_rank_mode[dev].store(m, std::memory_order_release);
     }
     if (m == kRankNone) return fail(SR_ERR_UNSUPPORTED, "neither LDS-atomic nor ballot ranking passes the self-check on device %d", dev);
-    *mode = force_ballot ? (int)kRankBallot : m;
+    *mode = force_ballot ? kRankBallot : static_cast<RankMode>(m);
     return SR_OK;
 }
 
 // ---- buffer layouts ------------------------------------------------------------------------------
+// A layout = the byte offsets of a state buffer's regions (every region 256-B aligned) + its total; a view = the typed pointers of one
+// buffer carved by that layout.  Every entry point carves once, through these.
 constexpr int kMaxTilesPerAxis = SR_MAX_TILES_PER_AXIS;   // binning.hip kXpMaxBins: 10-bit row / column fields, 1024-entry LDS histograms
+template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
+
 struct GeomLayout {
     size_t recs, depth_keys, tiles_touched, rect, clamped, sorted_keys, sorted_gid, rect_sorted, first, sh_jac, block_base, base_bytes,
-        n_scan_blocks, temp, temp_bytes, total;
+        counts, temp, temp_bytes, total;
 };
 GeomLayout geom_layout(int P) {
     GeomLayout L{};
     const size_t n = (size_t)(P > 0 ? P : 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.recs = take(n * kRecFloats * 4);
-    L.depth_keys = take(n * 4);
-    L.tiles_touched = take(n * 4);
-    L.rect = take(n * 8);
-    L.clamped = take(n);
-    L.sorted_keys = take(n * 4);
-    L.sorted_gid = take(n * 4);
-    L.rect_sorted = take(n * 8);
-    L.first = take(n * 4);
-    L.sh_jac = take(n * 36);
+    Carver c;
+    L.recs = c.take(n * kRecFloats * 4);
+    L.depth_keys = c.take(n * 4);
+    L.tiles_touched = c.take(n * 4);
+    L.rect = c.take(n * 8);
+    L.clamped = c.take(n);
+    L.sorted_keys = c.take(n * 4);
+    L.sorted_gid = c.take(n * 4);
+    L.rect_sorted = c.take(n * 8);
+    L.first = c.take(n * 4);
+    L.sh_jac = c.take(n * 36);
     L.base_bytes = tile_scan_temp_bytes(P);
-    L.block_base = take(L.base_bytes);
-    L.n_scan_blocks = (n + 2047) / 2048;   // the scan's block size (radix_sort.hip kRsTile)
+    L.block_base = c.take(L.base_bytes);
+    const size_t n_scan_blocks = (n + 2047) / 2048;   // the scan's block size (radix_sort.hip kRsTile)
+    L.counts = L.block_base + n_scan_blocks * 4;      // the frame's count words follow the block bases: GeomView::counts
     static thread_local int memo_P = -1;
     static thread_local size_t memo_bytes = 0;
     if (memo_P != P) {   // the depth sort's ping-pong + histogram; later pass X's [tile columns][blocks] histogram (any frame width)
@@ -242,9 +171,25 @@ GeomLayout geom_layout(int P) {
         memo_P = P;
     }
     L.temp_bytes = memo_bytes;
-    L.temp = take(L.temp_bytes);
-    L.total = off;
+    L.temp = c.take(L.temp_bytes);
+    L.total = c.off;
     return L;
+}
+// The words of GeomView::counts (SrGeomView.frame_counts), left by the emission scan.  (kCountOverflow is a per-block count the scan is done
+// with by the time the capacity guard writes it.)
+enum FrameCount { kCountDuplicates = 0, kCountVisible = 1, kCountOverflow = 2 };
+struct GeomView {
+    float4* recs; uint32_t* depth_keys; uint32_t* tiles_touched; uint2* rect; uint8_t* clamped;
+    uint32_t* sorted_keys; uint32_t* sorted_gid; uint2* rect_sorted; uint32_t* first;
+    float* sh_jac;          // (the stand-alone class pass keeps its class id bytes here: it has no SH colour)
+    uint32_t* block_base; void* temp;
+    uint32_t* counts;       // [FrameCount]
+};
+GeomView geom_view(void* geom, const GeomLayout& L) {
+    return GeomView{at<float4>(geom, L.recs), at<uint32_t>(geom, L.depth_keys), at<uint32_t>(geom, L.tiles_touched), at<uint2>(geom, L.rect),
+                    at<uint8_t>(geom, L.clamped), at<uint32_t>(geom, L.sorted_keys), at<uint32_t>(geom, L.sorted_gid), at<uint2>(geom, L.rect_sorted),
+                    at<uint32_t>(geom, L.first), at<float>(geom, L.sh_jac), at<uint32_t>(geom, L.block_base), at<void>(geom, L.temp),
+                    at<uint32_t>(geom, L.counts)};
 }
 
 struct BinLayout {
@@ -254,20 +199,29 @@ BinLayout bin_layout(uint32_t D, int W, int H) {
     BinLayout L{};
     const size_t n = (size_t)(D > 0 ? D : 1);
     const int tiles = ((W + 7) / 8) * ((H + 7) / 8);   // sized for the smallest tile shape (8x8); the reference's 16x16 uses a quarter
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.columns = take(n * 8);   // column items of the expanding partition: at most D of them
-    L.point_list = take(n * 4);
-    L.hit_mask = take(n * 2);
-    L.ranges = take((size_t)(tiles > 0 ? tiles : 1) * 8);
-    L.order = take((size_t)(tiles > 0 ? tiles : 1) * 4);
-    L.tile_counts = take((size_t)(tiles > 0 ? tiles : 1) * 4);
-    L.row_total = take((size_t)kMaxTilesPerAxis * 4);
-    L.n_columns = take(4);
+    Carver c;
+    L.columns = c.take(n * 8);   // column items of the expanding partition: at most D of them
+    L.point_list = c.take(n * 4);
+    L.hit_mask = c.take(n * 2);
+    L.ranges = c.take((size_t)(tiles > 0 ? tiles : 1) * 8);
+    L.order = c.take((size_t)(tiles > 0 ? tiles : 1) * 4);
+    L.tile_counts = c.take((size_t)(tiles > 0 ? tiles : 1) * 4);
+    L.row_total = c.take((size_t)kMaxTilesPerAxis * 4);
+    L.n_columns = c.take(4);
     L.hist_bytes = expand_y_hist_bytes(D, (H + 7) / 8);
-    L.hist = take(L.hist_bytes);
-    L.total = off;
+    L.hist = c.take(L.hist_bytes);
+    L.total = c.off;
     return L;
+}
+struct BinView {
+    uint2* columns;          // (dead once pass Y has run: the class passes keep their class-ordered tile lists here, as uint32_t)
+    uint32_t* point_list; uint16_t* hit_mask; uint2* ranges; uint32_t* order; uint32_t* tile_counts; uint32_t* row_total; uint32_t* n_columns; uint32_t* hist;
+    uint32_t* class_list() const { return reinterpret_cast<uint32_t*>(columns); }
+};
+BinView bin_view(void* binning, const BinLayout& L) {
+    return BinView{at<uint2>(binning, L.columns), at<uint32_t>(binning, L.point_list), at<uint16_t>(binning, L.hit_mask), at<uint2>(binning, L.ranges),
+                   at<uint32_t>(binning, L.order), at<uint32_t>(binning, L.tile_counts), at<uint32_t>(binning, L.row_total), at<uint32_t>(binning, L.n_columns),
+                   at<uint32_t>(binning, L.hist)};
 }
 
 struct ImgLayout { size_t final_T, n_contrib, total; };
@@ -279,15 +233,39 @@ ImgLayout img_layout(int W, int H) {
     L.total = align_up(L.n_contrib + hw * 2 * 4, 256);
     return L;
 }
+struct ImgView { float* final_T; uint32_t* n_contrib; };
+ImgView img_view(void* image, const ImgLayout& L) { return ImgView{at<float>(image, L.final_T), at<uint32_t>(image, L.n_contrib)}; }
+
+// The backward workspace: one gradient record (96 B; 112 B with 9 colour channels) + one `written` byte per (tile, Gaussian) duplicate, in
+// emission order (a Gaussian's duplicates are contiguous).  K7 writes a record -- and sets the slot's byte in `written` -- only where some
+// pixel contributed; K8 looks at the byte before it touches the record, so neither the records nor anything but these D bytes need clearing.
+size_t record_bytes(int color_channels) { return (size_t)(color_channels == 9 ? kGradFloats + 4 : kGradFloats) * 4; }
+struct WorkspaceLayout { size_t written, total; };
+WorkspaceLayout workspace_layout(uint32_t D, int color_channels) {
+    const size_t n = (size_t)(D > 0 ? D : 1);
+    WorkspaceLayout L{};
+    L.written = align_up(n * record_bytes(color_channels), 256);
+    L.total = L.written + align_up(n, 256);
+    return L;
+}
+struct WorkspaceView { float4* records; uint8_t* written; };
+WorkspaceView workspace_view(void* workspace, uint32_t D, int color_channels) {
+    return WorkspaceView{static_cast<float4*>(workspace), at<uint8_t>(workspace, workspace_layout(D, color_channels).written)};
+}
+
+struct TileShape { int w, h; };
+TileShape tile_shape(const SrFrame* frame) {   // (0 = the reference's 16x16)
+    return TileShape{frame->tile_width > 0 ? frame->tile_width : kTile, frame->tile_height > 0 ? frame->tile_height : kTile};
+}
 
 int check_common(const SrFrame* frame, const SrGaussians* g) {
     if (!frame || !g) return fail(SR_ERR_INVALID_ARGUMENT, "frame / gaussians is NULL");
     if (frame->image_width <= 0 || frame->image_height <= 0) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", frame->image_width, frame->image_height);
     if (g->P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
     {
-        const int tw = frame->tile_width > 0 ? frame->tile_width : kTile, th = frame->tile_height > 0 ? frame->tile_height : kTile;
-        const bool known = (tw == 16 && th == 16) || (tw == 8 && th == 8) || (tw == 16 && th == 8) || (tw == 32 && th == 8) || (tw == 32 && th == 16);
-        if (!known) return fail(SR_ERR_UNSUPPORTED, "tile shape %dx%d not in {8x8, 16x8, 16x16, 32x8, 32x16}", tw, th);
+        const TileShape t = tile_shape(frame);
+        const bool known = (t.w == 16 && t.h == 16) || (t.w == 8 && t.h == 8) || (t.w == 16 && t.h == 8) || (t.w == 32 && t.h == 8) || (t.w == 32 && t.h == 16);
+        if (!known) return fail(SR_ERR_UNSUPPORTED, "tile shape %dx%d not in {8x8, 16x8, 16x16, 32x8, 32x16}", t.w, t.h);
     }
     if (!frame->bg || !frame->viewmatrix || !frame->projmatrix || !frame->campos) return fail(SR_ERR_INVALID_ARGUMENT, "bg / viewmatrix / projmatrix / campos must be non-NULL device pointers");
     if (g->P > 0) {
@@ -322,16 +300,6 @@ int check_backward_frame(const SrFrame* frame) {
     return SR_OK;
 }
 
-// SR_FLAG_ONE_WAVE_BACKWARD / SR_FLAG_COOP_BACKWARD / SR_FLAG_ROW_BACKWARD each pick the blend PAIR of a frame (forward and backward): the forward
-// tests them in one order, the backward in another, and the row-mapped backward reads cell-granular hit masks that only its own forward writes --
-// so at most one of them per call.  (Forward and backward of one frame must carry the same one: include/surfel_raster.h.)
-int check_blend_pair_flags(const SrFrame* frame) {
-    const uint32_t pair = frame->flags & (SR_FLAG_ONE_WAVE_BACKWARD | SR_FLAG_COOP_BACKWARD | SR_FLAG_ROW_BACKWARD);
-    if (pair & (pair - 1))
-        return fail(SR_ERR_INVALID_ARGUMENT, "SR_FLAG_ONE_WAVE_BACKWARD, SR_FLAG_COOP_BACKWARD and SR_FLAG_ROW_BACKWARD exclude each other (flags 0x%x)", pair);
-    return SR_OK;
-}
-
 FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
     FrameDev f{};
     f.W = frame->image_width; f.H = frame->image_height;
@@ -344,7 +312,8 @@ FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
         f.bw_W = (int)(focal_x * frame->tanfovx * 2); f.bw_H = (int)(focal_y * frame->tanfovy * 2);
     }
 #endif
-    f.tile_w = frame->tile_width > 0 ? frame->tile_width : kTile; f.tile_h = frame->tile_height > 0 ? frame->tile_height : kTile;
+    const TileShape t = tile_shape(frame);
+    f.tile_w = t.w; f.tile_h = t.h;
     f.inv_tile_w = 1.f / (float)f.tile_w; f.inv_tile_h = 1.f / (float)f.tile_h;
     f.tiles_x = (f.W + f.tile_w - 1) / f.tile_w; f.tiles_y = (f.H + f.tile_h - 1) / f.tile_h;
     f.sh_degree = frame->sh_degree; f.sh_coeffs = g->sh_coeffs;
@@ -355,8 +324,65 @@ FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
     f.overflow = nullptr;   // (set by the backward entry points in capacity mode)
     return f;
 }
+// what the per-Gaussian backward kernels read of the geometry state
+void set_backward_state(FrameDev* f, const SrFrame* frame, const GeomView& G) {
+    f->first = G.first; f->first_base = G.block_base; f->sh_jac = G.sh_jac;
+    if (frame->flags & SR_FLAG_BINNING_CAPACITY) f->overflow = G.counts + kCountOverflow;
+}
 
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+// The blend PAIR of a frame: which forward kernel, which backward kernel, and the hit-mask format the two share.  The forward and the
+// backward of one frame carry the same flags (include/surfel_raster.h) and both come through here, so they cannot disagree on the format
+// (a row-mapped backward on quadrant masks computed silently wrong gradients).  Only the 16x16 tile with three colour channels has a choice:
+//
+//   public flags (16x16, 3 channels)                 forward kernel                           backward kernel          hit masks
+//   blend_counters                                   kCounting                                as the pair flag says    per quadrant
+//   SR_FLAG_ROW_BACKWARD                             kRowsCellMasks                           kRows                    per 4x4 cell
+//   SR_FLAG_COOP_BACKWARD, culling on, no mapping    kCoop                                    kCoop                    per quadrant
+//   SR_FLAG_COOP_BACKWARD otherwise                  as without it                            kCoop                    per quadrant
+//   SR_FLAG_ONE_WAVE_BACKWARD                        as without it                            kOneWave                 per quadrant
+//   none of the three pair flags                     SR_FLAG_ROW_MAPPED_FORWARD: kRows        kByTileCount             per quadrant
+//                                                    SR_FLAG_QUADRANT_MAPPED_FORWARD or
+//                                                    SR_FLAG_NO_QUADRANT_CULL: kQuadrantBands
+//                                                    else: kDevicePicked
+//   every other tile shape / channel count           its one kernel (kCounting: 16x16 x 6)    kOneWave                 per quadrant
+//
+// Refused: two of the three pair flags; both mapping flags; SR_FLAG_ROW_MAPPED_FORWARD or SR_FLAG_ROW_BACKWARD off the 16x16 tile, with other
+// than three channels or with SR_FLAG_NO_QUADRANT_CULL -- and, in the forward call, with blend_counters; SR_FLAG_ROW_BACKWARD in a forward
+// call with SR_FLAG_QUADRANT_MAPPED_FORWARD or SR_FLAG_FORWARD_ONLY; blend_counters off 16x16 x {3, 6} or with SR_FLAG_FORWARD_ONLY.
+// `forward_call`: the preconditions of the forward-only flags (mapping, counters, forward-only) bind the forward call alone -- a backward
+// call does not read those flags.
+int choose_blend(const SrFrame* frame, const FrameDev& f, bool forward_call, BlendChoice* out) {
+    const uint32_t flags = frame->flags;
+    const uint32_t pair = flags & (SR_FLAG_ONE_WAVE_BACKWARD | SR_FLAG_COOP_BACKWARD | SR_FLAG_ROW_BACKWARD);
+    if (pair & (pair - 1))
+        return fail(SR_ERR_INVALID_ARGUMENT, "SR_FLAG_ONE_WAVE_BACKWARD, SR_FLAG_COOP_BACKWARD and SR_FLAG_ROW_BACKWARD exclude each other (flags 0x%x)", pair);
+    const bool reference = f.tile_w == 16 && f.tile_h == 16 && f.colors == 3;   // the reference's tile, three colour channels
+    const bool cull = !(flags & SR_FLAG_NO_QUADRANT_CULL), counters = forward_call && frame->blend_counters != nullptr;
+    const bool rows = forward_call && (flags & SR_FLAG_ROW_MAPPED_FORWARD), quads = forward_call && (flags & SR_FLAG_QUADRANT_MAPPED_FORWARD);
+    const bool fwd_only = forward_call && (flags & SR_FLAG_FORWARD_ONLY);
+    if (fwd_only && counters) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_FORWARD_ONLY and blend_counters exclude each other");
+    if (counters && !(f.tile_w == 16 && f.tile_h == 16 && (f.colors == 3 || f.colors == 6)))
+        return fail(SR_ERR_UNSUPPORTED, "blend_counters: the counting variant of the forward blend exists for the 16x16 tile with 3 or 6 colour channels only");
+    if (rows && quads) return fail(SR_ERR_INVALID_ARGUMENT, "SR_FLAG_ROW_MAPPED_FORWARD and SR_FLAG_QUADRANT_MAPPED_FORWARD exclude each other");
+    if (rows && (!reference || counters || !cull))
+        return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_MAPPED_FORWARD: 16x16 tile, three colour channels, no counters, culling on");
+    if ((pair & SR_FLAG_ROW_BACKWARD) && (!reference || counters || !cull || quads || fwd_only))
+        return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_BACKWARD: 16x16 tile, three colour channels, no counters, culling on, the row-mapped forward, a backward to follow");
+    out->cull = cull;
+    out->mask = HitMaskFormat::kQuadrant;
+    out->backward = BackwardBlend::kOneWave;
+    out->forward = counters ? ForwardBlend::kCounting : ForwardBlend::kQuadrantBands;
+    if (!reference) return SR_OK;
+    out->backward = (pair & SR_FLAG_ROW_BACKWARD) ? BackwardBlend::kRows
+                    : (pair & SR_FLAG_ONE_WAVE_BACKWARD) ? BackwardBlend::kOneWave
+                    : (pair & SR_FLAG_COOP_BACKWARD) ? BackwardBlend::kCoop : BackwardBlend::kByTileCount;
+    if (counters) return SR_OK;   // (beats everything else)
+    if (cull && !rows && !quads && (pair & SR_FLAG_COOP_BACKWARD)) out->forward = ForwardBlend::kCoop;
+    else if (pair & SR_FLAG_ROW_BACKWARD) { out->forward = ForwardBlend::kRowsCellMasks; out->mask = HitMaskFormat::kCell; }
+    else if (rows) out->forward = ForwardBlend::kRows;
+    else if (cull && !quads) out->forward = ForwardBlend::kDevicePicked;
+    return SR_OK;
+}
 
 }  // namespace
 
@@ -369,22 +395,17 @@ const char* sr_last_error(void) { return g_err; }
 size_t sr_geom_bytes(int32_t P) { return geom_layout(P).total; }
 size_t sr_binning_bytes(int32_t P, uint32_t num_rendered, int32_t W, int32_t H) { (void)P; return bin_layout(num_rendered, W, H).total; }
 size_t sr_image_bytes(int32_t W, int32_t H) { return img_layout(W, H).total; }
-static size_t record_bytes(int color_channels) { return (size_t)(color_channels == 9 ? kGradFloats + 4 : kGradFloats) * 4; }
-
-size_t sr_backward_workspace_bytes(int32_t P, uint32_t num_rendered, int32_t color_channels) {
-    (void)P;   // one gradient record (96 B; 112 B with 9 colour channels) + one "written" byte per (tile, Gaussian) duplicate
-    const size_t n = (size_t)(num_rendered > 0 ? num_rendered : 1);
-    return align_up(n * record_bytes(color_channels), 256) + align_up(n, 256);
-}
+size_t sr_backward_workspace_bytes(int32_t P, uint32_t num_rendered, int32_t color_channels) { (void)P; return workspace_layout(num_rendered, color_channels).total; }
 
 int sr_geom_view(void* geom, size_t geom_bytes, int32_t P, SrGeomView* out) {
     if (!geom || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const GeomLayout L = geom_layout(P);
     if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-    out->splats = at<float>(geom, L.recs); out->depth_keys = at<uint32_t>(geom, L.depth_keys);
-    out->tiles_touched = at<uint32_t>(geom, L.tiles_touched); out->clamped = at<uint8_t>(geom, L.clamped);
-    out->sorted_gid = at<uint32_t>(geom, L.sorted_gid);
-    out->frame_counts = at<uint32_t>(geom, L.block_base) + L.n_scan_blocks;
+    const GeomView G = geom_view(geom, L);
+    out->splats = reinterpret_cast<float*>(G.recs); out->depth_keys = G.depth_keys;
+    out->tiles_touched = G.tiles_touched; out->clamped = G.clamped;
+    out->sorted_gid = G.sorted_gid;
+    out->frame_counts = G.counts;
     return SR_OK;
 }
 
@@ -393,8 +414,9 @@ int sr_binning_view(void* binning, size_t binning_bytes, int32_t P, uint32_t D, 
     if (!binning || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const BinLayout L = bin_layout(D, W, H);
     if (binning_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, L.total);
-    out->point_list = at<uint32_t>(binning, L.point_list);
-    out->ranges = at<uint32_t>(binning, L.ranges); out->tile_order = at<uint32_t>(binning, L.order);
+    const BinView B = bin_view(binning, L);
+    out->point_list = B.point_list;
+    out->ranges = reinterpret_cast<uint32_t*>(B.ranges); out->tile_order = B.order;
     return SR_OK;
 }
 
@@ -402,7 +424,8 @@ int sr_image_view(void* image, size_t image_bytes, int32_t W, int32_t H, SrImage
     if (!image || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const ImgLayout L = img_layout(W, H);
     if (image_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, L.total);
-    out->final_T = at<float>(image, L.final_T); out->n_contrib = at<uint32_t>(image, L.n_contrib);
+    const ImgView I = img_view(image, L);
+    out->final_T = I.final_T; out->n_contrib = I.n_contrib;
     return SR_OK;
 }
 
@@ -416,68 +439,54 @@ int sr_forward_plan(const SrFrame* frame, const SrGaussians* g, void* geom, size
     if (!geom || !radii) return fail(SR_ERR_INVALID_ARGUMENT, "geom / radii is NULL");
     const GeomLayout L = geom_layout(P);
     if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
+    const GeomView G = geom_view(geom, L);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FrameDev f = make_frame(frame, g);
-    f.sh_jac = (frame->flags & SR_FLAG_FORWARD_ONLY) ? nullptr : at<float>(geom, L.sh_jac);   // (forward only: K8, its one reader, will not run)
+    f.sh_jac = (frame->flags & SR_FLAG_FORWARD_ONLY) ? nullptr : G.sh_jac;   // (forward only: K8, its one reader, will not run)
     {
         StageTimer t(SR_STAGE_PREPROCESS, s);
-        SR_HIP(launch_preprocess_forward(P, f, *g, at<float4>(geom, L.recs), at<uint32_t>(geom, L.depth_keys),
-                                         at<uint32_t>(geom, L.tiles_touched), at<uint2>(geom, L.rect), at<uint8_t>(geom, L.clamped), radii, s));
+        SR_HIP(launch_preprocess_forward(P, f, *g, G.recs, G.depth_keys, G.tiles_touched, G.rect, G.clamped, radii, s));
     }
     if (int rc = debug_sync(frame, s, "preprocess_forward")) return rc;
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(s, (frame->flags & SR_FLAG_BALLOT_RANKING) != 0, &sort_mode)) return rc;   // (first call on a device: ~20 us self-check)
     // D, the scan's grand total, is the one word the host reads back (the reference does the same between scan and duplicateWithKeys).
     // It travels through a pinned host word (one block per host thread; with one event per (thread, device) the only things this library
     // keeps): the last scan kernel stores it there itself when the word is mapped into the device's address space -- no copy kernel
     // between the scan and the host's wake-up -- else a DMA copy does.
-    int sort_mode = kRankUnknown;
-    if (int rc = rank_mode(s, (frame->flags & SR_FLAG_BALLOT_RANKING) != 0, &sort_mode)) return rc;   // (first call on a device: ~20 us self-check)
-    const int depth_sort_mode = sort_mode | ((frame->flags & SR_FLAG_ONE_SWEEP_SORT) ? 0x100 : 0);   // (radix_sort.hip kSortOneSweepBit)
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) {
-        // the sync-free forward: D stays on the device (SrGeomView.frame_counts); no pinned word, no event, no host wait -- nothing in this
-        // call that a stream capture could not record
-        {
-            StageTimer t(SR_STAGE_SCAN, s);
-            SR_HIP(run_tile_count_scan(P, at<uint32_t>(geom, L.tiles_touched), at<uint32_t>(geom, L.first), at<void>(geom, L.block_base), L.base_bytes, nullptr, s));
-        }
-        if (int rc = debug_sync(frame, s, "emission_scan")) return rc;
-        {
-            StageTimer t(SR_STAGE_DEPTH_SORT, s);
-            SR_HIP(run_depth_sort(P, at<uint32_t>(geom, L.depth_keys), at<uint2>(geom, L.rect), at<uint32_t>(geom, L.sorted_keys),
-                                  at<uint32_t>(geom, L.sorted_gid), at<uint2>(geom, L.rect_sorted), at<void>(geom, L.temp), L.temp_bytes, depth_sort_mode,
-                                  f.tiles_x, f.tiles_y, at<uint32_t>(geom, L.block_base) + L.n_scan_blocks + 1, s));
-        }
-        *num_rendered_host = 0xFFFFFFFFu;   // unknown to the host
-        return debug_sync(frame, s, "depth_sort");
-    }
-    uint32_t* pinned = pinned_words();
+    // SR_FLAG_BINNING_CAPACITY, the sync-free forward: D stays on the device (SrGeomView.frame_counts); no pinned word, no event, no host
+    // wait -- nothing in this call that a stream capture could not record.
+    const bool read_back = !(frame->flags & SR_FLAG_BINNING_CAPACITY);
+    uint32_t* pinned = read_back ? pinned_words() : nullptr;
     uint32_t* pinned_dev = nullptr;
     if (pinned && (hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0) != hipSuccess)) pinned_dev = nullptr;
     {
         StageTimer t(SR_STAGE_SCAN, s);
-        SR_HIP(run_tile_count_scan(P, at<uint32_t>(geom, L.tiles_touched), at<uint32_t>(geom, L.first), at<void>(geom, L.block_base),
-                                   L.base_bytes, pinned_dev, s));
+        SR_HIP(run_tile_count_scan(P, G.tiles_touched, G.first, G.block_base, L.base_bytes, pinned_dev, s));
     }
     if (int rc = debug_sync(frame, s, "emission_scan")) return rc;
     // The depth sort is queued BEHIND the read-back and the host waits for the read-back only, so the GPU sorts while the caller wakes
     // up, sizes the binning buffer from D and queues the second phase.
-    static thread_local hipEvent_t copied_ev[kMaxDevices] = {};   // one marker per (calling thread, device): an event belongs to its device
-    int dev = 0;
-    SR_HIP(hipGetDevice(&dev));
     hipEvent_t copied = nullptr;
-    if (dev >= 0 && dev < kMaxDevices) {
-        if (!copied_ev[dev] && hipEventCreateWithFlags(&copied_ev[dev], hipEventDisableTiming) != hipSuccess) copied_ev[dev] = nullptr;
-        copied = copied_ev[dev];
+    if (read_back) {
+        static thread_local hipEvent_t copied_ev[kMaxDevices] = {};   // one marker per (calling thread, device): an event belongs to its device
+        int dev = 0;
+        SR_HIP(hipGetDevice(&dev));
+        if (dev >= 0 && dev < kMaxDevices) {
+            if (!copied_ev[dev] && hipEventCreateWithFlags(&copied_ev[dev], hipEventDisableTiming) != hipSuccess) copied_ev[dev] = nullptr;
+            copied = copied_ev[dev];
+        }
+        if (!pinned_dev) SR_HIP(hipMemcpyAsync(pinned ? pinned : num_rendered_host, G.counts + kCountDuplicates, 4, hipMemcpyDeviceToHost, s));
+        if (copied && pinned && hipEventRecord(copied, s) != hipSuccess) copied = nullptr;   // (then: wait for the stream instead)
     }
-    if (!pinned_dev) {
-        uint32_t* dst = pinned ? pinned : num_rendered_host;
-        SR_HIP(hipMemcpyAsync(dst, at<uint32_t>(geom, L.block_base) + L.n_scan_blocks, 4, hipMemcpyDeviceToHost, s));   // the scan's grand total
-    }
-    if (copied && pinned && hipEventRecord(copied, s) != hipSuccess) copied = nullptr;   // (then: wait for the stream instead)
     {
         StageTimer t(SR_STAGE_DEPTH_SORT, s);
-        SR_HIP(run_depth_sort(P, at<uint32_t>(geom, L.depth_keys), at<uint2>(geom, L.rect), at<uint32_t>(geom, L.sorted_keys),
-                              at<uint32_t>(geom, L.sorted_gid), at<uint2>(geom, L.rect_sorted), at<void>(geom, L.temp), L.temp_bytes, depth_sort_mode,
-                              f.tiles_x, f.tiles_y, at<uint32_t>(geom, L.block_base) + L.n_scan_blocks + 1, s));   // (+1: the scan's visible count)
+        SR_HIP(run_depth_sort(P, G.depth_keys, G.rect, G.sorted_keys, G.sorted_gid, G.rect_sorted, G.temp, L.temp_bytes, sort_mode,
+                              (frame->flags & SR_FLAG_ONE_SWEEP_SORT) != 0, f.tiles_x, f.tiles_y, G.counts + kCountVisible, s));
+    }
+    if (!read_back) {
+        *num_rendered_host = 0xFFFFFFFFu;   // unknown to the host
+        return debug_sync(frame, s, "depth_sort");
     }
     if (int rc = debug_sync(frame, s, "depth_sort")) return rc;
     if (copied && pinned) SR_HIP(hipEventSynchronize(copied));
@@ -488,7 +497,7 @@ int sr_forward_plan(const SrFrame* frame, const SrGaussians* g, void* geom, size
 
 namespace {
 // K3..K5 (duplicate emission, tile partition, tile ranges + dispatch order): shared by the blend forward and the per-class pass
-int bin_duplicates(const SrFrame* frame, const SrGaussians* g, const FrameDev& f, void* geom, size_t geom_bytes, void* binning, const BinLayout& B,
+int bin_duplicates(const SrFrame* frame, const SrGaussians* g, const FrameDev& f, void* geom, size_t geom_bytes, const BinView& B,
                    uint32_t D, hipStream_t s, float4** recs_out) {
     const int P = g->P;
     const int n_tiles = f.tiles_x * f.tiles_y;
@@ -497,35 +506,32 @@ int bin_duplicates(const SrFrame* frame, const SrGaussians* g, const FrameDev& f
         if (!geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL");
         const GeomLayout L = geom_layout(P);
         if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-        float4* recs = at<float4>(geom, L.recs);
-        *recs_out = recs;
+        const GeomView G = geom_view(geom, L);
+        *recs_out = G.recs;
         if (f.tiles_x > kMaxTilesPerAxis || f.tiles_y > kMaxTilesPerAxis)
             return fail(SR_ERR_INVALID_ARGUMENT, "%d x %d tiles: at most %d per axis (use a larger tile)", f.tiles_x, f.tiles_y, kMaxTilesPerAxis);
         if (L.temp_bytes < expand_x_hist_bytes(P, f.tiles_x)) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom scratch too small for the column histogram");
-        int sort_mode = kRankUnknown;
+        RankMode sort_mode = kRankUnknown;
         if (int rc = rank_mode(s, (frame->flags & SR_FLAG_BALLOT_RANKING) != 0, &sort_mode)) return rc;
         if (frame->flags & SR_FLAG_BINNING_CAPACITY)   // D = the caller's capacity: does the frame fit?  (else: nothing is binned, the flag is set)
-            SR_HIP(run_capacity_guard(at<uint32_t>(geom, L.block_base) + L.n_scan_blocks, D, s));
+            SR_HIP(run_capacity_guard(G.counts, D, s));
         {
             StageTimer t(SR_STAGE_EXPAND_X, s);
-            SR_HIP(run_expand_columns(P, f.tiles_x, n_tiles, at<uint2>(geom, L.rect_sorted), at<uint32_t>(geom, L.sorted_gid), at<uint2>(binning, B.columns),
-                                      at<uint32_t>(binning, B.n_columns), at<uint32_t>(geom, L.temp), at<uint32_t>(binning, B.row_total),
-                                      at<uint32_t>(binning, B.tile_counts), sort_mode, at<uint32_t>(geom, L.block_base) + L.n_scan_blocks + 1, s));
+            SR_HIP(run_expand_columns(P, f.tiles_x, n_tiles, G.rect_sorted, G.sorted_gid, B.columns, B.n_columns, static_cast<uint32_t*>(G.temp), B.row_total,
+                                      B.tile_counts, sort_mode, G.counts + kCountVisible, s));
         }
         if (int rc = debug_sync(frame, s, "expand_columns")) return rc;
         {
             StageTimer t(SR_STAGE_EXPAND_Y, s);
-            SR_HIP(run_expand_rows(D, f.tiles_x, f.tiles_y, at<uint2>(binning, B.columns), at<uint32_t>(binning, B.n_columns),
-                                   at<uint32_t>(binning, B.hist), at<uint32_t>(binning, B.row_total), at<uint32_t>(binning, B.point_list),
-                                   at<uint32_t>(binning, B.tile_counts), sort_mode, s));
+            SR_HIP(run_expand_rows(D, f.tiles_x, f.tiles_y, B.columns, B.n_columns, B.hist, B.row_total, B.point_list, B.tile_counts, sort_mode, s));
         }
         if (int rc = debug_sync(frame, s, "expand_rows")) return rc;
     } else {
-        SR_HIP(launch_zero_bytes(at<uint32_t>(binning, B.tile_counts), sizeof(uint32_t) * (size_t)n_tiles, s));   // (no partition ran)
+        SR_HIP(launch_zero_bytes(B.tile_counts, sizeof(uint32_t) * (size_t)n_tiles, s));   // (no partition ran)
     }
     {
         StageTimer t(SR_STAGE_RANGES, s);
-        SR_HIP(run_tile_ranges_order(n_tiles, at<uint32_t>(binning, B.tile_counts), at<uint2>(binning, B.ranges), at<uint32_t>(binning, B.order), s));
+        SR_HIP(run_tile_ranges_order(n_tiles, B.tile_counts, B.ranges, B.order, s));
     }
     return debug_sync(frame, s, "tile_ranges");
 }
@@ -545,15 +551,23 @@ ClassLayout class_layout(int W, int H, int n_classes) {
     L.total = L.ranges + align_up((tiles > 0 ? tiles : 1) * n * 8, 256);
     return L;
 }
+struct ClassView { float* state; uint32_t* last; uint32_t* tile_total; uint2* ranges; };
+ClassView class_view(void* class_image, const ClassLayout& L) {
+    return ClassView{at<float>(class_image, L.state), at<uint32_t>(class_image, L.last), at<uint32_t>(class_image, L.tile_total), at<uint2>(class_image, L.ranges)};
+}
 
-int check_class_pass(const SrFrame* frame, const SrGaussians* g, int n_classes) {
+// The preconditions of the four class entry points.  They differ in where the class ids come from -- column 0 of colors_precomp[P,3] (the
+// stand-alone pass) or an int32 array of their own (the pass on the binning of a colour pass, whose colours stay what they are) -- and in
+// whether a precomputed transMat is refused.
+enum class ClassIds { kInColors, kOwnArray };
+int check_class_pass(const SrFrame* frame, const SrGaussians* g, int n_classes, ClassIds ids, bool refuse_transmat) {
     if (int rc = check_common(frame, g)) return rc;
     if (frame->flags & SR_FLAG_BINNING_CAPACITY) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY serves the operator (sr_forward_* / sr_backward*), not the per-class pass");
     if (n_classes < 1 || n_classes > 6) return fail(SR_ERR_UNSUPPORTED, "n_classes %d not in 1..6", n_classes);
-    const int tw = frame->tile_width > 0 ? frame->tile_width : kTile, th = frame->tile_height > 0 ? frame->tile_height : kTile;
-    (void)tw; (void)th;   // (every tile shape check_common accepts: 8x8, 16x8, 16x16, 32x8, 32x16)
-    if (g->P > 0 && (g->shs || !g->colors_precomp || (g->color_channels != 0 && g->color_channels != 3)))
+    // (every tile shape check_common accepts: 8x8, 16x8, 16x16, 32x8, 32x16)
+    if (ids == ClassIds::kInColors && g->P > 0 && (g->shs || !g->colors_precomp || (g->color_channels != 0 && g->color_channels != 3)))
         return fail(SR_ERR_INVALID_ARGUMENT, "the per-class distortion pass takes the class ids in colors_precomp[P,3] (column 0), no SHs");
+    if (refuse_transmat && g->transMat_precomp) return fail(SR_ERR_UNSUPPORTED, "the per-class pass takes scales and rotations, not a precomputed transMat");
     return SR_OK;
 }
 }  // namespace
@@ -562,38 +576,26 @@ int sr_forward_render(const SrFrame* frame, const SrGaussians* g, void* geom, si
                       size_t binning_bytes, void* image, size_t image_bytes, uint32_t D, float* out_color,
                       float* out_allmap, void* stream) {
     if (int rc = check_common(frame, g)) return rc;
-    if (int rc = check_blend_pair_flags(frame)) return rc;
+    const FrameDev f = make_frame(frame, g);
+    BlendChoice blend;
+    if (int rc = choose_blend(frame, f, true, &blend)) return rc;
     const bool fwd_only = (frame->flags & SR_FLAG_FORWARD_ONLY) != 0;   // no backward follows: its state (image buffer, hit masks) is not written
     if (!binning || (!image && !fwd_only) || !out_color || !out_allmap) return fail(SR_ERR_INVALID_ARGUMENT, "binning / image / out_color / out_allmap is NULL");
     const int W = frame->image_width, H = frame->image_height;
-    const BinLayout B = bin_layout(D, W, H);
-    const ImgLayout I = img_layout(W, H);
-    if (binning_bytes < B.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, B.total);
-    if (!fwd_only && image_bytes < I.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, I.total);
-    if (fwd_only && frame->blend_counters) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_FORWARD_ONLY and blend_counters exclude each other");
+    const BinLayout BL = bin_layout(D, W, H);
+    const ImgLayout IL = img_layout(W, H);
+    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
+    if (!fwd_only && image_bytes < IL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, IL.total);
+    const BinView B = bin_view(binning, BL);
+    const ImgView I = fwd_only ? ImgView{nullptr, nullptr} : img_view(image, IL);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const FrameDev f = make_frame(frame, g);
-    if (frame->blend_counters && !(f.tile_w == 16 && f.tile_h == 16 && (f.colors == 3 || f.colors == 6)))
-        return fail(SR_ERR_UNSUPPORTED, "blend_counters: the counting variant of the forward blend exists for the 16x16 tile with 3 or 6 colour channels only");
     float4* recs = nullptr;
-    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, binning, B, D, s, &recs)) return rc;
+    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, B, D, s, &recs)) return rc;
     {
         StageTimer t(SR_STAGE_BLEND_FWD, s);
-        const bool rows = (frame->flags & SR_FLAG_ROW_MAPPED_FORWARD) != 0, quads = (frame->flags & SR_FLAG_QUADRANT_MAPPED_FORWARD) != 0;
-        if (rows && quads) return fail(SR_ERR_INVALID_ARGUMENT, "SR_FLAG_ROW_MAPPED_FORWARD and SR_FLAG_QUADRANT_MAPPED_FORWARD exclude each other");
-        if (rows && (!(f.tile_w == 16 && f.tile_h == 16 && f.colors == 3) || frame->blend_counters || (frame->flags & SR_FLAG_NO_QUADRANT_CULL)))
-            return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_MAPPED_FORWARD: 16x16 tile, three colour channels, no counters, culling on");
-        const bool cells = (frame->flags & SR_FLAG_ROW_BACKWARD) != 0;
-        if (cells && (!(f.tile_w == 16 && f.tile_h == 16 && f.colors == 3) || frame->blend_counters || (frame->flags & SR_FLAG_NO_QUADRANT_CULL) || quads || fwd_only))
-            return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_BACKWARD: 16x16 tile, three colour channels, no counters, culling on, the row-mapped forward, a backward to follow");
-        const int flags = ((frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1) | (frame->blend_counters ? 2 : 0) | (rows ? 4 : 0) | (quads ? 8 : 0) |
-                          ((frame->flags & SR_FLAG_ONE_WAVE_BACKWARD) ? 16 : 0) | ((frame->flags & SR_FLAG_COOP_BACKWARD) ? 32 : 0) |   // (the few-tile kernels: never / always)
-                          (cells ? 64 : 0);
-        const GeomLayout GL = geom_layout(g->P);   // (D and the visible count, left in the geometry state by the emission scan)
-        SR_HIP(launch_render_forward(f, at<uint2>(binning, B.ranges), at<uint32_t>(binning, B.order), at<uint32_t>(binning, B.point_list), recs, g->colors_precomp, out_color,
-                                     out_allmap, fwd_only ? nullptr : at<float>(image, I.final_T), fwd_only ? nullptr : at<uint32_t>(image, I.n_contrib),
-                                     fwd_only ? nullptr : at<uint16_t>(binning, B.hit_mask), flags,
-                                     reinterpret_cast<unsigned long long*>(frame->blend_counters), at<uint32_t>(geom, GL.block_base) + GL.n_scan_blocks, s));
+        const GeomView G = geom_view(geom, geom_layout(g->P));   // (D and the visible count, left in the geometry state by the emission scan)
+        SR_HIP(launch_render_forward(f, B.ranges, B.order, B.point_list, recs, g->colors_precomp, out_color, out_allmap, I.final_T, I.n_contrib,
+                                     fwd_only ? nullptr : B.hit_mask, blend, reinterpret_cast<unsigned long long*>(frame->blend_counters), G.counts, s));
     }
     return debug_sync(frame, s, "render_forward");
 }
@@ -602,31 +604,31 @@ size_t sr_class_image_bytes(int32_t W, int32_t H, int32_t n_classes) { return cl
 
 int sr_class_forward_render(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, void* geom, size_t geom_bytes, void* binning,
                             size_t binning_bytes, void* class_image, size_t class_image_bytes, uint32_t D, float* out_dist, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes)) return rc;
+    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kInColors, false)) return rc;
     if (!binning || !class_image || !out_dist) return fail(SR_ERR_INVALID_ARGUMENT, "binning / class_image / out_dist is NULL");
     if (g->P > 0 && !geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL (the class ids of the P Gaussians are staged in it, even when no duplicate was emitted)");
     const int W = frame->image_width, H = frame->image_height;
-    const BinLayout B = bin_layout(D, W, H);
-    const ClassLayout C = class_layout(W, H, n_classes);
-    if (binning_bytes < B.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, B.total);
-    if (class_image_bytes < C.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class image buffer %zu < %zu", class_image_bytes, C.total);
+    const BinLayout BL = bin_layout(D, W, H);
+    const ClassLayout CL = class_layout(W, H, n_classes);
+    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
+    if (class_image_bytes < CL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class image buffer %zu < %zu", class_image_bytes, CL.total);
+    const BinView B = bin_view(binning, BL);
+    const ClassView C = class_view(class_image, CL);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const FrameDev f = make_frame(frame, g);
     float4* recs = nullptr;
-    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, binning, B, D, s, &recs)) return rc;
+    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, B, D, s, &recs)) return rc;
     {
         // every tile list, stably partitioned by class: [class 0 by depth | class 1 by depth | ...] + a (begin, end) pair per (tile, class)
         StageTimer t(SR_STAGE_CLASS_PARTITION, s);
-        const GeomLayout GL = geom_layout(g->P);
-        SR_HIP(launch_class_partition(g->P, f.tiles_x * f.tiles_y, n_classes, g->colors_precomp, nullptr, at<uint2>(binning, B.ranges), at<uint32_t>(binning, B.point_list),
-                                      g->P > 0 && geom ? at<uint8_t>(geom, GL.sh_jac) : nullptr, at<uint32_t>(binning, B.columns), at<uint2>(class_image, C.ranges), s));
+        uint8_t* ids = g->P > 0 && geom ? reinterpret_cast<uint8_t*>(geom_view(geom, geom_layout(g->P)).sh_jac) : nullptr;
+        SR_HIP(launch_class_partition(g->P, f.tiles_x * f.tiles_y, n_classes, g->colors_precomp, nullptr, B.ranges, B.point_list, ids, B.class_list(), C.ranges, s));
     }
     if (int rc = debug_sync(frame, s, "class_partition")) return rc;
     {
         StageTimer t(SR_STAGE_CLASS_FWD, s);
-        SR_HIP(launch_class_forward(f, n_classes, at<uint2>(class_image, C.ranges), at<uint32_t>(binning, B.order), at<uint32_t>(binning, B.columns), recs, out_dist,
-                                    at<float>(class_image, C.state), at<uint32_t>(class_image, C.last), at<uint32_t>(class_image, C.tile_total),
-                                    at<uint16_t>(binning, B.hit_mask), (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
+        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), recs, out_dist, C.state, C.last, C.tile_total, B.hit_mask,
+                                    (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
     }
     return debug_sync(frame, s, "class_forward");
 }
@@ -634,7 +636,7 @@ int sr_class_forward_render(const SrFrame* frame, const SrGaussians* g, int32_t 
 int sr_class_backward(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, const int32_t* radii, void* geom, size_t geom_bytes,
                       void* binning, size_t binning_bytes, void* class_image, size_t class_image_bytes, uint32_t D, const float* dL_ddist,
                       void* workspace, size_t workspace_bytes, const SrGradients* grads, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes)) return rc;
+    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kInColors, false)) return rc;
     if (int rc = check_backward_frame(frame)) return rc;
     if (!grads) return fail(SR_ERR_INVALID_ARGUMENT, "grads is NULL");
     const int P = g->P;
@@ -642,28 +644,28 @@ int sr_class_backward(const SrFrame* frame, const SrGaussians* g, int32_t n_clas
     if (!radii || !geom || !binning || !class_image || !dL_ddist || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
     const int W = frame->image_width, H = frame->image_height;
     const GeomLayout L = geom_layout(P);
-    const BinLayout B = bin_layout(D, W, H);
-    const ClassLayout C = class_layout(W, H, n_classes);
-    if (geom_bytes < L.total || binning_bytes < B.total || class_image_bytes < C.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
-    if (workspace_bytes < sr_backward_workspace_bytes(P, D, 3)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, sr_backward_workspace_bytes(P, D, 3));
+    const BinLayout BL = bin_layout(D, W, H);
+    const ClassLayout CL = class_layout(W, H, n_classes);
+    if (geom_bytes < L.total || binning_bytes < BL.total || class_image_bytes < CL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
+    if (workspace_bytes < workspace_layout(D, 3).total) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, workspace_layout(D, 3).total);
+    const GeomView G = geom_view(geom, L);
+    const BinView B = bin_view(binning, BL);
+    const ClassView C = class_view(class_image, CL);
+    const WorkspaceView ws = workspace_view(workspace, D, 3);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FrameDev f = make_frame(frame, g);
-    f.first = at<uint32_t>(geom, L.first); f.first_base = at<uint32_t>(geom, L.block_base); f.sh_jac = at<float>(geom, L.sh_jac);
-    float4* inst_grads = static_cast<float4*>(workspace);
-    uint8_t* written = static_cast<uint8_t*>(workspace) + align_up((size_t)(D > 0 ? D : 1) * record_bytes(3), 256);
+    f.first = G.first; f.first_base = G.block_base; f.sh_jac = G.sh_jac;
     {
         StageTimer t(SR_STAGE_CLASS_BWD, s);
-        if (D > 0) SR_HIP(launch_zero_bytes(written, D, s));
+        if (D > 0) SR_HIP(launch_zero_bytes(ws.written, D, s));
         if (D > 0)
-            SR_HIP(launch_class_backward(f, n_classes, at<uint2>(class_image, C.ranges), at<uint32_t>(binning, B.order), at<uint32_t>(binning, B.columns), at<float4>(geom, L.recs),
-                                         at<float>(class_image, C.state), at<uint32_t>(class_image, C.last), at<uint32_t>(class_image, C.tile_total), dL_ddist,
-                                         at<uint16_t>(binning, B.hit_mask), inst_grads, written, 0, s));
+            SR_HIP(launch_class_backward(f, n_classes, C.ranges, B.order, B.class_list(), G.recs, C.state, C.last, C.tile_total, dL_ddist, B.hit_mask,
+                                         ws.records, ws.written, 0, s));
     }
     if (int rc = debug_sync(frame, s, "class_backward")) return rc;
     {
         StageTimer t(SR_STAGE_PREPROCESS_BWD, s);
-        SR_HIP(launch_preprocess_backward(P, f, *g, radii, at<uint8_t>(geom, L.clamped), at<float4>(geom, L.recs), inst_grads, written,
-                                          at<uint32_t>(geom, L.tiles_touched), *grads, s));
+        SR_HIP(launch_preprocess_backward(P, f, *g, radii, G.clamped, G.recs, ws.records, ws.written, G.tiles_touched, *grads, s));
     }
     return debug_sync(frame, s, "preprocess_backward");
 }
@@ -685,36 +687,34 @@ size_t sr_class_shared_bytes(int32_t P, int32_t W, int32_t H, int32_t n_classes,
 
 int sr_class_forward_shared(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, const int32_t* classes, void* geom, size_t geom_bytes,
                             void* binning, size_t binning_bytes, void* class_state, size_t class_state_bytes, uint32_t D, float* out_dist, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY serves the operator (sr_forward_* / sr_backward*), not the per-class pass");
-    if (n_classes < 1 || n_classes > 6) return fail(SR_ERR_UNSUPPORTED, "n_classes %d not in 1..6", n_classes);
+    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kOwnArray, true)) return rc;
     if (!binning || !class_state || !out_dist || (g->P > 0 && !classes)) return fail(SR_ERR_INVALID_ARGUMENT, "binning / class_state / out_dist / classes is NULL");
-    if (g->transMat_precomp) return fail(SR_ERR_UNSUPPORTED, "the per-class pass takes scales and rotations, not a precomputed transMat");
     const int W = frame->image_width, H = frame->image_height, P = g->P;
-    const BinLayout B = bin_layout(D, W, H);
-    const ClassSharedLayout S = class_shared_layout(P, W, H, n_classes, D);
-    if (binning_bytes < B.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, B.total);
-    if (class_state_bytes < S.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class state buffer %zu < %zu", class_state_bytes, S.total);
+    const BinLayout BL = bin_layout(D, W, H);
+    const ClassSharedLayout SL = class_shared_layout(P, W, H, n_classes, D);
+    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
+    if (class_state_bytes < SL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class state buffer %zu < %zu", class_state_bytes, SL.total);
     float4* recs = nullptr;
     if (P > 0 && D > 0) {
         if (!geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL");
         const GeomLayout L = geom_layout(P);
         if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-        recs = at<float4>(geom, L.recs);
+        recs = geom_view(geom, L).recs;
     }
+    const BinView B = bin_view(binning, BL);
+    const ClassView C = class_view(class_state, SL.C);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const FrameDev f = make_frame(frame, g);
     {
         StageTimer t(SR_STAGE_CLASS_PARTITION, s);
-        SR_HIP(launch_class_partition(P, f.tiles_x * f.tiles_y, n_classes, nullptr, classes, at<uint2>(binning, B.ranges), at<uint32_t>(binning, B.point_list),
-                                      at<uint8_t>(class_state, S.ids), at<uint32_t>(binning, B.columns), at<uint2>(class_state, S.C.ranges), s));
+        SR_HIP(launch_class_partition(P, f.tiles_x * f.tiles_y, n_classes, nullptr, classes, B.ranges, B.point_list, at<uint8_t>(class_state, SL.ids), B.class_list(),
+                                      C.ranges, s));
     }
     if (int rc = debug_sync(frame, s, "class_partition")) return rc;
     {
         StageTimer t(SR_STAGE_CLASS_FWD, s);
-        SR_HIP(launch_class_forward(f, n_classes, at<uint2>(class_state, S.C.ranges), at<uint32_t>(binning, B.order), at<uint32_t>(binning, B.columns), recs, out_dist,
-                                    at<float>(class_state, S.C.state), at<uint32_t>(class_state, S.C.last), at<uint32_t>(class_state, S.C.tile_total),
-                                    at<uint16_t>(class_state, S.hit), (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
+        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), recs, out_dist, C.state, C.last, C.tile_total, at<uint16_t>(class_state, SL.hit),
+                                    (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
     }
     return debug_sync(frame, s, "class_forward");
 }
@@ -722,65 +722,61 @@ int sr_class_forward_shared(const SrFrame* frame, const SrGaussians* g, int32_t 
 int sr_class_backward_shared(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, void* geom, size_t geom_bytes, void* binning,
                              size_t binning_bytes, void* class_state, size_t class_state_bytes, uint32_t D, const float* dL_ddist, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY serves the operator (sr_forward_* / sr_backward*), not the per-class pass");
+    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kOwnArray, false)) return rc;
     if (int rc = check_backward_frame(frame)) return rc;
-    if (n_classes < 1 || n_classes > 6) return fail(SR_ERR_UNSUPPORTED, "n_classes %d not in 1..6", n_classes);
     const int P = g->P;
     if (P == 0 || D == 0) return SR_OK;
     if (!geom || !binning || !class_state || !dL_ddist || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
     const int W = frame->image_width, H = frame->image_height;
     const GeomLayout L = geom_layout(P);
-    const BinLayout B = bin_layout(D, W, H);
-    const ClassSharedLayout S = class_shared_layout(P, W, H, n_classes, D);
-    if (geom_bytes < L.total || binning_bytes < B.total || class_state_bytes < S.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
-    if (workspace_bytes < sr_backward_workspace_bytes(P, D, g->color_channels)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, sr_backward_workspace_bytes(P, D, g->color_channels));
+    const BinLayout BL = bin_layout(D, W, H);
+    const ClassSharedLayout SL = class_shared_layout(P, W, H, n_classes, D);
+    if (geom_bytes < L.total || binning_bytes < BL.total || class_state_bytes < SL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
+    const size_t ws_bytes = workspace_layout(D, g->color_channels).total;
+    if (workspace_bytes < ws_bytes) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, ws_bytes);
+    const GeomView G = geom_view(geom, L);
+    const BinView B = bin_view(binning, BL);
+    const ClassView C = class_view(class_state, SL.C);
+    // the records and flags sr_backward_blend of the SAME frame left in the workspace: this pass adds to them
+    const WorkspaceView ws = workspace_view(workspace, D, g->color_channels);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FrameDev f = make_frame(frame, g);
-    f.first = at<uint32_t>(geom, L.first); f.first_base = at<uint32_t>(geom, L.block_base);
-    // the records and flags sr_backward_blend of the SAME frame left in the workspace: this pass adds to them
-    float4* inst_grads = static_cast<float4*>(workspace);
-    uint8_t* written = static_cast<uint8_t*>(workspace) + align_up((size_t)D * record_bytes(g->color_channels), 256);
+    f.first = G.first; f.first_base = G.block_base;
     {
         StageTimer t(SR_STAGE_CLASS_BWD, s);
-        SR_HIP(launch_class_backward(f, n_classes, at<uint2>(class_state, S.C.ranges), at<uint32_t>(binning, B.order), at<uint32_t>(binning, B.columns), at<float4>(geom, L.recs),
-                                     at<float>(class_state, S.C.state), at<uint32_t>(class_state, S.C.last), at<uint32_t>(class_state, S.C.tile_total), dL_ddist,
-                                     at<uint16_t>(class_state, S.hit), inst_grads, written, (int)(record_bytes(g->color_channels) / 16), s));
+        SR_HIP(launch_class_backward(f, n_classes, C.ranges, B.order, B.class_list(), G.recs, C.state, C.last, C.tile_total, dL_ddist, at<uint16_t>(class_state, SL.hit),
+                                     ws.records, ws.written, (int)(record_bytes(g->color_channels) / 16), s));
     }
     return debug_sync(frame, s, "class_backward_shared");
 }
 
 namespace {
 struct BackwardCtx {
-    int P; GeomLayout L; BinLayout B; ImgLayout I; FrameDev f; float4* inst_grads; uint8_t* written; hipStream_t s;
+    int P; GeomView G; BinView B; ImgView I; WorkspaceView ws; FrameDev f; BlendChoice blend; hipStream_t s;
 };
 // argument checks and buffer carving shared by the backward entry points
 int backward_ctx(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes,
                  void* image, size_t image_bytes, uint32_t D, void* workspace, size_t workspace_bytes, void* stream, BackwardCtx* c) {
     if (int rc = check_common(frame, g)) return rc;
     if (int rc = check_backward_frame(frame)) return rc;
-    if (int rc = check_blend_pair_flags(frame)) return rc;
-    const FrameDev shape = make_frame(frame, g);   // (the forward's preconditions of the row-mapped pair, on the same derived tile / channels)
-    if ((frame->flags & SR_FLAG_ROW_BACKWARD) && (!(shape.tile_w == 16 && shape.tile_h == 16 && shape.colors == 3) || (frame->flags & SR_FLAG_NO_QUADRANT_CULL)))
-        return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_ROW_BACKWARD: 16x16 tile, three colour channels, culling on (as in the forward of the frame)");
+    c->f = make_frame(frame, g);
+    if (int rc = choose_blend(frame, c->f, false, &c->blend)) return rc;
     c->P = g->P;
     if (c->P == 0) return SR_OK;
     if (!geom || !binning || !image || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
     const int W = frame->image_width, H = frame->image_height;
-    c->L = geom_layout(c->P); c->B = bin_layout(D, W, H); c->I = img_layout(W, H);
-    if (geom_bytes < c->L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, c->L.total);
-    if (binning_bytes < c->B.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, c->B.total);
-    if (image_bytes < c->I.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, c->I.total);
-    if (workspace_bytes < sr_backward_workspace_bytes(c->P, D, g->color_channels)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, sr_backward_workspace_bytes(c->P, D, g->color_channels));
+    const GeomLayout L = geom_layout(c->P);
+    const BinLayout BL = bin_layout(D, W, H);
+    const ImgLayout IL = img_layout(W, H);
+    if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
+    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
+    if (image_bytes < IL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, IL.total);
+    const size_t ws_bytes = workspace_layout(D, g->color_channels).total;
+    if (workspace_bytes < ws_bytes) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, ws_bytes);
+    c->G = geom_view(geom, L); c->B = bin_view(binning, BL); c->I = img_view(image, IL);
+    c->ws = workspace_view(workspace, D, g->color_channels);
     c->s = static_cast<hipStream_t>(stream);
-    c->f = make_frame(frame, g);
-    c->f.first = at<uint32_t>(geom, c->L.first); c->f.first_base = at<uint32_t>(geom, c->L.block_base); c->f.sh_jac = at<float>(geom, c->L.sh_jac);
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) c->f.overflow = at<uint32_t>(geom, c->L.block_base) + c->L.n_scan_blocks + 2;   // (frame_counts[2])
-    // per-(tile, Gaussian) gradient records in emission order (a Gaussian's duplicates are contiguous).  K7 writes a record --
-    // and sets the slot's byte in `written` -- only where some pixel contributed; K8 looks at the byte before it touches the
-    // record, so neither the records nor anything but these D bytes need clearing.
-    c->inst_grads = static_cast<float4*>(workspace);
-    c->written = static_cast<uint8_t*>(workspace) + align_up((size_t)(D > 0 ? D : 1) * record_bytes(g->color_channels), 256);
+    set_backward_state(&c->f, frame, c->G);
     return SR_OK;
 }
 }  // namespace
@@ -794,13 +790,10 @@ int sr_backward_blend(const SrFrame* frame, const SrGaussians* g, void* geom, si
     if (!dL_dcolor || !dL_dallmap) return fail(SR_ERR_INVALID_ARGUMENT, "dL_dcolor / dL_dallmap is NULL");
     {
         StageTimer t(SR_STAGE_BLEND_BWD, c.s);
-        if (D > 0) SR_HIP(launch_zero_bytes(c.written, D, c.s));
+        if (D > 0) SR_HIP(launch_zero_bytes(c.ws.written, D, c.s));
         if (D > 0)
-            SR_HIP(launch_render_backward(c.f, at<uint2>(binning, c.B.ranges), at<uint32_t>(binning, c.B.order), at<uint32_t>(binning, c.B.point_list), at<float4>(geom, c.L.recs), g->colors_precomp,
-                                          at<float>(image, c.I.final_T), at<uint32_t>(image, c.I.n_contrib), dL_dcolor, dL_dallmap, at<uint16_t>(binning, c.B.hit_mask), c.inst_grads, c.written,
-                                          !(frame->flags & SR_FLAG_NO_PRECOMP_COLOR_GRAD), c.s,
-                                          (frame->flags & SR_FLAG_ROW_BACKWARD) ? 3
-                                          : ((frame->flags & SR_FLAG_ONE_WAVE_BACKWARD) ? 1 : ((frame->flags & SR_FLAG_COOP_BACKWARD) ? 2 : 0))));
+            SR_HIP(launch_render_backward(c.f, c.B.ranges, c.B.order, c.B.point_list, c.G.recs, g->colors_precomp, c.I.final_T, c.I.n_contrib, dL_dcolor, dL_dallmap,
+                                          c.B.hit_mask, c.ws.records, c.ws.written, !(frame->flags & SR_FLAG_NO_PRECOMP_COLOR_GRAD), c.blend.backward, c.s));
     }
     return debug_sync(frame, c.s, "render_backward");
 }
@@ -815,15 +808,14 @@ int sr_backward_colors(const SrFrame* frame, const SrGaussians* g, const int32_t
     if (!radii || !geom || !workspace || !dL_dcolors) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
     const GeomLayout L = geom_layout(P);
     if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-    if (workspace_bytes < sr_backward_workspace_bytes(P, D, g->color_channels)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace too small");
+    if (workspace_bytes < workspace_layout(D, g->color_channels).total) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace too small");
+    const GeomView G = geom_view(geom, L);
+    const WorkspaceView ws = workspace_view(workspace, D, g->color_channels);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FrameDev f = make_frame(frame, g);
-    f.first = at<uint32_t>(geom, L.first); f.first_base = at<uint32_t>(geom, L.block_base); f.sh_jac = at<float>(geom, L.sh_jac);
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) f.overflow = at<uint32_t>(geom, L.block_base) + L.n_scan_blocks + 2;
-    const uint8_t* written = static_cast<uint8_t*>(workspace) + align_up((size_t)(D > 0 ? D : 1) * record_bytes(g->color_channels), 256);
+    set_backward_state(&f, frame, G);
     StageTimer t(SR_STAGE_PREPROCESS_BWD, s);
-    SR_HIP(launch_color_gradients(P, f, radii, at<uint8_t>(geom, L.clamped), at<float4>(geom, L.recs), static_cast<const float4*>(workspace), written,
-                                  at<uint32_t>(geom, L.tiles_touched), g->shs != nullptr, dL_dcolors, s));
+    SR_HIP(launch_color_gradients(P, f, radii, G.clamped, G.recs, ws.records, ws.written, G.tiles_touched, g->shs != nullptr, dL_dcolors, s));
     return debug_sync(frame, s, "color_gradients");
 }
 
@@ -837,8 +829,7 @@ int sr_backward_geometry(const SrFrame* frame, const SrGaussians* g, const int32
     if (!radii) return fail(SR_ERR_INVALID_ARGUMENT, "radii is NULL");
     {
         StageTimer t(SR_STAGE_PREPROCESS_BWD, c.s);
-        SR_HIP(launch_preprocess_backward(c.P, c.f, *g, radii, at<uint8_t>(geom, c.L.clamped), at<float4>(geom, c.L.recs), c.inst_grads, c.written,
-                                          at<uint32_t>(geom, c.L.tiles_touched), *grads, c.s));
+        SR_HIP(launch_preprocess_backward(c.P, c.f, *g, radii, c.G.clamped, c.G.recs, c.ws.records, c.ws.written, c.G.tiles_touched, *grads, c.s));
     }
     return debug_sync(frame, c.s, "preprocess_backward");
 }
@@ -857,10 +848,11 @@ int sr_debug_pair_decisions(const SrFrame* frame, const SrGaussians* g, void* ge
     if (g->P == 0 || D == 0) return SR_OK;
     if (!geom || !binning || !valid_bits || !use3d_bits) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
     const GeomLayout L = geom_layout(g->P);
-    const BinLayout B = bin_layout(D, frame->image_width, frame->image_height);
-    if (geom_bytes < L.total || binning_bytes < B.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
+    const BinLayout BL = bin_layout(D, frame->image_width, frame->image_height);
+    if (geom_bytes < L.total || binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
+    const BinView B = bin_view(binning, BL);
     const FrameDev f = make_frame(frame, g);
-    SR_HIP(launch_pair_decisions(f, at<uint2>(binning, B.ranges), at<uint32_t>(binning, B.point_list), at<float4>(geom, L.recs),
+    SR_HIP(launch_pair_decisions(f, B.ranges, B.point_list, geom_view(geom, L).recs,
                                  reinterpret_cast<unsigned long long*>(valid_bits), reinterpret_cast<unsigned long long*>(use3d_bits), static_cast<hipStream_t>(stream)));
     return SR_OK;
 }
@@ -889,7 +881,7 @@ int sr_knn_mean_dist2(int32_t n_query, const float* query, int32_t n_reference, 
     if (n_reference == 0) return fail(SR_ERR_INVALID_ARGUMENT, "empty reference cloud");
     if (!reference || !out || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (workspace_bytes < knn_workspace_bytes(nq, n_reference)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, knn_workspace_bytes(nq, n_reference));
-    int sort_mode = kRankUnknown;
+    RankMode sort_mode = kRankUnknown;
     if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &sort_mode)) return rc;
     SR_HIP(knn_mean_dist2(nq, query, n_reference, reference, K, take_sqrt, out, workspace, workspace_bytes, sort_mode, static_cast<hipStream_t>(stream)));
     return SR_OK;
@@ -1016,9 +1008,9 @@ int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t 
 }
 
 int sr_rank_mode(void* stream) {
-    int mode = kRankUnknown;
+    RankMode mode = kRankUnknown;
     if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &mode)) return rc;
-    return mode;
+    return (int)mode;
 }
 
 size_t sr_debug_radix_sort_temp_bytes(uint32_t n) { return radix_sort_temp_bytes(n); }
@@ -1028,10 +1020,10 @@ int sr_debug_radix_sort(const uint32_t* keys_in, const uint32_t* vals_in, uint32
     if (n > 0 && (!keys_in || !keys_out || !vals_out || !temp)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (total_bits < 1 || total_bits > 32) return fail(SR_ERR_INVALID_ARGUMENT, "total_bits %d not in 1..32", total_bits);
     if (temp_bytes < radix_sort_temp_bytes(n)) return fail(SR_ERR_BUFFER_TOO_SMALL, "temp %zu < %zu", temp_bytes, radix_sort_temp_bytes(n));
-    int sort_mode = kRankUnknown;
+    RankMode sort_mode = kRankUnknown;
     if (int rc = rank_mode(static_cast<hipStream_t>(stream), (flags & SR_FLAG_BALLOT_RANKING) != 0, &sort_mode)) return rc;
-    if (flags & SR_FLAG_ONE_SWEEP_SORT) sort_mode |= 0x100;   // (radix_sort.hip kSortOneSweepBit)
-    SR_HIP(radix_sort_pairs(keys_in, vals_in, keys_out, vals_out, n, total_bits, temp, temp_bytes, static_cast<hipStream_t>(stream), nullptr, nullptr, sort_mode));
+    SR_HIP(radix_sort_pairs(keys_in, vals_in, keys_out, vals_out, n, total_bits, temp, temp_bytes, static_cast<hipStream_t>(stream), nullptr, nullptr, sort_mode,
+                            (flags & SR_FLAG_ONE_SWEEP_SORT) != 0));
     return SR_OK;
 }
 

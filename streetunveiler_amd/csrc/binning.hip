@@ -12,17 +12,9 @@
 //      (the "expanding partition" below); pass Y also counts the entries per tile, so the tile ranges are one
 //      exclusive scan of 8 160 counters.
 // Stability of every step makes (tile, depth, id) the final order.  Integer work only.
-#include "common.h"
+#include "launch.h"
 
 namespace sr {
-
-// radix_sort.hip
-size_t radix_sort_temp_bytes(uint32_t n);
-hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t n,
-                            int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, int rank_mode,
-                            int rect_bx = 0, int rect_by = 0, const uint32_t* n_live = nullptr);
-size_t tile_count_scan_temp_bytes(uint32_t n);
-hipError_t tile_count_scan(const uint32_t* counts, uint32_t* out, uint32_t n, void* temp, size_t temp_bytes, uint32_t* total_host, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // K3 + K4: the "expanding partition".  The final list is ordered by (tile row, tile column, depth rank), so an LSD partition runs
@@ -431,14 +423,14 @@ size_t expand_y_hist_bytes(uint32_t D, int tiles_y) { return (size_t)tiles_y * (
 // `n_visible` (device word, the emission scan's count of Gaussians with a tile): the sort compacts -- only the first *n_visible entries of
 // the three outputs are written, the culled Gaussians are dropped by the first pass (radix_sort.hip).
 hipError_t run_depth_sort(int P, const uint32_t* depth_keys, const uint2* rect, uint32_t* sorted_keys,
-                          uint32_t* sorted_gid, uint2* rect_sorted, void* temp, size_t temp_bytes, int rank_mode, int tiles_x, int tiles_y,
-                          const uint32_t* n_visible, hipStream_t s) {
+                          uint32_t* sorted_gid, uint2* rect_sorted, void* temp, size_t temp_bytes, RankMode rank_mode, bool one_sweep, int tiles_x,
+                          int tiles_y, const uint32_t* n_visible, hipStream_t s) {
     if (P == 0) return hipSuccess;
     // the sort also delivers the tile rectangles in depth order, so the scan and the partition read sequentially: packed into a word that
     // rides along with the Gaussian's id where its fields (0 .. tiles_x, 0 .. tiles_y) fit into 32 bits -- up to 255 x 255 tiles, or
     // e.g. 511 x 127 -- and gathered by the last pass for wider frames (radix_sort.hip)
     const int bx = 32 - __builtin_clz((unsigned)(tiles_x > 0 ? tiles_x : 1)), by = 32 - __builtin_clz((unsigned)(tiles_y > 0 ? tiles_y : 1));
-    return radix_sort_pairs(depth_keys, nullptr, sorted_keys, sorted_gid, (uint32_t)P, 32, temp, temp_bytes, s, rect, rect_sorted, rank_mode, bx, by, n_visible);
+    return radix_sort_pairs(depth_keys, nullptr, sorted_keys, sorted_gid, (uint32_t)P, 32, temp, temp_bytes, s, rect, rect_sorted, rank_mode, one_sweep, bx, by, n_visible);
 }
 
 // K2: emission offsets = scan of tiles_touched in id order (block-local values in first, block bases + total D in block_base).
@@ -456,14 +448,14 @@ static void launch_expand_scatter_r(int bins, int blocks, hipStream_t s, Args...
     else hipLaunchKernelGGL((expand_scatter_kernel<AXIS, 10, kAtomicRank>), dim3(blocks), dim3(kXpThreads), 0, s, a...);
 }
 template <int AXIS, typename... Args>
-static void launch_expand_scatter(int rank_mode, int bins, int blocks, hipStream_t s, Args... a) {
+static void launch_expand_scatter(RankMode rank_mode, int bins, int blocks, hipStream_t s, Args... a) {
     if (rank_mode == kRankAtomic) launch_expand_scatter_r<AXIS, true>(bins, blocks, s, a...);
     else launch_expand_scatter_r<AXIS, false>(bins, blocks, s, a...);
 }
 
 // K3: Gaussians in depth order -> column items ordered by (tile column, depth).  Also zeroes tile_counts.  n_columns (device word) receives the number of column items.
 hipError_t run_expand_columns(int P, int tiles_x, int n_tiles, const uint2* rect_sorted, const uint32_t* sorted_gid, uint2* columns,
-                              uint32_t* n_columns, uint32_t* hist, uint32_t* row_total, uint32_t* tile_counts, int rank_mode, const uint32_t* n_visible,
+                              uint32_t* n_columns, uint32_t* hist, uint32_t* row_total, uint32_t* tile_counts, RankMode rank_mode, const uint32_t* n_visible,
                               hipStream_t s) {
     if (P == 0) return hipSuccess;
     if (tiles_x > kXpMaxBins || (rank_mode != kRankAtomic && rank_mode != kRankBallot)) return hipErrorInvalidValue;
@@ -480,7 +472,7 @@ hipError_t run_expand_columns(int P, int tiles_x, int n_tiles, const uint2* rect
 // K4: column items -> point_list ordered by (tile row, tile column, depth) + the entries per tile.  The number of column items is
 // only known on the device; the grid is sized for the upper bound D and surplus blocks leave at once.
 hipError_t run_expand_rows(uint32_t D, int tiles_x, int tiles_y, const uint2* columns, const uint32_t* n_columns, uint32_t* hist, uint32_t* row_total,
-                           uint32_t* point_list, uint32_t* tile_counts, int rank_mode, hipStream_t s) {
+                           uint32_t* point_list, uint32_t* tile_counts, RankMode rank_mode, hipStream_t s) {
     if (D == 0) return hipSuccess;
     if (tiles_y > kXpMaxBins || (rank_mode != kRankAtomic && rank_mode != kRankBallot)) return hipErrorInvalidValue;
     const int nb = (int)((D + kXpInputsY - 1) / kXpInputsY);

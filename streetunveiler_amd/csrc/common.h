@@ -50,7 +50,7 @@ struct FrameDev {
     int tile_w, tile_h;           // pixels per tile: powers of two, multiples of 8 (8x8 quadrant = 1 pixel per lane)
     float inv_tile_w, inv_tile_h; // exact reciprocals
     int sh_degree, sh_coeffs;
-    int colors;   // colour channels blended per pixel: 3, or 6 (precomputed colours only)
+    int colors;   // colour channels blended per pixel: 3, 6 (precomputed colours only) or 9 (SH colour + six precomputed channels)
     int activations;   // SR_ACT_* bits: inputs are the raw (pre-activation) parameters
     float scale_modifier;
     const float* bg;

@@ -13,18 +13,9 @@
 //           B = ds/d(s1), Cm = ds/d(s12), A = ds/d(mu1) - 2 mu1 B - mu2 Cm;  the same separable zero-padded window over three fields.
 //           g is read from device memory.  With the composite: dL/dsky = (1 - alpha) dL/dx,  dL/dalpha = -sum_c sky_c dL/dx_c
 //           (one workgroup walks the channels of its tile, so that sum needs no atomics either).
-#include "common.h"
+#include "launch.h"   // LossImages
 
 namespace sr {
-
-struct LossImages {
-    int W, H, C;
-    float lambda;
-    const float* image;   // [C,H,W]
-    const float* gt;      // [C,H,W]
-    const float* sky;     // [C,H,W] or NULL
-    const float* alpha;   // [1,H,W] or NULL (with sky)
-};
 
 constexpr int kLossTW = 32, kLossTH = 16, kLossR = 5;
 constexpr int kLossSW = kLossTW + 2 * kLossR, kLossSH = kLossTH + 2 * kLossR;   // staged tile with its halo: 42 x 26

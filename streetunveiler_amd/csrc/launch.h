@@ -1,0 +1,137 @@
+// launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
+// they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
+// changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
+// Host-only: nothing in here is a kernel parameter except PostCam and LossImages, which their kernels take by value.
+#pragma once
+#include "common.h"
+
+namespace sr {
+
+// ---- the blend pair of a frame (api.hip choose_blend decides, once per call; the launchers switch on it) -----------------------------
+// The forward kernels of the 16x16 tile with three colour channels (every other shape / channel count has one kernel, plus the counting
+// variant of 16x16 with three or six channels).
+enum class ForwardBlend {
+    kDevicePicked,     // render_forward_auto_kernel: rows or quadrant bands per frame, from the emission scan's counts
+    kQuadrantBands,    // render_forward_kernel<false, 3, 2, 1, 2>
+    kRows,             // render_forward_rows_kernel<2, 1, 2>
+    kRowsCellMasks,    // render_forward_rows_kernel<2, 1, 2, true>: hit masks per 4x4 cell, for BackwardBlend::kRows
+    kCoop,             // render_forward_coop_kernel
+    kCounting,         // render_forward_kernel<true, NCH, 2, 2, 1> (SrFrame.blend_counters)
+};
+enum class BackwardBlend {
+    kByTileCount,      // the cooperative kernel below kCoopBelowTiles tiles, else one wave per tile (render_bwd.hip)
+    kOneWave,          // render_backward_kernel
+    kCoop,             // render_backward_coop_kernel<3>
+    kRows,             // render_backward_rows_kernel: reads CELL-granular hit masks
+};
+enum class HitMaskFormat { kQuadrant, kCell };   // what the forward writes per list entry and the backward of the same frame reads
+struct BlendChoice {
+    ForwardBlend forward;
+    BackwardBlend backward;
+    HitMaskFormat mask;
+    bool cull;   // quadrant culling on (SR_FLAG_NO_QUADRANT_CULL clear)
+};
+
+// ---- preprocess.hip ------------------------------------------------------------------------------------------------------------------
+hipError_t launch_preprocess_forward(int P, const FrameDev& f, const SrGaussians& g, float4* recs, uint32_t* depth_keys,
+                                     uint32_t* tiles_touched, uint2* rect, uint8_t* clamped, int32_t* radii, hipStream_t s);
+hipError_t launch_preprocess_backward(int P, const FrameDev& f, const SrGaussians& g, const int32_t* radii,
+                                      const uint8_t* clamped, const float4* recs, const float4* inst_grads, const uint8_t* written,
+                                      const uint32_t* tiles_touched, const SrGradients& out, hipStream_t s);
+hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
+hipError_t launch_sh_gradient_expand(int P, int M, int deg, int V, const float* means3D, const float* campos, const float* gc,
+                                     float* dL_dsh, hipStream_t s);
+hipError_t launch_color_gradients(int P, const FrameDev& f, const int32_t* radii, const uint8_t* clamped, const float4* recs, const float4* inst_grads,
+                                  const uint8_t* written, const uint32_t* tiles_touched, bool mask_clamped, float* dL_dcolors, hipStream_t s);
+
+// ---- radix_sort.hip ------------------------------------------------------------------------------------------------------------------
+size_t radix_sort_temp_bytes(uint32_t n);
+// `one_sweep`: SR_FLAG_ONE_SWEEP_SORT -- the one-sweep passes where they apply (32-bit keys, from kOneSweepFrom items up)
+hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t n,
+                            int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, RankMode rank_mode,
+                            bool one_sweep, int rect_bx = 0, int rect_by = 0, const uint32_t* n_live = nullptr);
+size_t tile_count_scan_temp_bytes(uint32_t n);
+hipError_t tile_count_scan(const uint32_t* counts, uint32_t* out, uint32_t n, void* temp, size_t temp_bytes, uint32_t* total_host, hipStream_t s);
+hipError_t launch_rank_selfcheck(uint32_t* result, hipStream_t s);
+hipError_t lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, hipStream_t s);
+
+// ---- binning.hip ---------------------------------------------------------------------------------------------------------------------
+size_t depth_sort_temp_bytes(int P);
+size_t tile_scan_temp_bytes(int P);
+size_t expand_x_hist_bytes(int P, int tiles_x);
+size_t expand_y_hist_bytes(uint32_t D, int tiles_y);
+hipError_t run_depth_sort(int P, const uint32_t* depth_keys, const uint2* rect, uint32_t* sorted_keys,
+                          uint32_t* sorted_gid, uint2* rect_sorted, void* temp, size_t temp_bytes, RankMode rank_mode, bool one_sweep, int tiles_x,
+                          int tiles_y, const uint32_t* n_visible, hipStream_t s);
+hipError_t run_tile_count_scan(int P, const uint32_t* tiles_touched, uint32_t* first, void* block_base, size_t base_bytes, uint32_t* total_host,
+                               hipStream_t s);
+hipError_t run_expand_columns(int P, int tiles_x, int n_tiles, const uint2* rect_sorted, const uint32_t* sorted_gid, uint2* columns,
+                              uint32_t* n_columns, uint32_t* hist, uint32_t* row_total, uint32_t* tile_counts, RankMode rank_mode, const uint32_t* n_visible,
+                              hipStream_t s);
+hipError_t run_expand_rows(uint32_t D, int tiles_x, int tiles_y, const uint2* columns, const uint32_t* n_columns, uint32_t* hist, uint32_t* row_total,
+                           uint32_t* point_list, uint32_t* tile_counts, RankMode rank_mode, hipStream_t s);
+hipError_t run_tile_ranges_order(int n_tiles, const uint32_t* tile_counts, uint2* ranges, uint32_t* order, hipStream_t s);
+hipError_t run_capacity_guard(uint32_t* counts, uint32_t capacity, hipStream_t s);
+hipError_t launch_zero_bytes(void* p, size_t n, hipStream_t s);
+
+// ---- render.hip, render_bwd.hip ------------------------------------------------------------------------------------------------------
+hipError_t launch_render_forward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
+                                 const float* extra, float* out_color, float* out_allmap, float* final_T, uint32_t* n_contrib, uint16_t* hit_mask,
+                                 const BlendChoice& blend, unsigned long long* counters, const uint32_t* frame_counts, hipStream_t s);
+hipError_t launch_render_backward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
+                                  const float* extra, const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
+                                  const float* dL_dallmap, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, bool precomp_color_grads,
+                                  BackwardBlend blend, hipStream_t s);
+hipError_t launch_pair_decisions(const FrameDev& f, const uint2* ranges, const uint32_t* point_list, const float4* recs,
+                                 unsigned long long* valid_bits, unsigned long long* use3d_bits, hipStream_t s);
+
+// ---- render_class.hip ----------------------------------------------------------------------------------------------------------------
+hipError_t launch_class_partition(int P, int n_tiles, int n_classes, const float* class_cols, const int32_t* class_i32, const uint2* ranges,
+                                  const uint32_t* point_list, uint8_t* ids, uint32_t* cls_list, uint2* cls_ranges, hipStream_t s);
+hipError_t launch_class_forward(const FrameDev& f, int n_classes, const uint2* cls_ranges, const uint32_t* tile_order, const uint32_t* cls_list,
+                                const float4* recs, float* out_dist, float* cls_state, uint32_t* cls_last, uint32_t* tile_total, uint16_t* hit_mask,
+                                int cull, hipStream_t s);
+// `shared_rec_quads`: 0 = this pass owns the gradient records; else the float4s per record of the colour pass whose records it adds to
+hipError_t launch_class_backward(const FrameDev& f, int n_classes, const uint2* cls_ranges, const uint32_t* tile_order, const uint32_t* cls_list,
+                                 const float4* recs, const float* cls_state, const uint32_t* cls_last, const uint32_t* tile_total,
+                                 const float* dL_ddist, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, int shared_rec_quads, hipStream_t s);
+
+// ---- knn.hip -------------------------------------------------------------------------------------------------------------------------
+size_t knn_workspace_bytes(int nq, int nr);
+hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
+                          size_t ws_bytes, RankMode rank_mode, hipStream_t s);
+
+// ---- postprocess.hip -----------------------------------------------------------------------------------------------------------------
+struct PostCam {
+    int W, H;
+    float fx, fy, depth_ratio;
+    const float* view;   // device [16] world_view_transform (W2C^T, row-major)
+};
+hipError_t launch_postprocess_forward(const PostCam& cam, const float* allmap, float* rend_normal, float* surf_depth,
+                                      float* surf_normal, float* surf_point, hipStream_t s);
+hipError_t launch_postprocess_backward(const PostCam& cam, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
+                                       const float* g_surf_normal, const float* g_surf_point, float* scratch6, float* g_allmap,
+                                       hipStream_t s);
+
+// ---- image_loss.hip ------------------------------------------------------------------------------------------------------------------
+struct LossImages {
+    int W, H, C;
+    float lambda;
+    const float* image;   // [C,H,W]
+    const float* gt;      // [C,H,W]
+    const float* sky;     // [C,H,W] or NULL
+    const float* alpha;   // [1,H,W] or NULL (with sky)
+};
+bool image_loss_supported(int W, int H, int C);
+size_t image_loss_partial_bytes();
+hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s);
+hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
+                                      float* g_alpha, hipStream_t s);
+
+// ---- optimizer.hip -------------------------------------------------------------------------------------------------------------------
+bool adam_supported(const SrAdamSegment* segments, int n_segments);
+hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t s);
+hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
+                                      float* max_radii2D, hipStream_t s);
+
+}  // namespace sr

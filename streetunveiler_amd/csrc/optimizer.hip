@@ -17,7 +17,7 @@
 // search over the (at most 8) first-chunk numbers of the table -- selects over wave-uniform values, no private array, nothing indexed
 // with a run-time value.  A tensor whose four pointers are all 16-B aligned moves as dwordx4 (its n mod 4 tail as scalars); one that is
 // not moves as coalesced scalars.
-#include "common.h"
+#include "launch.h"
 
 namespace sr {
 

@@ -9,15 +9,9 @@
 //   surf_depth  = expected * (1 - depth_ratio) + depth_ratio * median
 //   surf_point  = surf_depth * ray_dir(x, y) + cam_pos,  ray_dir = R_c2w * ((x - W/2)/fx, (y - H/2)/fy, 1)
 //   surf_normal = normalize((P[y+1,x] - P[y-1,x]) x (P[y,x+1] - P[y,x-1])) * alpha      (0 on the border; alpha detached)
-#include "common.h"
+#include "launch.h"   // PostCam
 
 namespace sr {
-
-struct PostCam {
-    int W, H;
-    float fx, fy, depth_ratio;
-    const float* view;   // device [16] world_view_transform (W2C^T, row-major)
-};
 
 // c2w rotation (row-major R[9]) and position from W2C^T: general 3x3 inverse via the adjugate (the reference calls inverse())
 __device__ __forceinline__ void cam_to_world(const float* __restrict__ v, float R[9], float o[3]) {

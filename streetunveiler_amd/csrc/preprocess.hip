@@ -9,7 +9,7 @@
 // [REF /root/reference/gaussian_renderer/__init__.py:56-138]; SH polynomial
 // [REF /root/reference/utils/sh_utils.py:57-112]; quaternion convention
 // [REF /root/reference/utils/general_utils.py:85-98].
-#include "common.h"
+#include "launch.h"
 
 namespace sr {
 

@@ -10,7 +10,7 @@
 // wave owns 512 of them and ranks them 64 at a time with one LDS atomic per item on the (wave, digit) run counter (see the rank
 // phase below).  No atomics on global memory, integer work only, no MFMA.
 #include <cstdlib>
-#include "common.h"
+#include "launch.h"
 
 namespace sr {
 
@@ -75,7 +75,6 @@ __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint32_t* __r
 // on top.  Kept: built, tested bit-exact on every ranking path, and the number to beat for whoever has a cheaper look-back.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kOneSweepFrom = 1u << 18;
-constexpr int kSortOneSweepBit = 0x100;   // in the `rank_mode` argument of radix_sort_pairs
 constexpr uint32_t kSwInclusive = 1u << 28, kSwValue = (1u << 28) - 1u;   // word = tag << 29 | inclusive << 28 | value
 template <int kSortItems>
 __global__ __launch_bounds__(kRsThreads) void rs_hist_all_kernel(const uint32_t* __restrict__ keys, uint32_t n, int drop, uint32_t* __restrict__ ghist) {
@@ -454,11 +453,9 @@ size_t radix_sort_temp_bytes(uint32_t n) {
 // `n_live` != nullptr (device word): a COMPACTING sort -- items whose key is 0xFFFFFFFF are dropped by the first pass, *n_live must be the
 // number of the others, and only keys_out / vals_out / aux_out[0 .. *n_live) are written.
 hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t n,
-                            int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, int rank_mode,
-                            int rect_bx, int rect_by, const uint32_t* n_live) {
+                            int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, RankMode rank_mode,
+                            bool one_sweep, int rect_bx, int rect_by, const uint32_t* n_live) {
     if (n == 0) return hipSuccess;
-    const bool sweep_wanted = (rank_mode & kSortOneSweepBit) != 0;   // (rides in the ranking argument: SR_FLAG_ONE_SWEEP_SORT)
-    rank_mode &= ~kSortOneSweepBit;
     if (temp_bytes < radix_sort_temp_bytes(n) || (rank_mode != kRankAtomic && rank_mode != kRankBallot)) return hipErrorInvalidValue;
     int passes = (total_bits + 7) / 8;
     if (passes < 1) passes = 1;
@@ -476,7 +473,7 @@ hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, ui
     uint32_t* tickets = ghist + 4 * kRsMaxBins;        // [4] block counters, one per pass
     const uint32_t* ki = keys_in; const uint32_t* vi = vals_in;
     int shift = 0, left = total_bits;
-    const bool sweep = sweep_wanted && total_bits == 32 && passes == 4 && n >= kOneSweepFrom && n <= kSwValue;
+    const bool sweep = one_sweep && total_bits == 32 && passes == 4 && n >= kOneSweepFrom && n <= kSwValue;
     if (sweep) {
         // status table (in the histogram table's place: the same [blocks][256] words), row totals, digit totals, tickets: zeroed once per sort
         const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(tickets + 16) - reinterpret_cast<char*>(hist));

@@ -30,6 +30,7 @@
 // Behavioural contract: SURVEY.md Appendix A.4 / A.5; output channel order
 // [REF /root/reference/gaussian_renderer/__init__.py:149-165].
 #include "blend_common.h"
+#include "launch.h"
 
 #ifndef SR_K6_COLOURS_UP_FRONT
 #define SR_K6_COLOURS_UP_FRONT 1
@@ -662,18 +663,18 @@ __global__ __launch_bounds__(kWave) void pair_decisions_kernel(FrameDev f, const
 // launchers ---------------------------------------------------------------------------------------
 // Tile shapes: SR_FOR_TILE_SHAPE (blend_common.h).  Every shape carries the 6- / 9-channel passes; only the reference shape the counter variant.
 
-// (bit 5 of `flags`: the cooperative forward -- measured and NOT picked by itself: see render_forward_coop_kernel;
-//  bit 6: the row-mapped kernel writing CELL-granular hit masks -- what render_backward_rows_kernel reads; 16x16, three channels, culling on)
-// flags: bit 0 = quadrant culling on (SR_FLAG_NO_QUADRANT_CULL clear), bit 1 = counter variant (counters != NULL), bit 2 / bit 3 = the row-mapped /
-// the quadrant-mapped kernel forced (else, for the 16x16 tile with three channels and culling on, the device picks per frame: frame_counts)
+// `blend` (launch.h; api.hip choose_blend): the kernel of the 16x16 tile with three colour channels -- every other shape / channel count has
+// one kernel, plus the counting variant (ForwardBlend::kCounting, counters != NULL) of 16x16 with six channels -- and whether quadrant culling
+// is on.  (The cooperative forward is measured and NOT picked by itself: see render_forward_coop_kernel.  kRowsCellMasks writes the
+// CELL-granular hit masks render_backward_rows_kernel reads.  kDevicePicked chooses per frame from frame_counts = [D, visible].)
 hipError_t launch_render_forward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
-                                 const float* extra, float* out_color, float* out_allmap, float* final_T, uint32_t* n_contrib,
-                                 uint16_t* hit_mask, int flags, unsigned long long* counters, const uint32_t* frame_counts, hipStream_t s) {
+                                 const float* extra, float* out_color, float* out_allmap, float* final_T, uint32_t* n_contrib, uint16_t* hit_mask,
+                                 const BlendChoice& blend, unsigned long long* counters, const uint32_t* frame_counts, hipStream_t s) {
     const int n_tiles = f.tiles_x * f.tiles_y;
     if (n_tiles == 0) return hipSuccess;
-    const dim3 block(kWave);
-    const int cull = flags & 1;
-    const bool count = (flags & 2) != 0 && counters != nullptr;
+    const dim3 block(kWave), band_grid((n_tiles + kXcds - 1) / kXcds * kXcds * 2);   // (two 16x8 band waves per tile)
+    const int cull = blend.cull ? 1 : 0;
+    const bool count = blend.forward == ForwardBlend::kCounting && counters != nullptr;
 #define SR_LAUNCH_FWD(STATS, NCH, QX, QY, SPLIT)                                                                                  \
     hipLaunchKernelGGL((render_forward_kernel<STATS, NCH, QX, QY, SPLIT>),                                                          \
                        dim3(SPLIT > 1 ? (n_tiles + kXcds - 1) / kXcds * kXcds * SPLIT : n_tiles), block, 0, s, f, \
@@ -682,18 +683,32 @@ hipError_t launch_render_forward(const FrameDev& f, const uint2* ranges, const u
         // the reference's tile: two 16x8 band waves per tile (the counter variant stays whole so that it counts each entry once)
         if (f.colors == 9) { SR_LAUNCH_FWD(false, 9, 2, 1, 2); }
         else if (f.colors == 6) { if (count) SR_LAUNCH_FWD(true, 6, 2, 2, 1); else SR_LAUNCH_FWD(false, 6, 2, 1, 2); }
-        else if (count)         SR_LAUNCH_FWD(true, 3, 2, 2, 1);
-        else if (cull && !(flags & (4 | 8)) && (flags & 32))   // (explicitly asked for: SR_FLAG_COOP_BACKWARD in sr_forward_render)
-                                hipLaunchKernelGGL(render_forward_coop_kernel, dim3(n_tiles), dim3(4 * kWave), 0, s, f, ranges, tile_order, point_list, recs, out_color,
-                                                   out_allmap, final_T, n_contrib, hit_mask);
-        else if (flags & 64)    hipLaunchKernelGGL((render_forward_rows_kernel<2, 1, 2, true>), dim3((n_tiles + kXcds - 1) / kXcds * kXcds * 2), block, 0, s, f, ranges,
-                                                   tile_order, point_list, recs, out_color, out_allmap, final_T, n_contrib, hit_mask);   // (cell-granular hit masks)
-        else if (flags & 4)     hipLaunchKernelGGL((render_forward_rows_kernel<2, 1, 2>), dim3((n_tiles + kXcds - 1) / kXcds * kXcds * 2), block, 0, s, f, ranges,
-                                                   tile_order, point_list, recs, out_color, out_allmap, final_T, n_contrib, hit_mask);
-        else if (cull && !(flags & 8) && frame_counts)
-                                hipLaunchKernelGGL(render_forward_auto_kernel, dim3((n_tiles + kXcds - 1) / kXcds * kXcds * 2), block, 0, s, f, ranges,
-                                                   tile_order, point_list, recs, out_color, out_allmap, final_T, n_contrib, hit_mask, frame_counts);
-        else                    SR_LAUNCH_FWD(false, 3, 2, 1, 2);
+        else switch (blend.forward) {
+            case ForwardBlend::kCounting:
+                if (!counters) return hipErrorInvalidValue;
+                SR_LAUNCH_FWD(true, 3, 2, 2, 1);
+                break;
+            case ForwardBlend::kCoop:   // (explicitly asked for: SR_FLAG_COOP_BACKWARD in sr_forward_render)
+                hipLaunchKernelGGL(render_forward_coop_kernel, dim3(n_tiles), dim3(4 * kWave), 0, s, f, ranges, tile_order, point_list, recs, out_color,
+                                   out_allmap, final_T, n_contrib, hit_mask);
+                break;
+            case ForwardBlend::kRowsCellMasks:
+                hipLaunchKernelGGL((render_forward_rows_kernel<2, 1, 2, true>), band_grid, block, 0, s, f, ranges, tile_order, point_list, recs, out_color,
+                                   out_allmap, final_T, n_contrib, hit_mask);
+                break;
+            case ForwardBlend::kRows:
+                hipLaunchKernelGGL((render_forward_rows_kernel<2, 1, 2>), band_grid, block, 0, s, f, ranges, tile_order, point_list, recs, out_color,
+                                   out_allmap, final_T, n_contrib, hit_mask);
+                break;
+            case ForwardBlend::kDevicePicked:
+                if (!frame_counts) return hipErrorInvalidValue;
+                hipLaunchKernelGGL(render_forward_auto_kernel, band_grid, block, 0, s, f, ranges, tile_order, point_list, recs, out_color, out_allmap,
+                                   final_T, n_contrib, hit_mask, frame_counts);
+                break;
+            case ForwardBlend::kQuadrantBands:
+                SR_LAUNCH_FWD(false, 3, 2, 1, 2);
+                break;
+        }
     } else if (f.colors != 3 && f.tile_w == 32 && f.tile_h == 16) {
         // 32x16 with 6 / 9 channels: two 32x8 band waves per tile, like the 3-channel pass (K7 walks the list once per band there: render_bwd.hip)
         if (f.colors == 9) { SR_LAUNCH_FWD(false, 9, 4, 1, 2); } else { SR_LAUNCH_FWD(false, 6, 4, 1, 2); }

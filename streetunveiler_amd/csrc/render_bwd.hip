@@ -2,6 +2,7 @@
 // A translation unit of its own: it is compiled with the max-ILP machine scheduler (build.py), which interleaves the independent
 // chains of a quadrant block better (K7 1.688 -> 1.670 ms) but costs the forward kernel a spill at its 80-register budget.
 #include "blend_common.h"
+#include "launch.h"
 
 #ifndef SR_K7_NINE_BANDED
 #define SR_K7_NINE_BANDED 0
@@ -403,31 +404,30 @@ void render_backward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, c
     if (pend) flush_record<kGQ, true>(&s_out[lane][0], inst_grads, written, pslot, 0.f, 0.f, false);
 }
 
-// coop_mode: 0 = by tile count (the cooperative kernel below kCoopBelowTiles tiles of 16x16 with three colour channels), 1 = never, 2 = always (A/B, tests),
-// 3 = the row-mapped kernel: the forward must have written CELL-granular hit masks (launch_render_forward flags bit 6)
+// BackwardBlend::kByTileCount (16x16 tile, three colour channels, no flag of the caller's: api.hip choose_blend): the cooperative kernel --
+// four quadrant waves per tile instead of one wave -- below kCoopBelowTiles tiles (the reference's `-r 4` frames), one wave per tile from there.
 constexpr int kCoopBelowTiles = 2600;
-static inline bool coop_few_tiles(const FrameDev& f, int coop_mode) {
-    if (!(f.tile_w == 16 && f.tile_h == 16 && f.colors == 3) || coop_mode == 1) return false;
-    return coop_mode == 2 || f.tiles_x * f.tiles_y < kCoopBelowTiles;
-}
 
-// flags: bit 0 = quadrant culling on (SR_FLAG_NO_QUADRANT_CULL clear), bit 1 = counter variant (counters != NULL), bit 2 = row-mapped kernel
+// `blend` (launch.h): kCoop and kRows exist for the 16x16 tile with three colour channels only; kRows needs the CELL-granular hit masks of
+// ForwardBlend::kRowsCellMasks.  Every other shape / channel count takes kOneWave.
 hipError_t launch_render_backward(const FrameDev& f, const uint2* ranges, const uint32_t* tile_order, const uint32_t* point_list, const float4* recs,
                                   const float* extra, const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                  const float* dL_dallmap, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, bool precomp_color_grads, hipStream_t s,
-                                  int coop_mode) {
+                                  const float* dL_dallmap, const uint16_t* hit_mask, float4* inst_grads, uint8_t* written, bool precomp_color_grads,
+                                  BackwardBlend blend, hipStream_t s) {
     const int n_tiles = f.tiles_x * f.tiles_y;
     if (n_tiles == 0) return hipSuccess;
-    if (coop_mode == 3) {
-        if (!(f.tile_w == 16 && f.tile_h == 16 && f.colors == 3)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(render_backward_rows_kernel, dim3(n_tiles), dim3(kWave), 0, s, f, ranges, tile_order, point_list, recs, final_T, n_contrib,
-                           dL_dcolor, dL_dallmap, hit_mask, inst_grads, written);
-        return hipGetLastError();
-    }
-    if (coop_few_tiles(f, coop_mode)) {   // few tiles (the reference's `-r 4` frames): four quadrant waves per tile instead of one wave
-        hipLaunchKernelGGL((render_backward_coop_kernel<3>), dim3(n_tiles), dim3(4 * kWave), 0, s, f, ranges, tile_order, point_list, recs, final_T, n_contrib,
-                           dL_dcolor, dL_dallmap, hit_mask, inst_grads, written);
-        return hipGetLastError();
+    if (blend != BackwardBlend::kOneWave && !(f.tile_w == 16 && f.tile_h == 16 && f.colors == 3)) return hipErrorInvalidValue;
+    if (blend == BackwardBlend::kByTileCount) blend = n_tiles < kCoopBelowTiles ? BackwardBlend::kCoop : BackwardBlend::kOneWave;
+    switch (blend) {
+        case BackwardBlend::kRows:
+            hipLaunchKernelGGL(render_backward_rows_kernel, dim3(n_tiles), dim3(kWave), 0, s, f, ranges, tile_order, point_list, recs, final_T, n_contrib,
+                               dL_dcolor, dL_dallmap, hit_mask, inst_grads, written);
+            return hipGetLastError();
+        case BackwardBlend::kCoop:
+            hipLaunchKernelGGL((render_backward_coop_kernel<3>), dim3(n_tiles), dim3(4 * kWave), 0, s, f, ranges, tile_order, point_list, recs, final_T, n_contrib,
+                               dL_dcolor, dL_dallmap, hit_mask, inst_grads, written);
+            return hipGetLastError();
+        default: break;   // kOneWave: by tile shape and channel count, below
     }
     if (!precomp_color_grads && f.tile_w == 16 && f.tile_h == 16 && f.colors != 3) {   // (the reference tile only: elsewhere the sums are formed and nobody reads them)
 #define SR_LAUNCH_BWD_NOXG(NCH) hipLaunchKernelGGL((render_backward_kernel<NCH, 2, 2, 1, false>), dim3(n_tiles), dim3(kWave), 0, s, f, ranges, tile_order, point_list, recs, extra, \

@@ -12,10 +12,9 @@
 // 67 M staged entries for 8.6 M useful ones, 9.3 GiB fetched per backward launch, a third of the forward's issue slots scalar --
 // profiles/r05_train_step_*)
 #include "blend_common.h"
+#include "launch.h"
 
 namespace sr {
-
-hipError_t launch_zero_bytes(void* p, size_t n, hipStream_t s);   // binning.hip
 
 constexpr int kClassMax = 8;
 constexpr uint8_t kNoClass = 255;

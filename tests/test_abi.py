@@ -59,6 +59,180 @@ def test_argument_errors_without_gpu(lib):
     assert rc == -1 and b"image size" in lib.sr_last_error()
 
 
+# ---- layout identity -------------------------------------------------------------------------------------------------------------------
+# Recorded from the library of commit 6eaaa90 (before the layouts moved behind typed views), not computed here: the sizes the six *_bytes
+# functions report and the offsets the three *_view functions report into one host buffer.  A buffer sized by one build of the library and
+# carved by another, or a saved training state, depends on none of them moving.
+GEOM_BYTES = {
+    0: 9984, 1: 9984, 2047: 344576, 2048: 344576, 2049: 348928, 100000: 16557312}
+BINNING_BYTES = {   # (D, W, H); P does not enter
+    (0, 1, 1): 6144, (0, 203, 125): 12288, (0, 1920, 1080): 524800,
+    (1, 1, 1): 6144, (1, 203, 125): 12288, (1, 1920, 1080): 524800,
+    (5000, 1, 1): 76032, (5000, 203, 125): 82176, (5000, 1920, 1080): 595712}
+IMAGE_BYTES = {
+    (1, 1): 512, (203, 125): 507648, (1920, 1080): 41472000}
+CLASS_IMAGE_BYTES = {   # (W, H, n_classes)
+    (1, 1, 1): 1024, (1, 1, 6): 1024, (203, 125, 1): 411392,
+    (203, 125, 6): 2466048, (1920, 1080, 1): 33566720, (1920, 1080, 6): 201398528}
+CLASS_SHARED_BYTES = {   # (P, W, H, n_classes, D)
+    (0, 1, 1, 1, 0): 1536, (0, 1, 1, 1, 1): 1536, (0, 1, 1, 1, 5000): 11520,
+    (0, 1, 1, 6, 0): 1536, (0, 1, 1, 6, 1): 1536, (0, 1, 1, 6, 5000): 11520,
+    (0, 203, 125, 1, 0): 411904, (0, 203, 125, 1, 1): 411904, (0, 203, 125, 1, 5000): 421888,
+    (0, 203, 125, 6, 0): 2466560, (0, 203, 125, 6, 1): 2466560, (0, 203, 125, 6, 5000): 2476544,
+    (0, 1920, 1080, 1, 0): 33567232, (0, 1920, 1080, 1, 1): 33567232, (0, 1920, 1080, 1, 5000): 33577216,
+    (0, 1920, 1080, 6, 0): 201399040, (0, 1920, 1080, 6, 1): 201399040, (0, 1920, 1080, 6, 5000): 201409024,
+    (1, 1, 1, 1, 0): 1536, (1, 1, 1, 1, 1): 1536, (1, 1, 1, 1, 5000): 11520,
+    (1, 1, 1, 6, 0): 1536, (1, 1, 1, 6, 1): 1536, (1, 1, 1, 6, 5000): 11520,
+    (1, 203, 125, 1, 0): 411904, (1, 203, 125, 1, 1): 411904, (1, 203, 125, 1, 5000): 421888,
+    (1, 203, 125, 6, 0): 2466560, (1, 203, 125, 6, 1): 2466560, (1, 203, 125, 6, 5000): 2476544,
+    (1, 1920, 1080, 1, 0): 33567232, (1, 1920, 1080, 1, 1): 33567232, (1, 1920, 1080, 1, 5000): 33577216,
+    (1, 1920, 1080, 6, 0): 201399040, (1, 1920, 1080, 6, 1): 201399040, (1, 1920, 1080, 6, 5000): 201409024,
+    (2047, 1, 1, 1, 0): 3328, (2047, 1, 1, 1, 1): 3328, (2047, 1, 1, 1, 5000): 13312,
+    (2047, 1, 1, 6, 0): 3328, (2047, 1, 1, 6, 1): 3328, (2047, 1, 1, 6, 5000): 13312,
+    (2047, 203, 125, 1, 0): 413696, (2047, 203, 125, 1, 1): 413696, (2047, 203, 125, 1, 5000): 423680,
+    (2047, 203, 125, 6, 0): 2468352, (2047, 203, 125, 6, 1): 2468352, (2047, 203, 125, 6, 5000): 2478336,
+    (2047, 1920, 1080, 1, 0): 33569024, (2047, 1920, 1080, 1, 1): 33569024, (2047, 1920, 1080, 1, 5000): 33579008,
+    (2047, 1920, 1080, 6, 0): 201400832, (2047, 1920, 1080, 6, 1): 201400832, (2047, 1920, 1080, 6, 5000): 201410816,
+    (2048, 1, 1, 1, 0): 3328, (2048, 1, 1, 1, 1): 3328, (2048, 1, 1, 1, 5000): 13312,
+    (2048, 1, 1, 6, 0): 3328, (2048, 1, 1, 6, 1): 3328, (2048, 1, 1, 6, 5000): 13312,
+    (2048, 203, 125, 1, 0): 413696, (2048, 203, 125, 1, 1): 413696, (2048, 203, 125, 1, 5000): 423680,
+    (2048, 203, 125, 6, 0): 2468352, (2048, 203, 125, 6, 1): 2468352, (2048, 203, 125, 6, 5000): 2478336,
+    (2048, 1920, 1080, 1, 0): 33569024, (2048, 1920, 1080, 1, 1): 33569024, (2048, 1920, 1080, 1, 5000): 33579008,
+    (2048, 1920, 1080, 6, 0): 201400832, (2048, 1920, 1080, 6, 1): 201400832, (2048, 1920, 1080, 6, 5000): 201410816,
+    (2049, 1, 1, 1, 0): 3584, (2049, 1, 1, 1, 1): 3584, (2049, 1, 1, 1, 5000): 13568,
+    (2049, 1, 1, 6, 0): 3584, (2049, 1, 1, 6, 1): 3584, (2049, 1, 1, 6, 5000): 13568,
+    (2049, 203, 125, 1, 0): 413952, (2049, 203, 125, 1, 1): 413952, (2049, 203, 125, 1, 5000): 423936,
+    (2049, 203, 125, 6, 0): 2468608, (2049, 203, 125, 6, 1): 2468608, (2049, 203, 125, 6, 5000): 2478592,
+    (2049, 1920, 1080, 1, 0): 33569280, (2049, 1920, 1080, 1, 1): 33569280, (2049, 1920, 1080, 1, 5000): 33579264,
+    (2049, 1920, 1080, 6, 0): 201401088, (2049, 1920, 1080, 6, 1): 201401088, (2049, 1920, 1080, 6, 5000): 201411072,
+    (100000, 1, 1, 1, 0): 101376, (100000, 1, 1, 1, 1): 101376, (100000, 1, 1, 1, 5000): 111360,
+    (100000, 1, 1, 6, 0): 101376, (100000, 1, 1, 6, 1): 101376, (100000, 1, 1, 6, 5000): 111360,
+    (100000, 203, 125, 1, 0): 511744, (100000, 203, 125, 1, 1): 511744, (100000, 203, 125, 1, 5000): 521728,
+    (100000, 203, 125, 6, 0): 2566400, (100000, 203, 125, 6, 1): 2566400, (100000, 203, 125, 6, 5000): 2576384,
+    (100000, 1920, 1080, 1, 0): 33667072, (100000, 1920, 1080, 1, 1): 33667072, (100000, 1920, 1080, 1, 5000): 33677056,
+    (100000, 1920, 1080, 6, 0): 201498880, (100000, 1920, 1080, 6, 1): 201498880, (100000, 1920, 1080, 6, 5000): 201508864}
+WORKSPACE_BYTES = {   # (D, colour channels); P does not enter
+    (0, 3): 512, (0, 6): 512, (0, 9): 512,
+    (1, 3): 512, (1, 6): 512, (1, 9): 512,
+    (5000, 3): 485120, (5000, 6): 485120, (5000, 9): 565248}
+GEOM_VIEW = {   # P: offsets of (splats, depth_keys, tiles_touched, clamped, sorted_gid, frame_counts)
+    0: (0, 256, 512, 1024, 1536, 2564), 1: (0, 256, 512, 1024, 1536, 2564),
+    2047: (0, 163840, 172032, 196608, 206848, 313348), 2048: (0, 163840, 172032, 196608, 206848, 313348),
+    2049: (0, 164096, 172544, 197632, 208384, 315912), 100000: (0, 8000000, 8400128, 9600256, 10100480, 15301060)}
+BINNING_VIEW = {   # (D, W, H): offsets of (point_list, ranges, tile_order)
+    (0, 1, 1): (256, 768, 1024), (0, 203, 125): (256, 768, 4096), (0, 1920, 1080): (256, 768, 260096),
+    (1, 1, 1): (256, 768, 1024), (1, 203, 125): (256, 768, 4096), (1, 1920, 1080): (256, 768, 260096),
+    (5000, 1, 1): (40192, 70656, 70912), (5000, 203, 125): (40192, 70656, 73984), (5000, 1920, 1080): (40192, 70656, 329984)}
+IMAGE_VIEW = {   # (W, H): offsets of (final_T, n_contrib)
+    (1, 1): (0, 256), (203, 125): (0, 304640), (1920, 1080): (0, 24883200)}
+LAYOUT_P = [0, 1, 2047, 2048, 2049, 100000]
+LAYOUT_D = [0, 1, 5000]
+LAYOUT_WH = [(1, 1), (203, 125), (1920, 1080)]
+LAYOUT_CLASSES = [1, 6]
+LAYOUT_CHANNELS = [3, 6, 9]
+
+
+def test_state_buffer_sizes_are_the_recorded_ones(lib):
+    assert sorted(GEOM_BYTES) == LAYOUT_P and len(CLASS_SHARED_BYTES) == 6 * 3 * 2 * 3
+    for P in LAYOUT_P:
+        assert lib.sr_geom_bytes(P) == GEOM_BYTES[P], P
+        for D in LAYOUT_D:
+            for W, H in LAYOUT_WH:
+                assert lib.sr_binning_bytes(P, D, W, H) == BINNING_BYTES[(D, W, H)], (P, D, W, H)
+                for n in LAYOUT_CLASSES:
+                    assert lib.sr_class_shared_bytes(P, W, H, n, D) == CLASS_SHARED_BYTES[(P, W, H, n, D)], (P, W, H, n, D)
+            for NC in LAYOUT_CHANNELS:
+                assert lib.sr_backward_workspace_bytes(P, D, NC) == WORKSPACE_BYTES[(D, NC)], (P, D, NC)
+    for W, H in LAYOUT_WH:
+        assert lib.sr_image_bytes(W, H) == IMAGE_BYTES[(W, H)], (W, H)
+        for n in LAYOUT_CLASSES:
+            assert lib.sr_class_image_bytes(W, H, n) == CLASS_IMAGE_BYTES[(W, H, n)], (W, H, n)
+
+
+def _view_offsets(view, base):
+    return tuple(getattr(view, name) - base for name, _ in view._fields_)
+
+
+def test_state_buffer_views_point_where_they_did(lib):
+    for P in LAYOUT_P:
+        n = lib.sr_geom_bytes(P)
+        buf, view = ctypes.create_string_buffer(n), _lib.SrGeomView()
+        assert lib.sr_geom_view(ctypes.addressof(buf), n, P, ctypes.byref(view)) == 0
+        assert _view_offsets(view, ctypes.addressof(buf)) == GEOM_VIEW[P], P
+        assert lib.sr_geom_view(ctypes.addressof(buf), n - 1, P, ctypes.byref(view)) == -3   # SR_ERR_BUFFER_TOO_SMALL
+    for D in LAYOUT_D:
+        for W, H in LAYOUT_WH:
+            n = lib.sr_binning_bytes(2048, D, W, H)
+            buf, view = ctypes.create_string_buffer(n), _lib.SrBinningView()
+            assert lib.sr_binning_view(ctypes.addressof(buf), n, 2048, D, W, H, ctypes.byref(view)) == 0
+            assert _view_offsets(view, ctypes.addressof(buf)) == BINNING_VIEW[(D, W, H)], (D, W, H)
+    for W, H in LAYOUT_WH:
+        n = lib.sr_image_bytes(W, H)
+        buf, view = ctypes.create_string_buffer(n), _lib.SrImageView()
+        assert lib.sr_image_view(ctypes.addressof(buf), n, W, H, ctypes.byref(view)) == 0
+        assert _view_offsets(view, ctypes.addressof(buf)) == IMAGE_VIEW[(W, H)], (W, H)
+
+
+# ---- refusal table ---------------------------------------------------------------------------------------------------------------------
+INVALID, UNSUPPORTED = -1, -4   # SR_ERR_INVALID_ARGUMENT, SR_ERR_UNSUPPORTED
+ONE_WAVE, COOP, ROWS = _lib.SR_FLAG_ONE_WAVE_BACKWARD, _lib.SR_FLAG_COOP_BACKWARD, _lib.SR_FLAG_ROW_BACKWARD
+# (flags, tile, colour channels, blend_counters set) -> (code, fragment of sr_last_error()); tile None = the default 16x16
+PAIR_CONFLICTS = [((a, None, 3, False), (INVALID, "exclude each other")) for a in (ONE_WAVE | COOP, ONE_WAVE | ROWS, COOP | ROWS, ONE_WAVE | COOP | ROWS)]
+ROW_PAIR_SHAPE = [((ROWS, (8, 8), 3, False), (UNSUPPORTED, "SR_FLAG_ROW_BACKWARD")),
+                  ((ROWS, None, 6, False), (UNSUPPORTED, "SR_FLAG_ROW_BACKWARD")),
+                  ((ROWS | _lib.SR_FLAG_NO_QUADRANT_CULL, None, 3, False), (UNSUPPORTED, "SR_FLAG_ROW_BACKWARD"))]
+FORWARD_ONLY_REFUSALS = [((ROWS | _lib.SR_FLAG_QUADRANT_MAPPED_FORWARD, None, 3, False), (UNSUPPORTED, "SR_FLAG_ROW_BACKWARD")),
+                         ((ROWS | _lib.SR_FLAG_FORWARD_ONLY, None, 3, False), (UNSUPPORTED, "SR_FLAG_ROW_BACKWARD")),
+                         ((_lib.SR_FLAG_ROW_MAPPED_FORWARD | _lib.SR_FLAG_QUADRANT_MAPPED_FORWARD, None, 3, False), (INVALID, "exclude each other")),
+                         ((_lib.SR_FLAG_ROW_MAPPED_FORWARD, (32, 16), 3, False), (UNSUPPORTED, "ROW_MAPPED")),
+                         ((0, (16, 8), 3, True), (UNSUPPORTED, "blend_counters")),
+                         ((_lib.SR_FLAG_FORWARD_ONLY, None, 3, True), (UNSUPPORTED, "blend_counters"))]
+
+
+def test_refused_flag_combinations_without_gpu(lib):
+    """Every combination of blend-pair flags, mapping flags, tile shape, channel count and counters that the library refuses, and the class
+    passes' n_classes / SR_FLAG_BINNING_CAPACITY refusals: the code and the message fragment of commit 6eaaa90.  Only refused calls are made, on
+    dummy host pointers -- a refusal comes before the first HIP call of its entry point, or this test could not run without a GPU."""
+    dummy = ctypes.create_string_buffer(64)
+    p, big, D = ctypes.addressof(dummy), 1 << 40, 10
+
+    def frame(flags, tile=None, counters=False):
+        tw, th = tile or (0, 0)
+        return _lib.SrFrame(64, 96, 1.0, 1.0, 1.0, 0, 0, 0, p, p, p, p, tw, th, flags, p if counters else None)
+
+    def gaussians(channels=3):   # precomputed colours: every channel count, and what the stand-alone class pass takes
+        return _lib.SrGaussians(100, 0, channels, 0, p, p, p, p, None, p, None, None)
+
+    grads = _lib.SrGradients(p, p, p, p, p, p, p, p)
+
+    def check(rc, want, what):
+        code, fragment = want
+        assert rc == code and fragment.encode() in lib.sr_last_error(), (what, rc, lib.sr_last_error())
+
+    for (flags, tile, channels, counters), want in PAIR_CONFLICTS + ROW_PAIR_SHAPE + FORWARD_ONLY_REFUSALS:
+        fr, g = frame(flags, tile, counters), gaussians(channels)
+        check(lib.sr_forward_render(ctypes.byref(fr), ctypes.byref(g), p, big, p, big, p, big, D, p, p, None), want, ("forward", flags, tile, channels, counters))
+    for (flags, tile, channels, counters), want in PAIR_CONFLICTS + ROW_PAIR_SHAPE:   # (a backward call does not read the forward-only flags)
+        fr, g = frame(flags, tile, counters), gaussians(channels)
+        check(lib.sr_backward_blend(ctypes.byref(fr), ctypes.byref(g), p, big, p, big, p, big, D, p, p, p, big, None), want, ("backward_blend", flags, tile, channels))
+        check(lib.sr_backward_geometry(ctypes.byref(fr), ctypes.byref(g), p, p, big, p, big, p, big, D, p, big, ctypes.byref(grads), None), want,
+              ("backward_geometry", flags, tile, channels))
+
+    def class_calls(fr, g, n):
+        return [("class_forward_render", lib.sr_class_forward_render, (ctypes.byref(fr), ctypes.byref(g), n, p, big, p, big, p, big, D, p, None)),
+                ("class_backward", lib.sr_class_backward, (ctypes.byref(fr), ctypes.byref(g), n, p, p, big, p, big, p, big, D, p, p, big, ctypes.byref(grads), None)),
+                ("class_forward_shared", lib.sr_class_forward_shared, (ctypes.byref(fr), ctypes.byref(g), n, p, p, big, p, big, p, big, D, p, None)),
+                ("class_backward_shared", lib.sr_class_backward_shared, (ctypes.byref(fr), ctypes.byref(g), n, p, big, p, big, p, big, D, p, p, big, None))]
+
+    fr, g = frame(0), gaussians(3)
+    for n in (0, 7):
+        for name, fn, args in class_calls(fr, g, n):
+            check(fn(*args), (UNSUPPORTED, "n_classes"), (name, n))
+    fr = frame(_lib.SR_FLAG_BINNING_CAPACITY)
+    for name, fn, args in class_calls(fr, g, 3):
+        check(fn(*args), (UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY"), (name, "capacity"))
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import torch
     from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
