@@ -4,16 +4,20 @@
 // reference runs as ~25 full-image torch kernels (plus a 25 MB host->device upload of the pixel grid per call).
 // One streaming pass forward, two backward; pure HBM-bound elementwise/stencil work (~60 B/pixel in, ~40 B/pixel out).
 //
-//   rend_normal = R_c2w * allmap[2:5]
+//   rend_normal = V3^T * allmap[2:5],  V3 = the world-to-view 3x3 itself (the reference multiplies by its transpose, it does not invert it)
 //   expected    = nan_to_num(allmap[0] / allmap[1], 0, 0);  median = nan_to_num(allmap[5], 0, 0)
 //   surf_depth  = expected * (1 - depth_ratio) + depth_ratio * median
-//   surf_point  = surf_depth * ray_dir(x, y) + cam_pos,  ray_dir = R_c2w * ((x - W/2)/fx, (y - H/2)/fy, 1)
+//   surf_point  = surf_depth * ray_dir(x, y) + cam_pos,  ray_dir = R_c2w * ((x - W/2)/fx, (y - H/2)/fy, 1),  R_c2w = inverse(V3)
 //   surf_normal = normalize((P[y+1,x] - P[y-1,x]) x (P[y,x+1] - P[y,x-1])) * alpha      (0 on the border; alpha detached)
+// On a rigid camera V3^T and inverse(V3) agree to an ulp; on a scaled 3x3 they differ by the scale squared, and only the rays and the
+// camera position take the inverse.  NaN and +inf depths become 0 (with a zero gradient); -inf is not handled like torch.nan_to_num(x, 0, 0)
+// handles it (that maps it to the lowest finite float, this maps it to 0): depths are never negative, so it never occurs.
 #include "launch.h"   // PostCam
 
 namespace sr {
 
-// c2w rotation (row-major R[9]) and position from W2C^T: general 3x3 inverse via the adjugate (the reference calls inverse())
+// c2w rotation (row-major R[9]) and position from W2C^T: general 3x3 inverse via the adjugate (the reference calls inverse()); for the ray
+// directions and the camera position only -- the normals go through the view matrix itself (rotate_normal / rotate_normal_adjoint)
 __device__ __forceinline__ void cam_to_world(const float* __restrict__ v, float R[9], float o[3]) {
     // W2C[r][c] = v[4c + r]
     const float a = v[0], b = v[4], c = v[8], d = v[1], e = v[5], f = v[9], g = v[2], h = v[6], i = v[10];
@@ -27,6 +31,18 @@ __device__ __forceinline__ void cam_to_world(const float* __restrict__ v, float 
     o[0] = -(R[0] * tx + R[1] * ty + R[2] * tz);
     o[1] = -(R[3] * tx + R[4] * ty + R[5] * tz);
     o[2] = -(R[6] * tx + R[7] * ty + R[8] * tz);
+}
+
+// out = V3^T n with V3[r][c] = W2C[r][c] = v[4c + r]:  the reference's  n_row @ world_view_transform[:3, :3].T
+__device__ __forceinline__ void rotate_normal(const float* __restrict__ v, const float n[3], float out[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = v[4 * k] * n[0] + v[4 * k + 1] * n[1] + v[4 * k + 2] * n[2];
+}
+
+// its adjoint: out = V3 g
+__device__ __forceinline__ void rotate_normal_adjoint(const float* __restrict__ v, const float g[3], float out[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = v[c] * g[0] + v[4 + c] * g[1] + v[8 + c] * g[2];
 }
 
 __device__ __forceinline__ float finite_or_zero(float x) { return (x == x && fabsf(x) <= 3.402823466e38f) ? x : 0.f; }
@@ -52,10 +68,10 @@ __global__ __launch_bounds__(256) void postprocess_forward_kernel(PostCam cam, c
     const size_t HW = (size_t)cam.W * cam.H, pix = (size_t)y * cam.W + x;
     float R[9], o[3];
     cam_to_world(cam.view, R, o);
-    const float n0 = allmap[2 * HW + pix], n1 = allmap[3 * HW + pix], n2 = allmap[4 * HW + pix];
-    rend_normal[pix] = R[0] * n0 + R[1] * n1 + R[2] * n2;
-    rend_normal[HW + pix] = R[3] * n0 + R[4] * n1 + R[5] * n2;
-    rend_normal[2 * HW + pix] = R[6] * n0 + R[7] * n1 + R[8] * n2;
+    const float n[3] = {allmap[2 * HW + pix], allmap[3 * HW + pix], allmap[4 * HW + pix]};
+    float rn[3];
+    rotate_normal(cam.view, n, rn);
+    rend_normal[pix] = rn[0]; rend_normal[HW + pix] = rn[1]; rend_normal[2 * HW + pix] = rn[2];
     const float d = surf_depth_at(allmap, HW, pix, cam.depth_ratio);
     surf_depth[pix] = d;
     float p[3];
@@ -150,9 +166,9 @@ __global__ __launch_bounds__(256) void postprocess_backward_gather_kernel(PostCa
     g_allmap[6 * HW + pix] = 0.f;
     float gn[3] = {0.f, 0.f, 0.f};
     if (g_rend_normal) { gn[0] = g_rend_normal[pix]; gn[1] = g_rend_normal[HW + pix]; gn[2] = g_rend_normal[2 * HW + pix]; }
-    g_allmap[2 * HW + pix] = R[0] * gn[0] + R[3] * gn[1] + R[6] * gn[2];   // R^T g
-    g_allmap[3 * HW + pix] = R[1] * gn[0] + R[4] * gn[1] + R[7] * gn[2];
-    g_allmap[4 * HW + pix] = R[2] * gn[0] + R[5] * gn[1] + R[8] * gn[2];
+    float gr[3];
+    rotate_normal_adjoint(cam.view, gn, gr);
+    g_allmap[2 * HW + pix] = gr[0]; g_allmap[3 * HW + pix] = gr[1]; g_allmap[4 * HW + pix] = gr[2];
 }
 
 static dim3 post_grid(int W, int H) { return dim3((W + 63) / 64, (H + 3) / 4); }

@@ -11,6 +11,7 @@ from oracle.postprocess_torch import postprocess_allmap as postprocess_allmap_to
 from streetunveiler_amd.gaussian_renderer import (PipelineParams, SurfelModel, postprocess_allmap, render, render_semantic,
                                                   render_semantic_with_mask, render_with_mask)
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tests import postprocess_cases as pc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -249,6 +250,11 @@ def _postprocess_against_torch(cam, W, H):
         assert np.isfinite(ggpu).all()
         scale = np.abs(gref).max()
         assert np.abs(ggpu - gref).max() <= 2e-4 * scale, np.abs(ggpu - gref).max() / scale
+        # ... and per map and per gradient channel, against the float32 restatement's own deviation (tests/postprocess_cases.py): that one
+        # scale is channel 1's at the smallest alpha, 1e4 times anything channels 2-5 hold
+        got = dict({k: out[k].detach().double().cpu().numpy() for k in pc.ALL_MAPS}, g_allmap=ggpu.astype(np.float64))
+        pc.assert_within_bar(got, pc.run(postprocess_allmap_torch, cam, ratio, allmap, grads, torch.float64),
+                             pc.run(postprocess_allmap_torch, cam, ratio, allmap, grads, torch.float32), f"postprocess.hip {W}x{H} ratio {ratio}")
 
 
 def test_fused_postprocess_matches_reference_fixture(golden_dir):
@@ -277,6 +283,14 @@ def test_fused_postprocess_matches_reference_fixture(golden_dir):
             assert np.isfinite(got).all() and fin.mean() > 0.8
             scale = np.abs(ref[fin]).max()
             assert np.abs(got[fin] - ref[fin]).max() <= 2e-4 * scale, (pre, run, np.abs(got[fin] - ref[fin]).max() / scale)
+            # ... and per map and per gradient channel (tests/postprocess_cases.py): truth = the float64 restatement on the stored allmap,
+            # yardstick = the deviation of the reference's own stored float32 maps and gradient from it
+            up = {k: torch.tensor(z[pre + "up_" + k]) for k in maps}
+            truth = pc.run(postprocess_allmap_torch, cam.to("cpu"), float(ratio), torch.tensor(z[pre + run + "_allmap"]), up, torch.float64)
+            np.testing.assert_array_equal(np.isfinite(truth["g_allmap"]), fin)
+            stored = dict({k: z[pre + run + "_" + k].astype(np.float64) for k in maps}, g_allmap=ref.astype(np.float64))
+            hip = dict({k: out[k].detach().double().cpu().numpy() for k in maps}, g_allmap=got.astype(np.float64))
+            pc.assert_within_bar(hip, truth, stored, f"postprocess.hip fixture {pre}{run}")
 
 
 def test_fused_activations_and_ply_checkpoint(tmp_path):
