@@ -78,12 +78,18 @@ __global__ void knn_morton_kernel(const float* __restrict__ pts, int n, const fl
     codes[i] = spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2);
 }
 
-// sorted[i] = (x, y, z, original index) of the i-th point along the curve
+// sorted[i] = (x, y, z, original index) of the i-th point along the curve.
+// A point with a NaN or inf coordinate is nobody's neighbour and has none, as in the oracle, whose `d < best` never takes its NaN / inf
+// distance.  It is stored as (inf, inf, inf): its distance to every finite point is then +inf, which the fminf / fmaxf chain of insert_best
+// carries through and drops, and never NaN, for which both calls hand back best[k] and duplicate every entry one slot down.  The search
+// kernel switches such a query off (`live`), the box kernel leaves it out of the AABBs; the scan loop pays nothing for it.
 __global__ void knn_gather_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ order, int n, float4* __restrict__ sorted) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t j = order[i];
-    sorted[i] = make_float4(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], __uint_as_float(j));
+    const float x = pts[3 * (size_t)j], y = pts[3 * (size_t)j + 1], z = pts[3 * (size_t)j + 2];
+    const bool finite = fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX;   // false for NaN too
+    sorted[i] = finite ? make_float4(x, y, z, __uint_as_float(j)) : make_float4(INFINITY, INFINITY, INFINITY, __uint_as_float(j));
 }
 
 // AABB of each run of kKnnBox curve-consecutive points: boxes[2b] = (min, -), boxes[2b+1] = (max, -)
@@ -93,6 +99,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_boxes_kernel(const float4* __
     float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int j = threadIdx.x; j < kKnnBox && base + j < n; j += kKnnThreads) {
         const float4 p = sorted[base + j];
+        if (!(p.x <= FLT_MAX)) continue;   // a non-finite point (knn_gather_kernel): no candidate, so no part of the box
         lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
         hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
     }
@@ -123,7 +130,7 @@ __device__ __forceinline__ float dist2(const float4 a, const float4 b) {
 }
 
 template <int K>
-__device__ __forceinline__ void insert_best(float (&best)[K], float d) {   // keeps best[] ascending; branch-free
+__device__ __forceinline__ void insert_best(float (&best)[K], float d) {   // keeps best[] ascending; branch-free; d is never NaN (knn_gather_kernel)
 #pragma unroll
     for (int k = 0; k < K; ++k) { const float lo = fminf(best[k], d); d = fmaxf(best[k], d); best[k] = lo; }
 }
@@ -150,6 +157,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_search_kernel(const float4* _
     const int pos = wave_base + lane;
     const bool valid = pos < nq;
     const float4 q = q_sorted[valid ? pos : nq - 1];
+    const bool live = valid && q.x <= FLT_MAX;   // a non-finite query (knn_gather_kernel) searches nothing: its lists stay FLT_MAX, its mean is inf
     float best[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) best[k] = FLT_MAX;
@@ -173,12 +181,12 @@ __global__ __launch_bounds__(kKnnThreads) void knn_search_kernel(const float4* _
 
     // AABB of the wave's queries
     const float big = FLT_MAX;
-    const float wlo[3] = {wave_min(valid ? q.x : big), wave_min(valid ? q.y : big), wave_min(valid ? q.z : big)};
-    const float whi[3] = {wave_max(valid ? q.x : -big), wave_max(valid ? q.y : -big), wave_max(valid ? q.z : -big)};
+    const float wlo[3] = {wave_min(live ? q.x : big), wave_min(live ? q.y : big), wave_min(live ? q.z : big)};
+    const float whi[3] = {wave_max(live ? q.x : -big), wave_max(live ? q.y : -big), wave_max(live ? q.z : -big)};
 
     for (int g = 0; g < n_boxes; g += kWave) {
         // the worst bound any lane still has: a box farther than that from the wave's AABB cannot matter to anyone
-        const float bound = wave_max(valid ? fminf(reject, best[K - 1]) : 0.f);
+        const float bound = wave_max(live ? fminf(reject, best[K - 1]) : 0.f);
         bool need = false;
         if (g + lane < n_boxes) {
             const float4 bl = boxes[2 * (g + lane)], bh = boxes[2 * (g + lane) + 1];
@@ -196,7 +204,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_search_kernel(const float4* _
             const float px = fmaxf(0.f, fmaxf(bl.x - q.x, q.x - bh.x)), py = fmaxf(0.f, fmaxf(bl.y - q.y, q.y - bh.y)),
                         pz = fmaxf(0.f, fmaxf(bl.z - q.z, q.z - bh.z));
             const float pd = (px * px + py * py) + pz * pz;
-            const bool mine = valid && !(pd > reject) && !(pd > best[K - 1]);
+            const bool mine = live && !(pd > reject) && !(pd > best[K - 1]);
             if (ballot64(mine) == 0) continue;
             const int first = b * kKnnBox, last = min(nr, first + kKnnBox);
             for (int j = first; j < last; ++j) {
