@@ -341,6 +341,20 @@ size_t sr_knn_workspace_bytes(int32_t n_query, int32_t n_reference);
 int sr_knn_mean_dist2(int32_t n_query, const float* query, int32_t n_reference, const float* reference, int32_t K,
                       int32_t take_sqrt, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Radius clustering == GaussianModel.cluster_instance_with_mask / cluster_semantic_instance with parallel=False
+ * (/root/reference/scene/gaussian_model.py:579-651): the connected components of the graph that joins two active points when
+ * sqrtf((dx*dx + dy*dy) + dz*dz) < radius in float32 (strictly below), each named by its smallest point index.
+ * labels[i] = that index for an active point, -1 for a point with active[i] == 0, i for an active point with a NaN / inf coordinate
+ * (it is within range of nobody, itself included).  xyz [n,3] float32, active [n] uint8 or NULL (every point), labels [n] int64: device
+ * arrays; workspace: sr_cluster_workspace_bytes(n) bytes.  Exact and deterministic; a cloud whose points all lie within one radius of
+ * each other costs all its pairs.  SR_ERR_INVALID_ARGUMENT for n < 0, a radius that is not a finite number >= 0, or NULL xyz / labels /
+ * workspace with n > 0; SR_ERR_BUFFER_TOO_SMALL for a short workspace.
+ * Added without a new SR_ABI_VERSION: nothing that existed changed its signature, layout or meaning, so a caller built against the
+ * header before these two declarations runs unchanged against this library (a caller that needs them checks for the symbols). */
+size_t sr_cluster_workspace_bytes(int32_t n);
+int sr_cluster_radius(int32_t n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* K9: present[i] = (view-space z of means3D[i] > 0.2).  present is uint8 (torch.bool storage). */
 int sr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                     uint8_t* present, void* stream);

@@ -75,7 +75,7 @@ EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_e
            "sr_backward_workspace_bytes", "sr_geom_view", "sr_binning_view", "sr_image_view", "sr_forward_plan", "sr_sh_gradient_expand", "sr_knn_workspace_bytes", "sr_knn_mean_dist2",
            "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
            "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
-           "sr_adam_step", "sr_densification_stats"]
+           "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius"]
 
 _lib = None
 
@@ -148,6 +148,9 @@ def load():
     lib.sr_knn_workspace_bytes.restype = C.c_size_t
     lib.sr_knn_mean_dist2.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]
+    lib.sr_cluster_workspace_bytes.argtypes = [C.c_int32]
+    lib.sr_cluster_workspace_bytes.restype = C.c_size_t
+    lib.sr_cluster_radius.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.sr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sr_set_stage_timing.argtypes = [C.c_int]
     lib.sr_postprocess_forward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 7

@@ -36,6 +36,7 @@ SOURCES = [
     ("image_loss.hip", []),
     ("optimizer.hip", ["-ffp-contract=off"]),   # the Adam step's operation order is the one torch's single-tensor path states
     ("knn.hip", ["-ffp-contract=off"]),         # squared distances bit-identical to the brute-force oracle
+    ("cluster.hip", ["-ffp-contract=off"]),     # the distance predicate is bit-identical to the float32 expression it restates
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -1,5 +1,6 @@
 // api.hip -- the C-ABI (include/surfel_raster.h): buffer layouts, argument checks, stage sequencing.
 // No torch types, no exceptions across the boundary, nothing allocated persistently.
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -884,6 +885,21 @@ int sr_knn_mean_dist2(int32_t n_query, const float* query, int32_t n_reference, 
     RankMode sort_mode = kRankUnknown;
     if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &sort_mode)) return rc;
     SR_HIP(knn_mean_dist2(nq, query, n_reference, reference, K, take_sqrt, out, workspace, workspace_bytes, sort_mode, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+size_t sr_cluster_workspace_bytes(int32_t n) { return cluster_workspace_bytes(n > 0 ? n : 0); }
+
+int sr_cluster_radius(int32_t n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "negative point count");
+    if (!(radius >= 0.f && radius <= FLT_MAX)) return fail(SR_ERR_INVALID_ARGUMENT, "radius %g is not a finite number >= 0", (double)radius);
+    if (n == 0) return SR_OK;
+    if (!xyz || !labels || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (workspace_bytes < cluster_workspace_bytes(n)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, cluster_workspace_bytes(n));
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &sort_mode)) return rc;
+    SR_HIP(cluster_radius(n, xyz, active, radius, labels, workspace, workspace_bytes, sort_mode, static_cast<hipStream_t>(stream)));
     return SR_OK;
 }
 

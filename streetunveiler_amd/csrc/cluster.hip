@@ -1,0 +1,199 @@
+// Radius clustering of a point cloud == what GaussianModel.cluster_instance_with_mask / cluster_semantic_instance compute with
+// parallel=False [REF /root/reference/scene/gaussian_model.py:579-651]: the connected components of the graph "two active points are
+// joined when sqrtf((dx*dx + dy*dy) + dz*dz) < threshold", each named by its smallest point index.
+//
+// The search is the kNN's with a constant bound (knn.hip: Morton order, boxes of 512 curve-consecutive points, one wave64 per 64
+// consecutive queries, wave-uniform candidates), and every edge is looked at once: a query scans the candidates BEFORE its own place on
+// the curve.  On top of it sits a lock-free union-find over the ORIGINAL point indices (the ECL-CC scheme: Jaiganesh & Burtscher, HPDC
+// 2018): a root is only ever hooked under a SMALLER root, by compare-and-swap, so the root of a finished tree is the smallest index of
+// its component and the labels do not depend on the order in which the unions raced.  The only loops on shared state are the walk to a
+// root, which every step shortens, and the retry of a hook whose root another lane hooked first; no lane waits for another.
+// Integer / latency / VALU work only; no LDS, no MFMA.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "launch.h"
+
+namespace sr {
+
+constexpr int kWave = 64;
+constexpr int kClusterThreads = 256;
+
+// parent[] is shared by every wave of the edge kernel: relaxed agent-scope accesses, so that a retry reads memory again and not a register
+__device__ __forceinline__ int load_parent(const int* parent, int i) { return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store_parent(int* parent, int i, int v) { __hip_atomic_store(parent + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The root of x's tree, with path halving.  parent[i] <= i always, so the walk descends and ends.  The halving store goes to a node that
+// has been seen with a parent other than itself: it is no root and never becomes one again, so the store cannot undo a hook (hooks
+// write roots only), and what it writes is an ancestor of that node.
+__device__ __forceinline__ int find_root(int* parent, int x) {
+    int curr = load_parent(parent, x);
+    if (curr == x) return x;
+    int prev = x;
+    for (;;) {
+        const int next = load_parent(parent, curr);
+        if (next == curr) return curr;
+        store_parent(parent, prev, next);
+        prev = curr;
+        curr = next;
+    }
+}
+
+// Joins the trees of a and b: the larger root goes under the smaller.  A failed compare-and-swap means the larger one has been hooked
+// meanwhile, to something smaller still, which is where the next attempt starts: max(ra, rb) falls with every retry.
+__device__ __forceinline__ void unite(int* parent, int a, int b) {
+    int ra = find_root(parent, a), rb = find_root(parent, b);
+    while (ra != rb) {
+        const int hi = max(ra, rb), lo = min(ra, rb);
+        const int seen = atomicCAS(parent + hi, hi, lo);
+        if (seen == hi) return;
+        ra = seen;
+        rb = lo;
+    }
+}
+
+__global__ __launch_bounds__(kClusterThreads) void cluster_init_kernel(int n, int* __restrict__ parent) {
+    const long long i = (long long)blockIdx.x * kClusterThreads + threadIdx.x;
+    if (i < n) parent[i] = (int)i;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// The squared distance of the predicate, in its operation order (-ffp-contract=off: build.py)
+__device__ __forceinline__ float dist2(const float4 a, const float4 b) {
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// A box (or a point: lo == hi) against a box, with the same operations on the gaps: a gap is no larger than the coordinate difference of
+// any pair of points from the two, and subtraction, multiplication and addition of float32 are monotone, so a pair whose dist2 is below
+// a bound has boxes whose gap2 is below it.  Needs no slack.  (An empty box is (FLT_MAX, -FLT_MAX): its gap2 is inf.)
+__device__ __forceinline__ float gap2(const float4 alo, const float4 ahi, const float (&blo)[3], const float (&bhi)[3]) {
+    const float gx = fmaxf(0.f, fmaxf(alo.x - bhi[0], blo[0] - ahi.x));
+    const float gy = fmaxf(0.f, fmaxf(alo.y - bhi[1], blo[1] - ahi.y));
+    const float gz = fmaxf(0.f, fmaxf(alo.z - bhi[2], blo[2] - ahi.z));
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// One wave = 64 curve-consecutive queries.  sorted[] holds the points that take part first, in Morton order, and every other point behind
+// them as (inf, inf, inf) (knn.hip, masked ordering); `d2_below` is the predicate as a bound on the squared distance (cluster_d2_below).
+__global__ __launch_bounds__(kClusterThreads) void cluster_edges_kernel(const float4* __restrict__ sorted, int n, const float4* __restrict__ boxes,
+                                                                         float d2_below, int* parent) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const long long wave_base = ((long long)blockIdx.x * (kClusterThreads / kWave) + threadIdx.x / kWave) * kWave;
+    if (wave_base >= n) return;
+    const bool valid = wave_base + lane < n;
+    const int pos = valid ? (int)(wave_base + lane) : n - 1;
+    const float4 q = sorted[pos];
+    const bool live = valid && q.x <= FLT_MAX;
+    if (ballot64(live) == 0) return;   // the tail of the curve: nobody here takes part
+    const int qi = __float_as_int(q.w);
+
+    const float big = FLT_MAX;
+    const float wlo[3] = {wave_min(live ? q.x : big), wave_min(live ? q.y : big), wave_min(live ? q.z : big)};
+    const float whi[3] = {wave_max(live ? q.x : -big), wave_max(live ? q.y : -big), wave_max(live ? q.z : -big)};
+    const float qp[3] = {q.x, q.y, q.z};
+
+    const int own_box = (int)(wave_base / kKnnBox);   // 64 divides 512: the wave's queries share a box
+    const int limit = (int)(wave_base + kWave - 1 < n ? wave_base + kWave - 1 : n);   // candidates end before the wave's last query
+    for (int g = 0; g <= own_box; g += kWave) {
+        bool need = false;
+        if (g + lane <= own_box) need = gap2(boxes[2 * (size_t)(g + lane)], boxes[2 * (size_t)(g + lane) + 1], wlo, whi) < d2_below;
+        unsigned long long todo = ballot64(need);
+        while (todo) {
+            const int b = g + __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const bool mine = live && gap2(boxes[2 * (size_t)b], boxes[2 * (size_t)b + 1], qp, qp) < d2_below;
+            if (ballot64(mine) == 0) continue;
+            const int first = b * kKnnBox, last = first + min(kKnnBox, limit - first);
+            for (int j = first; j < last; ++j) {
+                const float4 c = sorted[j];   // wave-uniform address
+                const bool hit = mine && j < pos && dist2(q, c) < d2_below;
+                if (hit) {
+                    const int ci = __float_as_int(c.w);
+                    // in a dense cluster almost every edge joins what is joined already: two loads, no atomic
+                    if (load_parent(parent, qi) != load_parent(parent, ci)) unite(parent, qi, ci);
+                }
+            }
+        }
+    }
+}
+
+// After the edge kernel has finished (the kernel boundary is the fence): labels by ORIGINAL index, read off the sorted array, which knows
+// who took part.
+__global__ __launch_bounds__(kClusterThreads) void cluster_labels_kernel(const float4* __restrict__ sorted, const uint8_t* __restrict__ active, int n,
+                                                                          int* parent, long long* __restrict__ labels) {
+    const long long pos = (long long)blockIdx.x * kClusterThreads + threadIdx.x;
+    if (pos >= n) return;
+    const float4 p = sorted[pos];
+    const int i = __float_as_int(p.w);
+    if (p.x <= FLT_MAX) labels[i] = find_root(parent, i);
+    else labels[i] = (active && !active[i]) ? -1 : i;   // masked out | active with a NaN / inf coordinate: in range of nobody, itself included
+}
+
+struct ClusterLayout {
+    size_t partial, bounds, codes, codes_sorted, order, sorted, boxes, parent, sort_temp, total;
+    int n_boxes;
+};
+
+static ClusterLayout cluster_layout(int n) {
+    ClusterLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 1, 256); return o; };
+    L.n_boxes = (int)(((long long)n + kKnnBox - 1) / kKnnBox);
+    L.partial = take(cloud_bounds_partial_bytes(n));
+    L.bounds = take(6 * 4);
+    L.codes = take((size_t)n * 4); L.codes_sorted = take((size_t)n * 4); L.order = take((size_t)n * 4);
+    L.sorted = take((size_t)n * 16);
+    L.boxes = take((size_t)L.n_boxes * 32);
+    L.parent = take((size_t)n * 4);
+    L.sort_temp = take(radix_sort_temp_bytes((uint32_t)n));
+    L.total = off;
+    return L;
+}
+
+template <class T> static T* wat(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+// sqrtf(d2) < r  <=>  d2 < T, with T the smallest float32 whose root is not below r: sqrtf is correctly rounded, hence monotone, so the
+// float32 values split into those below T, whose root is below r, and the rest.  r * r lies within a few steps of T; the two loops walk
+// there whichever side it is on.  (r == 0: T = 0, no pair.  A root is taken nowhere else: the kernels compare squared distances with T.)
+static float cluster_d2_below(float r) {
+    float t = r * r;
+    while (t > 0.f && sqrtf(nextafterf(t, -INFINITY)) >= r) t = nextafterf(t, -INFINITY);
+    while (sqrtf(t) < r) t = nextafterf(t, INFINITY);
+    return t;
+}
+
+size_t cluster_workspace_bytes(int n) { return cluster_layout(n).total; }
+
+// n >= 1; radius finite and >= 0 (api.hip)
+hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* ws, size_t ws_bytes,
+                          RankMode rank_mode, hipStream_t s) {
+    const ClusterLayout L = cluster_layout(n);
+    if (ws_bytes < L.total) return hipErrorInvalidValue;
+    float* bounds = wat<float>(ws, L.bounds);
+    const CloudOrder o{wat<uint32_t>(ws, L.codes), wat<uint32_t>(ws, L.codes_sorted), wat<uint32_t>(ws, L.order), wat<float4>(ws, L.sorted)};
+    int* parent = wat<int>(ws, L.parent);
+    const dim3 grid((unsigned)(((long long)n + kClusterThreads - 1) / kClusterThreads)), block(kClusterThreads);
+    hipError_t e = cloud_bounds_masked(xyz, active, n, wat<float>(ws, L.partial), bounds, s);
+    if (e != hipSuccess) return e;
+    e = cloud_order(xyz, active, true, n, bounds, o, wat<void>(ws, L.sort_temp), radix_sort_temp_bytes((uint32_t)n), rank_mode, s);
+    if (e != hipSuccess) return e;
+    e = cloud_boxes(o.sorted, n, wat<float4>(ws, L.boxes), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cluster_init_kernel, grid, block, 0, s, n, parent);
+    hipLaunchKernelGGL(cluster_edges_kernel, grid, block, 0, s, o.sorted, n, wat<float4>(ws, L.boxes), cluster_d2_below(radius), parent);
+    hipLaunchKernelGGL(cluster_labels_kernel, grid, block, 0, s, o.sorted, active, n, parent, reinterpret_cast<long long*>(labels));
+    return hipGetLastError();
+}
+
+}  // namespace sr

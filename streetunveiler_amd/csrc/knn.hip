@@ -19,14 +19,30 @@
 namespace sr {
 
 constexpr int kWave = 64;
-constexpr int kKnnBox = 512;
 constexpr int kKnnThreads = 256;
 
-// ---- bounding box -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kKnnThreads) void knn_bounds_partial_kernel(const float* __restrict__ pts, int n, float* __restrict__ partial) {
+// ---- ordering a cloud ---------------------------------------------------------------------------------------
+// Bounds, Morton codes, the sorted (x, y, z, index) array and the box AABBs are what cluster.hip searches too (launch.h: cloud_order and
+// its neighbours).  Its clouds carry a mask -- kMasked: a point takes part when active[i] != 0 (active == nullptr: every point) and its
+// coordinates are finite.  A point that does not is left out of the bounds, gets kDeadCode, which the 31-bit sort puts behind every
+// live point of the curve, and is stored as (inf, inf, inf) like a non-finite point of the kNN.  The kNN's own instantiations
+// (kMasked = false) are the kernels they were.
+constexpr uint32_t kDeadCode = 1u << 30;
+
+template <bool kMasked>
+__device__ __forceinline__ bool takes_part(const float* __restrict__ pts, const uint8_t* __restrict__ active, size_t i) {
+    if (!kMasked) return true;
+    if (active && !active[i]) return false;
+    return fabsf(pts[3 * i]) <= FLT_MAX && fabsf(pts[3 * i + 1]) <= FLT_MAX && fabsf(pts[3 * i + 2]) <= FLT_MAX;   // false for NaN too
+}
+
+template <bool kMasked>
+__global__ __launch_bounds__(kKnnThreads) void knn_bounds_partial_kernel(const float* __restrict__ pts, const uint8_t* __restrict__ active, int n,
+                                                                          float* __restrict__ partial) {
     __shared__ float s_red[6][kKnnThreads / kWave];
     float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int i = blockIdx.x * kKnnThreads + threadIdx.x; i < n; i += gridDim.x * kKnnThreads) {
+        if (!takes_part<kMasked>(pts, active, (size_t)i)) continue;
 #pragma unroll
         for (int c = 0; c < 3; ++c) { const float v = pts[3 * (size_t)i + c]; lo[c] = fminf(lo[c], v); hi[c] = fmaxf(hi[c], v); }
     }
@@ -65,9 +81,12 @@ __device__ __forceinline__ uint32_t spread10(uint32_t v) {   // 10 bits -> every
     return v;
 }
 
-__global__ void knn_morton_kernel(const float* __restrict__ pts, int n, const float* __restrict__ bounds, uint32_t* __restrict__ codes) {
+template <bool kMasked>
+__global__ void knn_morton_kernel(const float* __restrict__ pts, const uint8_t* __restrict__ active, int n, const float* __restrict__ bounds,
+                                  uint32_t* __restrict__ codes) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (!takes_part<kMasked>(pts, active, (size_t)i)) { codes[i] = kDeadCode; return; }
     uint32_t q[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -83,12 +102,14 @@ __global__ void knn_morton_kernel(const float* __restrict__ pts, int n, const fl
 // distance.  It is stored as (inf, inf, inf): its distance to every finite point is then +inf, which the fminf / fmaxf chain of insert_best
 // carries through and drops, and never NaN, for which both calls hand back best[k] and duplicate every entry one slot down.  The search
 // kernel switches such a query off (`live`), the box kernel leaves it out of the AABBs; the scan loop pays nothing for it.
-__global__ void knn_gather_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ order, int n, float4* __restrict__ sorted) {
+template <bool kMasked>
+__global__ void knn_gather_kernel(const float* __restrict__ pts, const uint8_t* __restrict__ active, const uint32_t* __restrict__ order, int n,
+                                  float4* __restrict__ sorted) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t j = order[i];
     const float x = pts[3 * (size_t)j], y = pts[3 * (size_t)j + 1], z = pts[3 * (size_t)j + 2];
-    const bool finite = fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX;   // false for NaN too
+    const bool finite = fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX && !(kMasked && active && !active[j]);   // false for NaN too
     sorted[i] = finite ? make_float4(x, y, z, __uint_as_float(j)) : make_float4(INFINITY, INFINITY, INFINITY, __uint_as_float(j));
 }
 
@@ -232,6 +253,34 @@ struct KnnLayout {
 
 static int bounds_blocks(int n) { const int b = (n + kKnnThreads * 8 - 1) / (kKnnThreads * 8); return b < 1 ? 1 : (b > 1024 ? 1024 : b); }
 
+// ---- the ordering steps, for the search below and for cluster.hip (launch.h) ---------------------------------------------------
+size_t cloud_bounds_partial_bytes(int n) { return (size_t)bounds_blocks(n) * 6 * 4; }
+
+hipError_t cloud_bounds_masked(const float* pts, const uint8_t* active, int n, float* partial, float* bounds, hipStream_t s) {
+    const int blocks = bounds_blocks(n);
+    hipLaunchKernelGGL(knn_bounds_partial_kernel<true>, dim3(blocks), dim3(kKnnThreads), 0, s, pts, active, n, partial);
+    hipLaunchKernelGGL(knn_bounds_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, bounds);
+    return hipGetLastError();
+}
+
+hipError_t cloud_order(const float* pts, const uint8_t* active, bool masked, int n, const float* bounds, const CloudOrder& o, void* sort_temp,
+                       size_t temp_bytes, RankMode rank_mode, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (masked) hipLaunchKernelGGL(knn_morton_kernel<true>, grid, block, 0, s, pts, active, n, bounds, o.codes);
+    else hipLaunchKernelGGL(knn_morton_kernel<false>, grid, block, 0, s, pts, active, n, bounds, o.codes);
+    const hipError_t e = radix_sort_pairs(o.codes, nullptr, o.codes_sorted, o.order, (uint32_t)n, masked ? 31 : 30, sort_temp, temp_bytes, s, nullptr,
+                                          nullptr, rank_mode, false);
+    if (e != hipSuccess) return e;
+    if (masked) hipLaunchKernelGGL(knn_gather_kernel<true>, grid, block, 0, s, pts, active, o.order, n, o.sorted);
+    else hipLaunchKernelGGL(knn_gather_kernel<false>, grid, block, 0, s, pts, active, o.order, n, o.sorted);
+    return hipGetLastError();
+}
+
+hipError_t cloud_boxes(const float4* sorted, int n, float4* boxes, hipStream_t s) {
+    hipLaunchKernelGGL(knn_boxes_kernel, dim3((n + kKnnBox - 1) / kKnnBox), dim3(kKnnThreads), 0, s, sorted, n, boxes);
+    return hipGetLastError();
+}
+
 KnnLayout knn_layout(int nq, int nr) {   // nq == 0: self search
     KnnLayout L{};
     size_t off = 0;
@@ -262,23 +311,21 @@ hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* refer
     const KnnLayout L = knn_layout(nq, nr);
     if (ws_bytes < L.total) return hipErrorInvalidValue;
     float* partial = wat<float>(ws, L.partial); float* bounds = wat<float>(ws, L.bounds);
-    hipLaunchKernelGGL(knn_bounds_partial_kernel, dim3(L.blocks_r), dim3(kKnnThreads), 0, s, reference, nr, partial);
-    if (!self) hipLaunchKernelGGL(knn_bounds_partial_kernel, dim3(L.blocks_q), dim3(kKnnThreads), 0, s, query, nq, partial + 6 * L.blocks_r);
+    const uint8_t* const all = nullptr;   // the kNN's clouds carry no mask
+    hipLaunchKernelGGL(knn_bounds_partial_kernel<false>, dim3(L.blocks_r), dim3(kKnnThreads), 0, s, reference, all, nr, partial);
+    if (!self) hipLaunchKernelGGL(knn_bounds_partial_kernel<false>, dim3(L.blocks_q), dim3(kKnnThreads), 0, s, query, all, nq, partial + 6 * L.blocks_r);
     hipLaunchKernelGGL(knn_bounds_final_kernel, dim3(1), dim3(64), 0, s, partial, L.blocks_r + L.blocks_q, bounds);
     const size_t temp_bytes = radix_sort_temp_bytes((uint32_t)(nq > nr ? nq : nr));
-    auto order_cloud = [&](const float* pts, int n, size_t codes, size_t codes_sorted, size_t order, size_t sorted) -> hipError_t {
-        hipLaunchKernelGGL(knn_morton_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, bounds, wat<uint32_t>(ws, codes));
-        hipError_t e = radix_sort_pairs(wat<uint32_t>(ws, codes), nullptr, wat<uint32_t>(ws, codes_sorted), wat<uint32_t>(ws, order),
-                                        (uint32_t)n, 30, wat<void>(ws, L.sort_temp), temp_bytes, s, nullptr, nullptr, rank_mode, false);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(knn_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, wat<uint32_t>(ws, order), n, wat<float4>(ws, sorted));
-        return hipGetLastError();
+    auto order = [&](const float* pts, int n, size_t codes, size_t codes_sorted, size_t order, size_t sorted) {
+        const CloudOrder o{wat<uint32_t>(ws, codes), wat<uint32_t>(ws, codes_sorted), wat<uint32_t>(ws, order), wat<float4>(ws, sorted)};
+        return cloud_order(pts, all, false, n, bounds, o, wat<void>(ws, L.sort_temp), temp_bytes, rank_mode, s);
     };
-    hipError_t e = order_cloud(reference, nr, L.r_codes, L.r_codes_sorted, L.r_order, L.r_sorted);
+    hipError_t e = order(reference, nr, L.r_codes, L.r_codes_sorted, L.r_order, L.r_sorted);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(knn_boxes_kernel, dim3(L.n_boxes), dim3(kKnnThreads), 0, s, wat<float4>(ws, L.r_sorted), nr, wat<float4>(ws, L.boxes));
+    e = cloud_boxes(wat<float4>(ws, L.r_sorted), nr, wat<float4>(ws, L.boxes), s);
+    if (e != hipSuccess) return e;
     if (!self) {
-        e = order_cloud(query, nq, L.q_codes, L.q_codes_sorted, L.q_order, L.q_sorted);
+        e = order(query, nq, L.q_codes, L.q_codes_sorted, L.q_order, L.q_sorted);
         if (e != hipSuccess) return e;
     }
     const int n_search = self ? nr : nq;

@@ -100,6 +100,26 @@ hipError_t launch_class_backward(const FrameDev& f, int n_classes, const uint2* 
 size_t knn_workspace_bytes(int nq, int nr);
 hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
                           size_t ws_bytes, RankMode rank_mode, hipStream_t s);
+// The kNN's ordering of a cloud, step by step, for cluster.hip: bounds -> Morton codes, sort, sorted (x, y, z, index) array -> the AABB
+// of every run of kKnnBox curve-consecutive points.  `masked`: a point with active[i] == 0 (active == nullptr: none) or a non-finite
+// coordinate is left out of the bounds and the boxes, sorted behind every other point and stored as (inf, inf, inf).
+constexpr int kKnnBox = 512;
+struct CloudOrder {   // device arrays of n entries each
+    uint32_t* codes;
+    uint32_t* codes_sorted;
+    uint32_t* order;
+    float4* sorted;
+};
+size_t cloud_bounds_partial_bytes(int n);
+hipError_t cloud_bounds_masked(const float* pts, const uint8_t* active, int n, float* partial, float* bounds, hipStream_t s);
+hipError_t cloud_order(const float* pts, const uint8_t* active, bool masked, int n, const float* bounds, const CloudOrder& o, void* sort_temp,
+                       size_t temp_bytes, RankMode rank_mode, hipStream_t s);
+hipError_t cloud_boxes(const float4* sorted, int n, float4* boxes, hipStream_t s);
+
+// ---- cluster.hip ---------------------------------------------------------------------------------------------------------------------
+size_t cluster_workspace_bytes(int n);
+hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* ws, size_t ws_bytes,
+                          RankMode rank_mode, hipStream_t s);
 
 // ---- postprocess.hip -----------------------------------------------------------------------------------------------------------------
 struct PostCam {
