@@ -1,6 +1,7 @@
 // blend_common.h -- device helpers shared by the blend kernels (render.hip: K6 / decision dump, render_bwd.hip: K7; render_class.hip: the
 // per-class distortion pass): staging of list entries into the tile-local form, exact quadrant culling, the ray-splat test,
-// the emission index of a duplicate, and the wave-level transpose-reduction of the per-entry gradient sums.
+// the emission index of a duplicate, the wave-level transpose-reduction of the per-entry gradient sums, the hit-mask encoding and its
+// decoder, the forward's per-pixel state / step / stores (ForwardPixel ...) and the backward's per-pair arithmetic (BackwardPixel ...).
 #pragma once
 #include "common.h"
 
@@ -541,10 +542,122 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
 }
 
+// Exact (entry, quadrant) hit mask for the backward: K7 visits only the pairs that reached a pixel in the forward.  16 bits per list entry;
+// two-band tiles (16x16, 32x16): low byte = the QX quadrant bits of the upper band, high byte = those of the lower band.
+template <int QX, int QY, int SPLIT>
+__device__ __forceinline__ void store_hit_mask(uint16_t* __restrict__ hit_mask, uint32_t pos, int part, uint32_t hm) {
+    if (SPLIT == 2) reinterpret_cast<uint8_t*>(hit_mask)[2 * (size_t)pos + part] = (uint8_t)hm;
+    else if (QY == 2) hit_mask[pos] = (uint16_t)((hm & ((1u << QX) - 1u)) | ((hm >> QX) << 8));
+    else hit_mask[pos] = (uint16_t)hm;
+}
 template <int QX, int QY>
-__device__ __forceinline__ uint32_t decode_hits(uint16_t h) {   // see the hit_mask store in K6
-    // two-band tiles (16x16, 32x16): low byte = the QX quadrant bits of the upper band, high byte = those of the lower band
+__device__ __forceinline__ uint32_t decode_hits(uint16_t h) {
     return QY == 2 ? (((uint32_t)h & ((1u << QX) - 1u)) | ((((uint32_t)h >> 8) & ((1u << QX) - 1u)) << QX)) : (uint32_t)h;
+}
+// a round's hits wait as scalar ballots (bit j of hit[q] = entry j reached a pixel of quadrant q): the quadrant bits of the entry `lane` stages
+template <int NQ>
+__device__ __forceinline__ uint32_t lane_hit_bits(const unsigned long long (&hit)[NQ], int lane) {
+    uint32_t hm = 0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) hm |= (uint32_t)((hit[q] >> lane) & 1ull) << q;
+    return hm;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The blend forward's straight-line pieces, written once: which band of which tile a workgroup owns, a pixel's running state, its step for
+// a pair that passed `intersect`, and its stores.  The walks (staging pipeline, prefetch distances, ballot / row loops, barriers) differ
+// for measured reasons and stay in the kernels (render.hip, render_class.hip).  Everything here is inlined into its callers.
+// ---------------------------------------------------------------------------------------------
+// A binning tile (QX*8 wide, QY*8*SPLIT high) is walked by SPLIT band waves.  Workgroups are dealt round-robin to the 8 XCDs, each with its
+// own L2: the SPLIT bands of one tile take consecutive slots of the SAME XCD, so that the second band finds the tile's records in that L2
+// instead of fetching them again (the grid is rounded up to whole XCD rows, so a slot can lie past the last tile: the caller returns).
+// (Xc, Yc): the local origin = centre of the binning tile, shared with K7 (identical staged values, identical decisions); yshift_px: this
+// band's quadrants relative to that centre.  Two steps, the caller's `return` between them: with the test inside, the origin's arithmetic
+// was scheduled in front of the branch.
+struct Band { int tile, part, tx0, ty0, yshift_px; float Xc, Yc; };
+template <int SPLIT>
+__device__ __forceinline__ void band_of_block(Band& b) {   // -> b.tile (still the slot in tile_order), b.part
+    b.tile = blockIdx.x; b.part = 0;
+    if (SPLIT > 1) {
+        const int xcd = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
+        b.tile = (k / SPLIT) * kXcds + xcd; b.part = k % SPLIT;
+    }
+}
+template <int QX, int QY, int SPLIT>
+__device__ __forceinline__ void band_origin(const FrameDev& f, const uint32_t* tile_order, Band& b) {
+    b.tile = (int)tile_order[b.tile];   // longest lists first (binning.hip tile_order_kernel)
+    b.tx0 = (b.tile % f.tiles_x) * (QX * 8); b.ty0 = (b.tile / f.tiles_x) * (QY * 8 * SPLIT) + b.part * (QY * 8);
+    b.Xc = (float)(b.tx0 + QX * 4); b.Yc = (float)((b.tile / f.tiles_x) * (QY * 8 * SPLIT) + QY * SPLIT * 4);
+    b.yshift_px = b.part * (QY * 8) - QY * (SPLIT - 1) * 4;
+}
+
+// T > 0: the pixel is live.  T < 0: done (saturated, or outside the image) -- |T| is its final transmittance.  (A separate flag per pixel
+// costs a byte compare, two moves and a four-instruction all-done test per quadrant test.)  C3..C8 are only live with 6 / 9 channels.
+struct ForwardPixel {
+    float T, C0, C1, C2, N0, N1, N2, Dsum, M1, M2, dist, med, C3, C4, C5, C6, C7, C8;
+    uint32_t lastc, medc;   // last / median contributor (1-based list position)
+};
+__device__ __forceinline__ void init_forward_pixel(ForwardPixel& p, bool inside) {
+    p.T = inside ? 1.f : -1.f; p.C0 = p.C1 = p.C2 = p.N0 = p.N1 = p.N2 = 0.f;
+    p.C3 = p.C4 = p.C5 = p.C6 = p.C7 = p.C8 = 0.f;
+    p.Dsum = p.M1 = p.M2 = p.dist = p.med = 0.f;
+    p.lastc = 0; p.medc = 0xFFFFFFFFu;
+}
+// the distortion sums of a blended pair (T: the transmittance in front of it, w = alpha T); shared with the per-class distortion pass
+__device__ __forceinline__ void distortion_step(float& dist, float& M1, float& M2, float T, float depth, float w) {
+    const float A = 1.f - T;
+    const float mm = kFN * (1.f - kNear * fast_rcp(depth));
+    dist += (mm * mm * A + M2 - 2.f * mm * M1) * w;
+    M1 += mm * w;
+    M2 += mm * mm * w;
+}
+// One live pixel and one entry that passed `intersect`.  e3..e6: the staged entry (e6: colour channels 6..8, read with NC = 9 only; by value,
+// the others by reference: the one combination that leaves the register counts of every instantiation where they were).
+template <int NC>
+__device__ __forceinline__ void blend_forward_step(ForwardPixel& p, const Hit& h, const float4& e3, const float4& e4, const float4& e5, const float4 e6, uint32_t contributor) {
+    const float test_T = p.T * (1.f - h.alpha);
+    const bool go = !(test_T < kTStop);   // else: done, and this entry is NOT blended
+    if (go) {
+        const float w = h.alpha * p.T;
+        p.Dsum += h.depth * w;
+        distortion_step(p.dist, p.M1, p.M2, p.T, h.depth, w);
+        if (p.T > 0.5f) { p.med = h.depth; p.medc = contributor; }
+        p.N0 += e4.x * w; p.N1 += e4.y * w; p.N2 += e4.z * w;
+        p.C0 += e4.w * w; p.C1 += e5.x * w; p.C2 += e5.y * w;
+        if (NC >= 6) { p.C3 += e5.z * w; p.C4 += e5.w * w; p.C5 += e3.w * w; }
+        if (NC == 9) { p.C6 += e6.x * w; p.C7 += e6.y * w; p.C8 += e6.z * w; }
+        p.lastc = contributor;
+    }
+    p.T = go ? test_T : -p.T;
+}
+// The pixel's outputs (channel order: DESIGN.md) and, final_T != NULL, the backward's per-pixel state (NULL with SR_FLAG_FORWARD_ONLY).
+template <int NC>
+__device__ __forceinline__ void store_forward_pixel(const ForwardPixel& p, const FrameDev& f, const float3 bg, size_t pix, float* __restrict__ out_color, float* __restrict__ out_allmap,
+                                                    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib) {
+    const size_t HW = (size_t)f.H * f.W;
+    const float Tq = fabsf(p.T);
+    if (final_T) {
+        final_T[pix] = Tq; final_T[HW + pix] = p.M1; final_T[2 * HW + pix] = p.M2;
+        n_contrib[pix] = p.lastc; n_contrib[HW + pix] = p.medc;
+    }
+    out_color[pix] = p.C0 + Tq * bg.x;
+    out_color[HW + pix] = p.C1 + Tq * bg.y;
+    out_color[2 * HW + pix] = p.C2 + Tq * bg.z;
+    if (NC >= 6) {
+        out_color[3 * HW + pix] = p.C3 + Tq * f.bg[3];
+        out_color[4 * HW + pix] = p.C4 + Tq * f.bg[4];
+        out_color[5 * HW + pix] = p.C5 + Tq * f.bg[5];
+    }
+    if (NC == 9) {
+        out_color[6 * HW + pix] = p.C6 + Tq * f.bg[6];
+        out_color[7 * HW + pix] = p.C7 + Tq * f.bg[7];
+        out_color[8 * HW + pix] = p.C8 + Tq * f.bg[8];
+    }
+    out_allmap[pix] = p.Dsum;
+    out_allmap[HW + pix] = 1.f - Tq;
+    out_allmap[2 * HW + pix] = p.N0; out_allmap[3 * HW + pix] = p.N1; out_allmap[4 * HW + pix] = p.N2;
+    out_allmap[5 * HW + pix] = p.med;
+    out_allmap[6 * HW + pix] = p.dist;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 // (each lane gathers one 80-B packed record with five dwordx4 loads, the next round's records are already in flight while
 // the current round is processed), and in the inner loop all 64 lanes read the same LDS address (broadcast ds_read_b128).
 // No MFMA: there is no dense contraction in this path.
+// The straight-line pieces every forward kernel here shares -- band decode, pixel state, its step per (pixel, entry) pair, its stores, the
+// hit-mask packing -- are written once in blend_common.h (ForwardPixel, blend_forward_step, ...); a kernel holds its walk.
 //
 // Staging also rewrites each record into the form the inner loop wants (tile-local coordinates, which also
 // removes the cancellation of the textbook k x l form):
@@ -37,15 +39,6 @@
 #endif
 namespace sr {
 
-// exact (entry, quadrant) hit mask for the backward: K7 visits only the pairs that reached a pixel in the forward.  16 bits per list entry;
-// two-band tiles: low byte = quadrants of the upper band, high byte = lower band (decode_hits, blend_common.h)
-template <int QX, int QY, int SPLIT>
-__device__ __forceinline__ void store_hit_mask(uint16_t* __restrict__ hit_mask, uint32_t pos, int part, uint32_t hm) {
-    if (SPLIT == 2) reinterpret_cast<uint8_t*>(hit_mask)[2 * (size_t)pos + part] = (uint8_t)hm;
-    else if (QY == 2) hit_mask[pos] = (uint16_t)((hm & ((1u << QX) - 1u)) | ((hm >> QX) << 8));
-    else hit_mask[pos] = (uint16_t)hm;
-}
-
 // ---------------------------------------------------------------------------------------------
 // K6
 // ---------------------------------------------------------------------------------------------
@@ -58,41 +51,26 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
                                                     float* __restrict__ out_color, float* __restrict__ out_allmap, float* __restrict__ final_T,
                                                     uint32_t* __restrict__ n_contrib, uint16_t* __restrict__ hit_mask, int cull, unsigned long long* __restrict__ g_stats) {
     const int lane = threadIdx.x;
-    // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2: the SPLIT bands of one tile take consecutive
-    // slots of the SAME XCD so that the second band finds the tile's records in that L2 instead of fetching them again.
-    int tile = blockIdx.x, part = 0;
-    if (SPLIT > 1) {
-        const int xcd = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
-        tile = (k / SPLIT) * kXcds + xcd; part = k % SPLIT;
-        if (tile >= f.tiles_x * f.tiles_y) return;
-    }
-    tile = (int)tile_order[tile];   // longest lists first (binning.hip tile_order_kernel)
+    Band b;
+    band_of_block<SPLIT>(b);
+    if (SPLIT > 1 && b.tile >= f.tiles_x * f.tiles_y) return;
+    band_origin<QX, QY, SPLIT>(f, tile_order, b);
     constexpr int NQ = QX * QY;   // 8x8 quadrants per wave = pixels per lane
-    const int tx0 = (tile % f.tiles_x) * (QX * 8), ty0 = (tile / f.tiles_x) * (QY * 8 * SPLIT) + part * (QY * 8);
-    // local origin = centre of the binning tile (shared with K7: identical staged values, identical decisions)
-    const float Xc = (float)(tx0 + QX * 4), Yc = (float)((tile / f.tiles_x) * (QY * 8 * SPLIT) + QY * SPLIT * 4);
-    const int yshift_px = part * (QY * 8) - QY * (SPLIT - 1) * 4;   // this band's quadrants relative to that centre
-    const float yshift = (float)yshift_px;
+    const int part = b.part, tx0 = b.tx0, ty0 = b.ty0, yshift_px = b.yshift_px;
+    const float Xc = b.Xc, Yc = b.Yc, yshift = (float)yshift_px;
     const int lx = lane & 7, ly = lane >> 3;
-    const uint2 range = ranges[tile];
+    const uint2 range = ranges[b.tile];
     const uint32_t n_total = range.y - range.x;
 
     float xl[NQ], yl[NQ];
-    // T[q] > 0: the pixel is live.  T[q] < 0: done (saturated, or outside the image) -- |T[q]| is its final transmittance.  (A separate
-    // flag per pixel costs a byte compare, two moves and a four-instruction all-done test per quadrant test.)
-    float T[NQ], C0[NQ], C1[NQ], C2[NQ], N0[NQ], N1[NQ], N2[NQ], Dsum[NQ], M1[NQ], M2[NQ], dist[NQ], med[NQ];
-    float C3[NQ], C4[NQ], C5[NQ], C6[NQ], C7[NQ], C8[NQ];   // only live in the 6- / 9-channel variants
-    uint32_t lastc[NQ], medc[NQ];
+    ForwardPixel p[NQ];
     uint32_t alive = 0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int px = tx0 + (q % QX) * 8 + lx, py = ty0 + (q / QX) * 8 + ly;
         xl[q] = (float)((q % QX) * 8 + lx - QX * 4); yl[q] = (float)((q / QX) * 8 + ly - QY * 4) + yshift;
-        T[q] = (px < f.W && py < f.H) ? 1.f : -1.f; C0[q] = C1[q] = C2[q] = N0[q] = N1[q] = N2[q] = 0.f;
-        C3[q] = C4[q] = C5[q] = C6[q] = C7[q] = C8[q] = 0.f;
-        Dsum[q] = M1[q] = M2[q] = dist[q] = med[q] = 0.f;
-        lastc[q] = 0; medc[q] = 0xFFFFFFFFu;
-        if (ballot64(T[q] > 0.f) != 0) alive |= 1u << q;
+        init_forward_pixel(p[q], px < f.W && py < f.H);
+        if (ballot64(p[q].T > 0.f) != 0) alive |= 1u << q;
     }
 
     // Memory pipeline of the walk (round 6): the list entry (gid) is requested TWO rounds ahead, the record it addresses one round ahead, and
@@ -105,7 +83,7 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
         const uint32_t gid = point_list[range.x + lane];
         load_record18(recs, gid, nr);   // (depth and radius, the record's last two floats, are not staged by the forward)
         if (NC == 6) nx = load_extra(extra, gid, 3);
-            if (NC == 9) { nx = load_extra(extra, gid, 0); ny = load_extra(extra, gid, 3); }
+        if (NC == 9) { nx = load_extra(extra, gid, 0); ny = load_extra(extra, gid, 3); }
     }
     if (kWave + (uint32_t)lane < n_total) gid_ahead = point_list[range.x + kWave + lane];
     // the hit masks of the round that ended last, not stored yet: they wait as the round's scalar ballots (no vector register across the staging)
@@ -124,12 +102,7 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
         // (the record loads are the LAST memory operations of the round: nothing needs a temporary register while their 18 destinations
         // are in flight -- at the 80-register budget the allocator otherwise moves half-arrived quads around, behind an s_waitcnt)
         const uint32_t gid = gid_ahead;
-        if (hit_mask && (uint32_t)lane < n_prev) {
-            uint32_t hm = 0;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) hm |= (uint32_t)((hit_prev[q] >> lane) & 1ull) << q;
-            store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, hm);
-        }
+        if (hit_mask && (uint32_t)lane < n_prev) store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, lane_hit_bits(hit_prev, lane));
         if (base + 2 * kWave + lane < n_total) gid_ahead = point_list[range.x + base + 2 * kWave + lane];
         __builtin_amdgcn_sched_barrier(0);
         if (base + kWave + lane < n_total) {
@@ -164,7 +137,7 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
             for (int q = 0; q < NQ; ++q) {
                 if (!(mj & (1u << q))) continue;  // wave-uniform
                 Hit h;
-                const bool valid = intersect(xl[q], yl[q], e0, e1, e2, e3, h) & (T[q] > 0.f);
+                const bool valid = intersect(xl[q], yl[q], e0, e1, e2, e3, h) & (p[q].T > 0.f);
                 if (kStats) {
                     const unsigned long long vb = ballot64(valid);
                     if (lane == 0) { atomicAdd(&g_stats[2], 1ull); if (vb) atomicAdd(&g_stats[3], 1ull); atomicAdd(&g_stats[4], (unsigned long long)__popcll(vb));
@@ -182,27 +155,9 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
                 if (ballot64(valid) == 0) continue;
                 hit[q] |= 1ull << j;
                 const float4 e4 = kColoursUpFront ? u4 : s_e[4][j], e5 = kColoursUpFront ? u5 : s_e[5][j];
-                if (valid) {
-                    const float test_T = T[q] * (1.f - h.alpha);
-                    const bool go = !(test_T < kTStop);   // else: done, and this entry is NOT blended
-                    if (go) {
-                        const float w = h.alpha * T[q];
-                        const float A = 1.f - T[q];
-                        const float mm = kFN * (1.f - kNear * fast_rcp(h.depth));
-                        dist[q] += (mm * mm * A + M2[q] - 2.f * mm * M1[q]) * w;
-                        Dsum[q] += h.depth * w;
-                        M1[q] += mm * w;
-                        M2[q] += mm * mm * w;
-                        if (T[q] > 0.5f) { med[q] = h.depth; medc[q] = contributor; }
-                        N0[q] += e4.x * w; N1[q] += e4.y * w; N2[q] += e4.z * w;
-                        C0[q] += e4.w * w; C1[q] += e5.x * w; C2[q] += e5.y * w;
-                        if (NC >= 6) { C3[q] += e5.z * w; C4[q] += e5.w * w; C5[q] += e3.w * w; }
-                        if (NC == 9) { const float4 e6 = kColoursUpFront ? u6 : s_e[6][j]; C6[q] += e6.x * w; C7[q] += e6.y * w; C8[q] += e6.z * w; }
-                        lastc[q] = contributor;
-                    }
-                    T[q] = go ? test_T : -T[q];
-                }
-                if (ballot64(T[q] > 0.f) == 0) alive &= ~(1u << q);
+                const float4 e6 = kColoursUpFront || NC != 9 ? u6 : s_e[6][j];
+                if (valid) blend_forward_step<NC>(p[q], h, e3, e4, e5, e6, contributor);
+                if (ballot64(p[q].T > 0.f) == 0) alive &= ~(1u << q);
             }
         }
         if (kStats && lane == 0) {   // [7]: entries with a contributing pixel somewhere in the tile = gradient records K7 will write
@@ -253,46 +208,16 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
             n_prev = n; base_prev = base;   // stored behind the next round's staging, or behind the walk
         }
     }
-    if (hit_mask && (uint32_t)lane < n_prev) {
-        uint32_t hm = 0;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) hm |= (uint32_t)((hit_prev[q] >> lane) & 1ull) << q;
-        store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, hm);
-    }
-    const size_t HW = (size_t)f.H * f.W;
-    const float bg0 = f.bg[0], bg1 = f.bg[1], bg2 = f.bg[2];
+    if (hit_mask && (uint32_t)lane < n_prev) store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, lane_hit_bits(hit_prev, lane));
+    const float3 bg = make_float3(f.bg[0], f.bg[1], f.bg[2]);
     int lane_again = threadIdx.x;
     asm volatile("" : "+v"(lane_again));   // the pixel coordinates are recomputed here instead of living in registers across the list walk
     const int lx2 = lane_again & 7, ly2 = lane_again >> 3;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int px = tx0 + (q % QX) * 8 + lx2, py = ty0 + (q / QX) * 8 + ly2;
-        if (px < f.W && py < f.H) {
-            const size_t pix = (size_t)py * f.W + px;
-            const float Tq = fabsf(T[q]);
-            if (final_T) {   // the backward's per-pixel state (NULL with SR_FLAG_FORWARD_ONLY)
-                final_T[pix] = Tq; final_T[HW + pix] = M1[q]; final_T[2 * HW + pix] = M2[q];
-                n_contrib[pix] = lastc[q]; n_contrib[HW + pix] = medc[q];
-            }
-            out_color[pix] = C0[q] + Tq * bg0;
-            out_color[HW + pix] = C1[q] + Tq * bg1;
-            out_color[2 * HW + pix] = C2[q] + Tq * bg2;
-            if (NC >= 6) {
-                out_color[3 * HW + pix] = C3[q] + Tq * f.bg[3];
-                out_color[4 * HW + pix] = C4[q] + Tq * f.bg[4];
-                out_color[5 * HW + pix] = C5[q] + Tq * f.bg[5];
-            }
-            if (NC == 9) {
-                out_color[6 * HW + pix] = C6[q] + Tq * f.bg[6];
-                out_color[7 * HW + pix] = C7[q] + Tq * f.bg[7];
-                out_color[8 * HW + pix] = C8[q] + Tq * f.bg[8];
-            }
-            out_allmap[pix] = Dsum[q];
-            out_allmap[HW + pix] = 1.f - Tq;
-            out_allmap[2 * HW + pix] = N0[q]; out_allmap[3 * HW + pix] = N1[q]; out_allmap[4 * HW + pix] = N2[q];
-            out_allmap[5 * HW + pix] = med[q];
-            out_allmap[6 * HW + pix] = dist[q];
-        }
+        if (px < f.W && py < f.H)
+            store_forward_pixel<NC>(p[q], f, bg, (size_t)py * f.W + px, out_color, out_allmap, final_T, n_contrib);
     }
 }
 
@@ -309,8 +234,8 @@ void render_forward_kernel(FrameDev f, const uint2* __restrict__ ranges, const u
 // ---------------------------------------------------------------------------------------------
 // K6, row-mapped (three colour channels): the wave's four 16-lane rows are the four 4x4 cells of a quadrant, and every row walks ITS
 // OWN list -- the entries of the round whose octagon reaches its cell -- so a wave step serves four different entries, one per row,
-// instead of one entry on 64 lanes of which a thin splat uses a dozen.  Same staging, same `intersect`, same per-pixel sequence of
-// operations as render_forward_kernel: bit-identical images, state and hit masks.  The rows' entry indices travel packed in one SGPR
+// instead of one entry on 64 lanes of which a thin splat uses a dozen.  Same staging, same `intersect`, same blend_forward_step
+// as render_forward_kernel: bit-identical images, state and hit masks.  The rows' entry indices travel packed in one SGPR
 // (next set bit of the row's 64-bit mask: scalar unit), every lane extracts its row's byte and reads the staged entry at ITS address.
 // ---------------------------------------------------------------------------------------------
 // kCells (round 6, the row-mapped BACKWARD's input: render_backward_rows_kernel): the hit masks are kept per (entry, 4x4 CELL) instead of per
@@ -324,34 +249,26 @@ __device__ __forceinline__ void render_forward_rows_body(float4 (*s_e)[kWave], u
                                                          float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint16_t* __restrict__ hit_mask) {
     constexpr int NC = 3;
     const int lane = threadIdx.x;
-    int tile = blockIdx.x, part = 0;
-    if (SPLIT > 1) {
-        const int xcd = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
-        tile = (k / SPLIT) * kXcds + xcd; part = k % SPLIT;
-        if (tile >= f.tiles_x * f.tiles_y) return;
-    }
-    tile = (int)tile_order[tile];
+    Band b;
+    band_of_block<SPLIT>(b);
+    if (SPLIT > 1 && b.tile >= f.tiles_x * f.tiles_y) return;
+    band_origin<QX, QY, SPLIT>(f, tile_order, b);
     constexpr int NQ = QX * QY;
-    const int tx0 = (tile % f.tiles_x) * (QX * 8), ty0 = (tile / f.tiles_x) * (QY * 8 * SPLIT) + part * (QY * 8);
-    const float Xc = (float)(tx0 + QX * 4), Yc = (float)((tile / f.tiles_x) * (QY * 8 * SPLIT) + QY * SPLIT * 4);
-    const int yshift_px = part * (QY * 8) - QY * (SPLIT - 1) * 4;
-    const float yshift = (float)yshift_px;
+    const int part = b.part, tx0 = b.tx0, ty0 = b.ty0, yshift_px = b.yshift_px;
+    const float Xc = b.Xc, Yc = b.Yc, yshift = (float)yshift_px;
     // row r = lane / 16 <-> cell (r & 1, r >> 1) of the quadrant; lane % 16 <-> pixel (l & 3, l >> 2) of the cell
     const int lx = ((lane >> 4) & 1) * 4 + (lane & 3), ly = (lane >> 5) * 4 + ((lane >> 2) & 3);
-    const uint2 range = ranges[tile];
+    const uint2 range = ranges[b.tile];
     const uint32_t n_total = range.y - range.x;
 
     const float xl0 = (float)(lx - QX * 4), yl0 = (float)(ly - QY * 4) + yshift;   // quadrant 0; quadrant q adds 8 (q % QX, q / QX)
-    float T[NQ], C0[NQ], C1[NQ], C2[NQ], N0[NQ], N1[NQ], N2[NQ], Dsum[NQ], M1[NQ], M2[NQ], dist[NQ], med[NQ];
-    uint32_t lastc[NQ], medc[NQ];
+    ForwardPixel p[NQ];
     uint32_t alive = 0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int px = tx0 + (q % QX) * 8 + lx, py = ty0 + (q / QX) * 8 + ly;
-        T[q] = (px < f.W && py < f.H) ? 1.f : -1.f; C0[q] = C1[q] = C2[q] = N0[q] = N1[q] = N2[q] = 0.f;
-        Dsum[q] = M1[q] = M2[q] = dist[q] = med[q] = 0.f;
-        lastc[q] = 0; medc[q] = 0xFFFFFFFFu;
-        if (ballot64(T[q] > 0.f) != 0) alive |= 1u << q;
+        init_forward_pixel(p[q], px < f.W && py < f.H);
+        if (ballot64(p[q].T > 0.f) != 0) alive |= 1u << q;
     }
     float4 nr[kRecQuads];
     const float4 nx = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -398,31 +315,15 @@ __device__ __forceinline__ void render_forward_rows_body(float4 (*s_e)[kWave], u
                 brow &= brow - 1ull;
                 const float4 e0 = s_e[0][j], e1 = s_e[1][j], e2 = s_e[2][j], e3 = s_e[3][j];
                 Hit h;
-                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (T[q] > 0.f) & act;
+                const bool valid = intersect(xq, yq, e0, e1, e2, e3, h) & (p[q].T > 0.f) & act;
                 if (ballot64(valid) == 0ull) continue;
                 const float4 e4 = s_e[4][j], e5 = s_e[5][j];
                 if (valid) {
                     if (kCells) s_hit[q][4 * j + (lane >> 4)] = 1; else s_hit[q][j] = 1;   // (every valid lane of the row stores the same byte)
-                    const uint32_t contributor = base + j + 1u;
-                    const float test_T = T[q] * (1.f - h.alpha);
-                    const bool go = !(test_T < kTStop);
-                    if (go) {
-                        const float w = h.alpha * T[q];
-                        const float A = 1.f - T[q];
-                        const float mm = kFN * (1.f - kNear * fast_rcp(h.depth));
-                        dist[q] += (mm * mm * A + M2[q] - 2.f * mm * M1[q]) * w;
-                        Dsum[q] += h.depth * w;
-                        M1[q] += mm * w;
-                        M2[q] += mm * mm * w;
-                        if (T[q] > 0.5f) { med[q] = h.depth; medc[q] = contributor; }
-                        N0[q] += e4.x * w; N1[q] += e4.y * w; N2[q] += e4.z * w;
-                        C0[q] += e4.w * w; C1[q] += e5.x * w; C2[q] += e5.y * w;
-                        lastc[q] = contributor;
-                    }
-                    T[q] = go ? test_T : -T[q];
+                    blend_forward_step<NC>(p[q], h, e3, e4, e5, nx, base + j + 1u);
                 }
                 // (a row whose sixteen pixels are done could drop the rest of its list: the test costs more per step than the steps it saves)
-                if (ballot64(T[q] > 0.f) == 0ull) { alive &= ~(1u << q); break; }
+                if (ballot64(p[q].T > 0.f) == 0ull) { alive &= ~(1u << q); break; }
             }
         }
         if (hit_mask) {
@@ -438,30 +339,15 @@ __device__ __forceinline__ void render_forward_rows_body(float4 (*s_e)[kWave], u
         }
     }
     if (hit_mask && (uint32_t)lane < n_prev) store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, hm_prev);
-    const size_t HW = (size_t)f.H * f.W;
-    const float bg0 = f.bg[0], bg1 = f.bg[1], bg2 = f.bg[2];
+    const float3 bg = make_float3(f.bg[0], f.bg[1], f.bg[2]);
     int lane_again = threadIdx.x;
     asm volatile("" : "+v"(lane_again));   // the pixel coordinates are recomputed here instead of living in registers across the list walk
     const int lx2 = ((lane_again >> 4) & 1) * 4 + (lane_again & 3), ly2 = (lane_again >> 5) * 4 + ((lane_again >> 2) & 3);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int px = tx0 + (q % QX) * 8 + lx2, py = ty0 + (q / QX) * 8 + ly2;
-        if (px < f.W && py < f.H) {
-            const size_t pix = (size_t)py * f.W + px;
-            const float Tq = fabsf(T[q]);
-            if (final_T) {   // the backward's per-pixel state (NULL with SR_FLAG_FORWARD_ONLY)
-                final_T[pix] = Tq; final_T[HW + pix] = M1[q]; final_T[2 * HW + pix] = M2[q];
-                n_contrib[pix] = lastc[q]; n_contrib[HW + pix] = medc[q];
-            }
-            out_color[pix] = C0[q] + Tq * bg0;
-            out_color[HW + pix] = C1[q] + Tq * bg1;
-            out_color[2 * HW + pix] = C2[q] + Tq * bg2;
-            out_allmap[pix] = Dsum[q];
-            out_allmap[HW + pix] = 1.f - Tq;
-            out_allmap[2 * HW + pix] = N0[q]; out_allmap[3 * HW + pix] = N1[q]; out_allmap[4 * HW + pix] = N2[q];
-            out_allmap[5 * HW + pix] = med[q];
-            out_allmap[6 * HW + pix] = dist[q];
-        }
+        if (px < f.W && py < f.H)
+            store_forward_pixel<NC>(p[q], f, bg, (size_t)py * f.W + px, out_color, out_allmap, final_T, n_contrib);
     }
 }
 
@@ -486,6 +372,8 @@ void render_forward_rows_kernel(FrameDev f, const uint2* __restrict__ ranges, co
 // MEASURED, and therefore only run when asked for (SR_FLAG_COOP_BACKWARD in sr_forward_render): 1.5 M Gaussians at 480x320 0.481 ms against
 // the band kernel's 0.487 (8x8 tiles: 0.37); C3 0.968 against 0.852 -- the three barriers per round make every quadrant wait for the slowest
 // one, which costs what the single staging saves.  The BACKWARD's cooperative form is the one that pays on small frames (render_bwd.hip).
+// (Its own copy of the pieces the other forward kernels take from blend_common.h: with them the 480x320 step measured 0.2 % slower,
+// outside the parent's run-to-run spread -- tools/notes_k6_shared_step.md.)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(4 * kWave) void render_forward_coop_kernel(FrameDev f, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order,
                                                                           const uint32_t* __restrict__ point_list, const float4* __restrict__ recs,

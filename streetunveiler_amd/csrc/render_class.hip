@@ -126,6 +126,7 @@ __global__ __launch_bounds__(kWave) void class_forward_kernel(FrameDev f, int n_
     __shared__ float4 s_e[entry_quads<0>()][kWave];
     const int lane = threadIdx.x;
     // the waves of one tile -- its classes, and the SPLIT bands of each (they walk the same sub-list) -- on one XCD
+    // (its own copy of band_of_block / band_origin, blend_common.h: through them class_forward_kernel<1, 1, 1> went from 72 to 62 SGPRs)
     const int xcd = blockIdx.x % kXcds;
     int k = blockIdx.x / kXcds;
     const int part = k % SPLIT; k /= SPLIT;
@@ -165,14 +166,7 @@ __global__ __launch_bounds__(kWave) void class_forward_kernel(FrameDev f, int n_
     for (int q = 0; q < NQ; ++q) hit_prev[q] = 0ull;
     uint32_t n_prev = 0, base_prev = 0;
     auto store_hits = [&]() {
-        if ((uint32_t)lane < n_prev) {
-            uint32_t hm = 0;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) hm |= (uint32_t)((hit_prev[q] >> lane) & 1ull) << q;
-            if (SPLIT == 2) reinterpret_cast<uint8_t*>(hit_mask)[2 * (size_t)(range.x + base_prev + lane) + part] = (uint8_t)hm;
-            else if (QY == 2) hit_mask[range.x + base_prev + lane] = (uint16_t)((hm & ((1u << QX) - 1u)) | ((hm >> QX) << 8));   // (decode_hits: a byte per quadrant row)
-            else hit_mask[range.x + base_prev + lane] = (uint16_t)hm;
-        }
+        if ((uint32_t)lane < n_prev) store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, lane_hit_bits(hit_prev, lane));
     };
     for (uint32_t base = 0; base < n_total && alive; base += kWave) {
         const uint32_t n = min((uint32_t)kWave, n_total - base);
@@ -208,12 +202,7 @@ __global__ __launch_bounds__(kWave) void class_forward_kernel(FrameDev f, int n_
                     if (test_T < kTStop) {
                         done |= 1u << q;  // this entry is NOT blended
                     } else {
-                        const float w = h.alpha * T[q];
-                        const float A = 1.f - T[q];
-                        const float mm = kFN * (1.f - kNear * fast_rcp(h.depth));
-                        dist[q] += (mm * mm * A + M2[q] - 2.f * mm * M1[q]) * w;
-                        M1[q] += mm * w;
-                        M2[q] += mm * mm * w;
+                        distortion_step(dist[q], M1[q], M2[q], T[q], h.depth, h.alpha * T[q]);
                         T[q] = test_T;
                         lastc[q] = contributor;
                     }

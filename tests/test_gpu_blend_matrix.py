@@ -365,3 +365,64 @@ def test_blend_instantiation_on_edge_scene(scene, config):
     if scene in FREE_F64_SCENES:
         _assert_free_f64(scene, config, out)
     _assert_cross_checks(scene, config, out)
+
+
+# ---- the 16x16 forward kernels that are not the band kernel: the same bits ---------------------------------------------------------------
+# The cooperative forward (backward_kernel="coop", culling on) and the counting variant (blend_counters; three and six channels) share the
+# band kernel's per-pixel step, initialisation, stores and hit-mask packing (csrc/blend_common.h).  On a frame that is a multiple of no tile
+# and on one whose pixels saturate: images and per-pixel state bit for bit the band kernel's, and -- the hit masks -- the one-wave backward
+# fed with the variant's state gives the band kernel's gradients bit for bit.
+FORWARD_VARIANTS = {"coop": (3, dict(backward_kernel="coop")), "counting-nc3": (3, dict(blend_counters=True)), "counting-nc6": (6, dict(blend_counters=True))}
+_BAND = {}
+
+
+def _forward_then_one_wave_backward(sc, nc, **forward_kw):
+    import diff_surfel_rasterization._C as _C
+    from tests.gpu_util import DEV, settings_for
+    g, cam = sc.g, sc.cam
+    W, H, P = cam.image_width, cam.image_height, g["means3D"].shape[0]
+    e = torch.empty(0, device=DEV)
+    d = lambda k: g[k].to(DEV)
+    bg, dc = (sc.bg9[:3], sc.dc9[:3]) if nc == 3 else (sc.bg9[3:], sc.dc9[3:])
+    s = settings_for(cam, bg, sc.deg if nc == 3 else 0)
+    sh, col = (d("shs"), e) if nc == 3 else (e, torch.as_tensor(sc.extra).to(DEV))
+    deg = sc.deg if nc == 3 else 0
+    if forward_kw.get("blend_counters"):
+        forward_kw = dict(forward_kw, blend_counters=torch.zeros(16, dtype=torch.int64, device=DEV))
+    D, color, allmap, radii, geom, binning, img = _C.rasterize_gaussians(s.bg, d("means3D"), col, d("opacities"), d("scales"), d("rotations"), 1.0, e, s.viewmatrix,
+                                                                          s.projmatrix, s.tanfovx, s.tanfovy, H, W, sh, deg, s.campos, False, False, **forward_kw)
+    if "blend_counters" in forward_kw:
+        torch.cuda.synchronize()
+        assert int(forward_kw["blend_counters"][0]) > 0, "the counting variant did not run"
+    iv = _C.image_view(img, W, H)
+    out = dict(color=color, allmap=allmap, radii=radii, final_T=iv["final_T"].clone(), n_contrib=iv["n_contrib"].clone())
+    grads = _C.rasterize_gaussians_backward(s.bg, d("means3D"), radii, col, d("scales"), d("rotations"), 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
+                                            dc.contiguous().to(DEV), sc.da.to(DEV), sh, deg, s.campos, geom, D, binning, img, False, backward_kernel="one_wave")
+    torch.cuda.synchronize()
+    out.update({f"grad{i}": t for i, t in enumerate(grads) if torch.is_tensor(t)})
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("variant", list(FORWARD_VARIANTS))
+@pytest.mark.parametrize("scene", ["ragged_bands", "opacity_extremes_2"])
+def test_forward_variant_is_bit_identical_to_the_band_kernel(scene, variant):
+    from tools.blend_pairs import _same_bits
+    from tools.edge_scenes import catalogue
+    nc, kw = FORWARD_VARIANTS[variant]
+    if _BAND.get("scene") != scene:
+        _BAND.clear()
+        _BAND.update(scene=scene, sc=catalogue()[scene]())
+    sc = _BAND["sc"]
+    if nc not in _BAND:   # the band kernel (SR_FLAG_QUADRANT_MAPPED_FORWARD), once per scene and channel count
+        _BAND[nc] = _forward_then_one_wave_backward(sc, nc, row_mapped=False)
+    band = _BAND[nc]
+    W, H = sc.cam.image_width, sc.cam.image_height
+    if scene == "ragged_bands":
+        assert W % 16 and H % 16
+    else:   # pixels that stopped at the transmittance floor (kTStop = 1e-4 of common.h) with list entries left
+        assert (band["final_T"][0] < 1e-3).mean() > 0.05, "the scene does not saturate"
+    assert band["n_contrib"].any() and np.abs(band["grad3"]).max() > 0
+    got = _forward_then_one_wave_backward(sc, nc, **kw)
+    assert set(got) == set(band)
+    for k in band:
+        assert _same_bits(got[k], band[k]), f"{scene} {variant}: {k} differs from the band kernel's"
