@@ -423,6 +423,65 @@ int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1
 int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii, float* xyz_gradient_accum, float* denom,
                            float* max_radii2D, void* stream);
 
+/* Densify-and-prune of the Gaussians and their Adam moments == GaussianModel.densify_and_prune with densify_and_clone, densify_and_split,
+ * densification_postfix, cat_tensors_to_optimizer, _prune_optimizer and prune_points of the reference (scene/gaussian_model.py:402-553),
+ * as one decision pass, one scan and one gather: every surviving row moves once.  Two calls with one host read-back between them.
+ *
+ * sr_densify_plan decides, per Gaussian i < P, in float32 (correctly rounded division; exp / log / sigmoid of the device library):
+ *     grad   = accum[i] / denom[i], NaN -> 0 (0/0 gives 0; x/0 with x > 0 stays +inf)
+ *     big    = max(exp(scaling[i][0]), exp(scaling[i][1]))                      (scaling is the raw [P,2] parameter)
+ *     clone  = |grad| >= max_grad && big <= percent_dense_extent;   split = grad >= max_grad && big > percent_dense_extent
+ *              (the reference tests the norm for the clone and the signed value for the split; accum is a sum of norms in training)
+ *     pruned = sigmoid(opacity[i]) < min_opacity || (prune_mask && prune_mask[i]) || (ws_limit >= 0 && big > ws_limit)
+ * a clone shares its parent's fate; the two children of a split parent share one, with their own scale exp(log(exp(s) / 1.6)) in the
+ * world-size test.  max_grad = +inf (or NaN) selects nothing, and only then may accum and denom be NULL: with min_opacity = -inf and
+ * ws_limit < 0 the pair of calls is a plain prune_points(prune_mask).  The reference's `max_radii2D > max_screen_size` test is not
+ * here because it never holds there: densification_postfix zeroes max_radii2D before the prune reads it; a max_screen_size only
+ * switches the world-size test on (ws_limit = 0.1 * extent, else negative).
+ * It leaves in the workspace (sr_densify_workspace_bytes(P) bytes, device memory, 256-B aligned):
+ *     offset 0                          uint8  flags[P]        SR_DENSIFY_FLAG_* bits
+ *     offset align256(P)                uint32 source_map[2P]  per OUTPUT row: source index | kind << 30 (SR_DENSIFY_KIND_*)
+ *     offset align256(P) + align256(8P) uint32 child_rank[P]   per kept child pair: its parent's rank among the split-selected
+ * and returns counts_out[4] = {kept originals K, kept clones C, split-selected S, kept child pairs H} (host memory; the call waits for
+ * the stream once).  Output order: the K surviving originals that were not split in index order, the C surviving clones, the H
+ * surviving first children, the H surviving second children: P_out = K + C + 2 H rows.  Exclusive scans, no atomics: deterministic.
+ *
+ * sr_densify_apply gathers up to SR_DENSIFY_MAX_SEGMENTS tensors of row_words 32-bit words per row from src [P rows] to dst [P_out rows]
+ * in one launch, each tensor walked as a flat stream of output words.  Roles:
+ *     COPY     every row is its source row, bit for bit (parameters of clones and children, int32 rows)
+ *     MOMENT   an original's row is copied, a new row (clone, child) is zeros
+ *     XYZ      row_words == 3; a child's row is R(rotation / |rotation|) (exp(s0) n0, exp(s1) n1, 0) + xyz with (n0, n1) = noise row
+ *              k * S + j of noise[2S,2] for child k of the j-th split-selected Gaussian; rotation [P,4], scaling [P,2]: the SOURCE arrays
+ *     SCALING  row_words == 2; a child's value is log(exp(s) / 1.6)
+ * row_words == 0 is legal and moves nothing; row_words <= 65535.  counts are the four words sr_densify_plan returned for this workspace.
+ * Both calls check every argument before their first HIP call, run on the caller's stream and allocate nothing; P == 0 is no error and
+ * no work; P < 2^30.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+#define SR_DENSIFY_MAX_SEGMENTS 8
+#define SR_DENSIFY_FLAG_CLONE 1
+#define SR_DENSIFY_FLAG_SPLIT 2
+#define SR_DENSIFY_FLAG_KEEP_SELF 4   /* the row itself survives (never set on a split parent); its clone, if any, survives with it */
+#define SR_DENSIFY_FLAG_KEEP_CHILD 8  /* split, and both children survive */
+#define SR_DENSIFY_KIND_ORIGINAL 0
+#define SR_DENSIFY_KIND_CLONE 1
+#define SR_DENSIFY_KIND_CHILD0 2
+#define SR_DENSIFY_KIND_CHILD1 3
+#define SR_DENSIFY_ROLE_COPY 0
+#define SR_DENSIFY_ROLE_MOMENT 1
+#define SR_DENSIFY_ROLE_XYZ 2
+#define SR_DENSIFY_ROLE_SCALING 3
+typedef struct SrDensifySegment {
+    const void* src;     /* [P, row_words] 32-bit words */
+    void* dst;           /* [P_out, row_words] */
+    int32_t row_words;
+    int32_t role;        /* SR_DENSIFY_ROLE_* */
+} SrDensifySegment;
+size_t sr_densify_workspace_bytes(int32_t P);
+int sr_densify_plan(int32_t P, const float* accum, const float* denom, const float* opacity, const float* scaling, float max_grad,
+                    float min_opacity, float percent_dense_extent, float ws_limit, const uint8_t* prune_mask, void* workspace,
+                    size_t workspace_bytes, uint32_t* counts_out, void* stream);
+int sr_densify_apply(int32_t P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+                     const SrDensifySegment* segments, int32_t n_segments, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

@@ -9,10 +9,11 @@ __version__ = "0.1.0"
 _IMAGE_LOSS = ("photometric_loss", "photometric_loss_torch", "image_loss_forward", "image_loss_backward", "image_loss_workspace")
 _OPTIM = ("SurfelAdam", "adam_step", "adam_step_float64", "densification_stats", "densification_stats_torch")
 _CLUSTER = ("radius_components", "cluster_instance_with_mask", "cluster_semantic_instance")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER)
+_DENSIFY = ("densify_and_prune", "prune_points", "densify_and_prune_tensors", "densify_and_prune_torch")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY)
 
 
-def __getattr__(name):   # the fused image loss, the optimizer step and the radius clustering, imported on first use (this package does not import torch by itself)
+def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering and densify / prune, imported on first use (this package does not import torch by itself)
     if name in _IMAGE_LOSS:
         from . import image_loss
         return getattr(image_loss, name)
@@ -22,4 +23,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step and the radi
     if name in _CLUSTER:
         from . import cluster
         return getattr(cluster, name)
+    if name in _DENSIFY:
+        from . import densify
+        return getattr(densify, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

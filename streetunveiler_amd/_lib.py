@@ -70,12 +70,23 @@ class SrAdamSegment(C.Structure):
 SR_ADAM_MAX_SEGMENTS, SR_ADAM_CHUNK = 8, 4096
 
 
+class SrDensifySegment(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int32), ("role", C.c_int32)]
+
+
+SR_DENSIFY_MAX_SEGMENTS = 8
+SR_DENSIFY_FLAG_CLONE, SR_DENSIFY_FLAG_SPLIT, SR_DENSIFY_FLAG_KEEP_SELF, SR_DENSIFY_FLAG_KEEP_CHILD = 1, 2, 4, 8
+SR_DENSIFY_KIND_ORIGINAL, SR_DENSIFY_KIND_CLONE, SR_DENSIFY_KIND_CHILD0, SR_DENSIFY_KIND_CHILD1 = 0, 1, 2, 3
+SR_DENSIFY_ROLE_COPY, SR_DENSIFY_ROLE_MOMENT, SR_DENSIFY_ROLE_XYZ, SR_DENSIFY_ROLE_SCALING = 0, 1, 2, 3
+
+
 # every symbol include/surfel_raster.h declares (checked by tests/test_abi.py)
 EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_error", "sr_geom_bytes", "sr_binning_bytes", "sr_image_bytes",
            "sr_backward_workspace_bytes", "sr_geom_view", "sr_binning_view", "sr_image_view", "sr_forward_plan", "sr_sh_gradient_expand", "sr_knn_workspace_bytes", "sr_knn_mean_dist2",
            "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
            "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
-           "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius"]
+           "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius",
+           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply"]
 
 _lib = None
 
@@ -161,6 +172,12 @@ def load():
     lib.sr_image_loss_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5
     lib.sr_adam_step.argtypes = [C.POINTER(SrAdamSegment), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.sr_densification_stats.argtypes = [C.c_int32] + [C.c_void_p] * 6
+    lib.sr_densify_workspace_bytes.argtypes = [C.c_int32]
+    lib.sr_densify_workspace_bytes.restype = C.c_size_t
+    lib.sr_densify_plan.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                                      C.POINTER(C.c_uint32), C.c_void_p]
+    lib.sr_densify_apply.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrDensifySegment),
+                                     C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.sr_debug_radix_sort_temp_bytes.argtypes = [C.c_uint32]
     lib.sr_debug_radix_sort_temp_bytes.restype = C.c_size_t
     lib.sr_debug_radix_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]

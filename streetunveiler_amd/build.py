@@ -37,6 +37,7 @@ SOURCES = [
     ("optimizer.hip", ["-ffp-contract=off"]),   # the Adam step's operation order is the one torch's single-tensor path states
     ("knn.hip", ["-ffp-contract=off"]),         # squared distances bit-identical to the brute-force oracle
     ("cluster.hip", ["-ffp-contract=off"]),     # the distance predicate is bit-identical to the float32 expression it restates
+    ("densify.hip", ["-ffp-contract=off"]),     # the order of the child position and the child scale is what the tests hold
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -77,7 +77,8 @@ int debug_sync(const SrFrame* frame, hipStream_t s, const char* what) {
 }
 
 // One 64-B pinned host block per calling thread (with one event per (thread, device) the only things this library keeps): word 0 =
-// the DMA target of the num_rendered read-back, word 8 = the result word of the rank self-check.
+// the DMA target of the num_rendered read-back, words 4..7 = the four counts of sr_densify_plan, word 8 = the result word of the rank
+// self-check.
 // (portable + mapped: valid on every device of the process, whichever is current when the thread first calls in.  Never freed: 64 B per
 // calling thread, and a destructor at thread / process exit could run after the HIP runtime has been torn down.)
 uint32_t* pinned_words() {
@@ -1013,6 +1014,68 @@ int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t
     if (((uintptr_t)viewspace_grad | (uintptr_t)radii | (uintptr_t)xyz_gradient_accum | (uintptr_t)denom | (uintptr_t)max_radii2D) & 3u)
         return fail(SR_ERR_INVALID_ARGUMENT, "viewspace_grad / radii / xyz_gradient_accum / denom / max_radii2D: a pointer is not 4-B aligned");
     SR_HIP(launch_densification_stats(P, viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+size_t sr_densify_workspace_bytes(int32_t P) { return densify_workspace_bytes(P > 0 ? P : 0); }
+
+int sr_densify_plan(int32_t P, const float* accum, const float* denom, const float* opacity, const float* scaling, float max_grad,
+                    float min_opacity, float percent_dense_extent, float ws_limit, const uint8_t* prune_mask, void* workspace,
+                    size_t workspace_bytes, uint32_t* counts_out, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (!counts_out) return fail(SR_ERR_INVALID_ARGUMENT, "counts_out is NULL");
+    counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    if (P == 0) return SR_OK;
+    if (P >= (1 << 30)) return fail(SR_ERR_UNSUPPORTED, "P = %d: the source map holds 30-bit indices", P);
+    DensifyRule rule{max_grad, min_opacity, percent_dense_extent, ws_limit, max_grad < INFINITY ? 1 : 0};   // (NaN: not below +inf)
+    if (rule.select && (!accum || !denom)) return fail(SR_ERR_INVALID_ARGUMENT, "accum / denom is NULL (only a max_grad of +inf goes without them)");
+    if (!opacity || !scaling) return fail(SR_ERR_INVALID_ARGUMENT, "opacity / scaling is NULL");
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < densify_workspace_bytes(P))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, densify_workspace_bytes(P));
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // K, C, S and H travel like sr_forward_plan's D: the totals kernel stores them into the calling thread's pinned words when those are
+    // mapped into the device's address space, else a DMA copy fetches them; the host waits for the stream once.
+    uint32_t* pinned = pinned_words();
+    uint32_t* pinned_dev = nullptr;
+    if (pinned && hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0) != hipSuccess) { pinned_dev = nullptr; (void)hipGetLastError(); }
+    SR_HIP(densify_plan(P, accum, denom, opacity, scaling, rule, prune_mask, workspace, pinned_dev ? pinned_dev + 4 : nullptr, s));
+    uint32_t* target = pinned ? pinned + 4 : counts_out;
+    if (!pinned_dev) SR_HIP(hipMemcpyAsync(target, densify_counts_device(P, workspace), 16, hipMemcpyDeviceToHost, s));
+    SR_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < 4; ++k) counts_out[k] = reinterpret_cast<volatile uint32_t*>(target)[k];
+    return SR_OK;
+}
+
+int sr_densify_apply(int32_t P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+                     const SrDensifySegment* segments, int32_t n_segments, void* workspace, size_t workspace_bytes, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if (n_segments < 0 || n_segments > SR_DENSIFY_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 0..%d", n_segments, SR_DENSIFY_MAX_SEGMENTS);
+    if (n_segments > 0 && !segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    const uint64_t K = counts[0], C = counts[1], S = counts[2], H = counts[3];
+    if (C > K || H > S || K + S > (uint64_t)P)
+        return fail(SR_ERR_INVALID_ARGUMENT, "counts {%u, %u, %u, %u} are not those of a plan over %d Gaussians", counts[0], counts[1], counts[2], counts[3], P);
+    const bool rows = K + C + 2 * H > 0;
+    for (int k = 0; k < n_segments; ++k) {
+        const SrDensifySegment& a = segments[k];
+        if (a.role < SR_DENSIFY_ROLE_COPY || a.role > SR_DENSIFY_ROLE_SCALING) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: unknown role %d", k, a.role);
+        if (a.row_words < 0 || a.row_words > 65535) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: row_words %d not in 0..65535", k, a.row_words);
+        if (a.role == SR_DENSIFY_ROLE_XYZ && a.row_words != 3) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the xyz role takes rows of 3 words, not %d", k, a.row_words);
+        if (a.role == SR_DENSIFY_ROLE_SCALING && a.row_words != 2) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the scaling role takes rows of 2 words, not %d", k, a.row_words);
+        if (a.row_words == 0 || !rows) continue;
+        if (!a.src || !a.dst) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: src / dst is NULL", k);
+        if (((uintptr_t)a.src | (uintptr_t)a.dst) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: src / dst is not 4-B aligned", k);
+        if (a.role == SR_DENSIFY_ROLE_XYZ && H > 0 && (!noise || !rotation || !scaling))
+            return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the xyz role needs noise, rotation and scaling when children survive", k);
+    }
+    if (P == 0 || !rows || n_segments == 0) return SR_OK;
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < densify_workspace_bytes(P))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, densify_workspace_bytes(P));
+    SR_HIP(densify_apply(P, counts, noise, rotation, scaling, segments, n_segments, workspace, static_cast<hipStream_t>(stream)));
     return SR_OK;
 }
 

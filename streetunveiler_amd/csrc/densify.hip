@@ -1,0 +1,269 @@
+// densify.hip -- the densify-and-prune step of the reference (scene/gaussian_model.py:402-553: densify_and_prune, densify_and_clone,
+// densify_and_split, densification_postfix, cat_tensors_to_optimizer, _prune_optimizer, prune_points) as one decision pass, one scan
+// and one gather (include/surfel_raster.h states the semantics):
+//   densify_decide_kernel   one thread per Gaussian: the flag byte (clone, split, keep-self, keep-child) + the four counts of its block
+//   densify_totals_kernel   exclusive scan of the block counts (one block); the four totals go to the host's pinned words
+//   densify_map_kernel      the scans inside each block again, from the flag bytes: every OUTPUT row's source index and kind
+//   densify_gather_kernel   up to 8 tensors per launch, each walked as a flat stream of 32-bit output words
+// No atomics anywhere: equal inputs give equal bits.  Built with -ffp-contract=off: the order of the child position and the child scale
+// below is the one that runs; the quotient accum / denom, 1 / norm and exp(s) / 1.6 are correctly rounded IEEE divisions.
+#include <cmath>
+
+#include "launch.h"
+
+namespace sr {
+
+constexpr int kDfThreads = 256;               // Gaussians per block of the decision and the map kernel
+constexpr int kDfChunkWords = 4096;           // output words of one tensor a workgroup of the gather handles per iteration
+constexpr int kDfMaxBlocks = 4096;            // 256 CUs x 16 workgroups; the rest is grid-strided
+constexpr uint32_t kDfIndexMask = 0x3FFFFFFFu;
+
+struct DensifyLayout {
+    size_t flags, map, child_rank, totals, total;
+    int nblocks;
+};
+static DensifyLayout densify_layout(int P) {
+    DensifyLayout L;
+    const size_t n = P > 0 ? (size_t)P : 0;
+    L.nblocks = (int)((n + kDfThreads - 1) / kDfThreads);
+    L.flags = 0;
+    L.map = align_up(n, 256);
+    L.child_rank = L.map + align_up(8 * n, 256);
+    L.totals = L.child_rank + align_up(4 * n, 256);
+    L.total = L.totals + align_up(16 * ((size_t)L.nblocks + 1), 256);
+    return L;
+}
+size_t densify_workspace_bytes(int P) { return densify_layout(P).total; }
+
+// ---- decision ------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float max_like_torch(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }   // torch.max keeps a NaN
+__device__ __forceinline__ float child_scale(float s) { return logf(__fdiv_rn(expf(s), 1.6f)); }
+
+__device__ __forceinline__ uint32_t densify_flags(int i, const float* __restrict__ accum, const float* __restrict__ denom,
+                                                  const float* __restrict__ opacity, const float* __restrict__ scaling,
+                                                  const uint8_t* __restrict__ prune_mask, const DensifyRule& r) {
+    bool clone_selected = false, split_selected = false;   // [REF] the clone tests torch.norm(grads), the split the signed padded_grad
+    if (r.select) {
+        float g = __fdiv_rn(accum[i], denom[i]);
+        if (g != g) g = 0.f;
+        clone_selected = fabsf(g) >= r.max_grad;
+        split_selected = g >= r.max_grad;
+    }
+    const float s0 = scaling[2 * (size_t)i], s1 = scaling[2 * (size_t)i + 1];
+    const float big = max_like_torch(expf(s0), expf(s1));
+    const bool clone = clone_selected && big <= r.percent_dense_extent;
+    const bool split = split_selected && big > r.percent_dense_extent;
+    const float alpha = __fdiv_rn(1.f, 1.f + expf(-opacity[i]));
+    const bool pruned = alpha < r.min_opacity || (prune_mask && prune_mask[i]);
+    const bool world = r.ws_limit >= 0.f;
+    const bool self_pruned = pruned || (world && big > r.ws_limit);
+    const float child_big = max_like_torch(expf(child_scale(s0)), expf(child_scale(s1)));
+    const bool child_pruned = pruned || (world && child_big > r.ws_limit);
+    return (clone ? SR_DENSIFY_FLAG_CLONE : 0u) | (split ? SR_DENSIFY_FLAG_SPLIT : 0u) |
+           (!split && !self_pruned ? SR_DENSIFY_FLAG_KEEP_SELF : 0u) | (split && !child_pruned ? SR_DENSIFY_FLAG_KEEP_CHILD : 0u);
+}
+
+// the four things that are counted, one byte each: kept originals | kept clones | split-selected | kept child pairs (a wave holds 64)
+__device__ __forceinline__ uint32_t packed_counts(uint32_t f) {
+    const uint32_t keep = (f >> 2) & 1u;
+    return keep | ((keep & f) << 8) | (((f >> 1) & 1u) << 16) | (((f >> 3) & 1u) << 24);
+}
+__device__ __forceinline__ uint4 unpack_counts(uint32_t p) { return make_uint4(p & 255u, (p >> 8) & 255u, (p >> 16) & 255u, p >> 24); }
+__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+__global__ __launch_bounds__(kDfThreads) void densify_decide_kernel(int P, const float* __restrict__ accum, const float* __restrict__ denom,
+                                                                    const float* __restrict__ opacity, const float* __restrict__ scaling,
+                                                                    const uint8_t* __restrict__ prune_mask, const DensifyRule rule,
+                                                                    uint8_t* __restrict__ flags, uint4* __restrict__ block_total) {
+    __shared__ uint32_t s_w[kDfThreads / 64];
+    const int tid = threadIdx.x, i = blockIdx.x * kDfThreads + tid;
+    uint32_t f = 0;
+    if (i < P) {
+        f = densify_flags(i, accum, denom, opacity, scaling, prune_mask, rule);
+        flags[i] = (uint8_t)f;
+    }
+    const uint32_t incl = wave_inclusive_scan(packed_counts(f));
+    if ((tid & 63) == 63) s_w[tid >> 6] = incl;
+    __syncthreads();
+    if (tid == 0) {
+        uint4 t = make_uint4(0, 0, 0, 0);
+        for (int k = 0; k < kDfThreads / 64; ++k) t = add4(t, unpack_counts(s_w[k]));
+        block_total[blockIdx.x] = t;
+    }
+}
+
+// exclusive scan of block_total[0 .. nblocks) in place, one block; block_total[nblocks] = the four totals, also stored straight into the
+// caller's pinned host words when given
+__global__ __launch_bounds__(kDfThreads) void densify_totals_kernel(uint4* __restrict__ block_total, int nblocks, uint4* __restrict__ total_host) {
+    __shared__ uint4 s_w[kDfThreads / 64];
+    __shared__ uint4 s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) s_carry = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    for (int c = 0; c < nblocks; c += kDfThreads) {
+        const int i = c + tid;
+        const uint4 x = i < nblocks ? block_total[i] : make_uint4(0, 0, 0, 0);
+        const uint4 incl = make_uint4(wave_inclusive_scan(x.x), wave_inclusive_scan(x.y), wave_inclusive_scan(x.z), wave_inclusive_scan(x.w));
+        if (lane == 63) s_w[w] = incl;
+        __syncthreads();
+        uint4 off = s_carry;
+        for (int k = 0; k < w; ++k) off = add4(off, s_w[k]);
+        const uint4 mine = add4(off, incl);
+        if (i < nblocks) block_total[i] = make_uint4(mine.x - x.x, mine.y - x.y, mine.z - x.z, mine.w - x.w);
+        __syncthreads();
+        if (tid == kDfThreads - 1) s_carry = mine;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        block_total[nblocks] = s_carry;
+        if (total_host) *total_host = s_carry;
+    }
+}
+
+__global__ __launch_bounds__(kDfThreads) void densify_map_kernel(int P, const uint8_t* __restrict__ flags, const uint4* __restrict__ block_base,
+                                                                 int nblocks, uint32_t* __restrict__ map, uint32_t* __restrict__ child_rank) {
+    __shared__ uint32_t s_w[kDfThreads / 64];
+    const int tid = threadIdx.x, w = tid >> 6, i = blockIdx.x * kDfThreads + tid;
+    const uint32_t f = i < P ? flags[i] : 0u;
+    const uint32_t packed = packed_counts(f);
+    const uint32_t incl = wave_inclusive_scan(packed);
+    if ((tid & 63) == 63) s_w[w] = incl;
+    __syncthreads();
+    uint4 at = add4(block_base[blockIdx.x], unpack_counts(incl - packed));
+    for (int k = 0; k < w; ++k) at = add4(at, unpack_counts(s_w[k]));
+    const uint4 total = block_base[nblocks];   // K, C, S, H
+    if (f & SR_DENSIFY_FLAG_KEEP_SELF) {
+        map[at.x] = (uint32_t)i;
+        if (f & SR_DENSIFY_FLAG_CLONE) map[total.x + at.y] = (uint32_t)i | ((uint32_t)SR_DENSIFY_KIND_CLONE << 30);
+    }
+    if (f & SR_DENSIFY_FLAG_KEEP_CHILD) {
+        const uint32_t first = total.x + total.y + at.w;
+        map[first] = (uint32_t)i | ((uint32_t)SR_DENSIFY_KIND_CHILD0 << 30);
+        map[first + total.w] = (uint32_t)i | ((uint32_t)SR_DENSIFY_KIND_CHILD1 << 30);
+        child_rank[at.w] = at.z;
+    }
+}
+
+hipError_t densify_plan(int P, const float* accum, const float* denom, const float* opacity, const float* scaling, const DensifyRule& rule,
+                        const uint8_t* prune_mask, void* workspace, uint32_t* counts_pinned_dev, hipStream_t s) {
+    const DensifyLayout L = densify_layout(P);
+    char* ws = static_cast<char*>(workspace);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(ws + L.flags);
+    uint4* totals = reinterpret_cast<uint4*>(ws + L.totals);
+    hipLaunchKernelGGL(densify_decide_kernel, dim3(L.nblocks), dim3(kDfThreads), 0, s, P, accum, denom, opacity, scaling, prune_mask, rule, flags, totals);
+    hipLaunchKernelGGL(densify_totals_kernel, dim3(1), dim3(kDfThreads), 0, s, totals, L.nblocks, reinterpret_cast<uint4*>(counts_pinned_dev));
+    hipLaunchKernelGGL(densify_map_kernel, dim3(L.nblocks), dim3(kDfThreads), 0, s, P, flags, totals, L.nblocks,
+                       reinterpret_cast<uint32_t*>(ws + L.map), reinterpret_cast<uint32_t*>(ws + L.child_rank));
+    return hipGetLastError();
+}
+
+const uint32_t* densify_counts_device(int P, const void* workspace) {
+    const DensifyLayout L = densify_layout(P);
+    return reinterpret_cast<const uint32_t*>(static_cast<const char*>(workspace) + L.totals + 16 * (size_t)L.nblocks);
+}
+
+// ---- gather --------------------------------------------------------------------------------------------------------------------------
+struct GatherSeg {
+    const uint32_t* src;
+    uint32_t* dst;
+    uint32_t row_words;
+    uint32_t magic;            // floor(2^32 / row_words) + 1: __umulhi(e, magic) == e / row_words for e < 65536 (row_words >= 2)
+    uint32_t role;
+    uint32_t rows_per_chunk;
+    uint32_t first_chunk;      // chunks of the launch in front of this tensor; 0xFFFFFFFF for an unused slot
+};
+struct GatherTable {
+    GatherSeg seg[SR_DENSIFY_MAX_SEGMENTS];
+    uint32_t total_chunks;
+    uint32_t rows_out;         // K + C + 2 H
+    uint32_t child_base;       // K + C: the output row of the first child
+    uint32_t n_split, n_child; // S, H
+    const uint32_t* map;
+    const uint32_t* child_rank;
+    const float* noise;
+    const float* rotation;
+    const float* scaling;
+};
+
+// [REF densify_and_split + utils/general_utils.py build_rotation] component `col` of R(q / |q|) (exp(s0) n0, exp(s1) n1, 0) + xyz
+__device__ __forceinline__ float child_position(const GatherTable& t, const float* __restrict__ xyz, uint32_t parent, uint32_t child, uint32_t row,
+                                                uint32_t col) {
+    const uint32_t j = t.child_rank[row - t.child_base - child * t.n_child];
+    const size_t at = 2 * ((size_t)child * t.n_split + j);
+    const float v0 = expf(t.scaling[2 * (size_t)parent]) * t.noise[at], v1 = expf(t.scaling[2 * (size_t)parent + 1]) * t.noise[at + 1];
+    const float* q = t.rotation + 4 * (size_t)parent;
+    const float norm = __fsqrt_rn(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const float r = __fdiv_rn(q[0], norm), x = __fdiv_rn(q[1], norm), y = __fdiv_rn(q[2], norm), z = __fdiv_rn(q[3], norm);
+    float a, b;
+    if (col == 0) { a = 1.f - 2.f * (y * y + z * z); b = 2.f * (x * y - r * z); }
+    else if (col == 1) { a = 2.f * (x * y + r * z); b = 1.f - 2.f * (x * x + z * z); }
+    else { a = 2.f * (x * z - r * y); b = 2.f * (y * z + r * x); }
+    return (a * v0 + b * v1) + xyz[3 * (size_t)parent + col];
+}
+
+__global__ __launch_bounds__(kDfThreads) void densify_gather_kernel(const GatherTable t) {
+    for (uint32_t c = blockIdx.x; c < t.total_chunks; c += gridDim.x) {
+        GatherSeg s = t.seg[0];
+#pragma unroll
+        for (int k = 1; k < SR_DENSIFY_MAX_SEGMENTS; ++k)
+            if (c >= t.seg[k].first_chunk) s = t.seg[k];   // first_chunk ascends; unused slots hold 0xFFFFFFFF
+        const uint32_t row0 = (c - s.first_chunk) * s.rows_per_chunk;
+        const uint32_t left = t.rows_out - row0;
+        const uint32_t n = (left < s.rows_per_chunk ? left : s.rows_per_chunk) * s.row_words;   // < 65536
+        uint32_t* __restrict__ out = s.dst + (size_t)row0 * s.row_words;
+        for (uint32_t e = threadIdx.x; e < n; e += kDfThreads) {
+            const uint32_t local = s.row_words == 1u ? e : __umulhi(e, s.magic);
+            const uint32_t col = e - local * s.row_words;
+            const uint32_t m = t.map[row0 + local];
+            const uint32_t parent = m & kDfIndexMask, kind = m >> 30;
+            uint32_t value;
+            if (kind == SR_DENSIFY_KIND_ORIGINAL || s.role == SR_DENSIFY_ROLE_COPY || (kind == SR_DENSIFY_KIND_CLONE && s.role != SR_DENSIFY_ROLE_MOMENT))
+                value = s.src[(size_t)parent * s.row_words + col];
+            else if (s.role == SR_DENSIFY_ROLE_MOMENT)
+                value = 0u;
+            else if (s.role == SR_DENSIFY_ROLE_SCALING)
+                value = __float_as_uint(child_scale(__uint_as_float(s.src[(size_t)parent * s.row_words + col])));
+            else
+                value = __float_as_uint(child_position(t, reinterpret_cast<const float*>(s.src), parent, kind - SR_DENSIFY_KIND_CHILD0, row0 + local, col));
+            out[e] = value;
+        }
+    }
+}
+
+hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+                         const SrDensifySegment* segments, int n_segments, const void* workspace, hipStream_t stream) {
+    const DensifyLayout L = densify_layout(P);
+    const char* ws = static_cast<const char*>(workspace);
+    GatherTable t{};
+    t.rows_out = counts[0] + counts[1] + 2 * counts[3];
+    t.child_base = counts[0] + counts[1];
+    t.n_split = counts[2];
+    t.n_child = counts[3];
+    t.map = reinterpret_cast<const uint32_t*>(ws + L.map);
+    t.child_rank = reinterpret_cast<const uint32_t*>(ws + L.child_rank);
+    t.noise = noise; t.rotation = rotation; t.scaling = scaling;
+    unsigned long long chunks = 0;
+    int used = 0;
+    for (int k = 0; k < n_segments && t.rows_out > 0; ++k) {
+        const SrDensifySegment& a = segments[k];
+        if (a.row_words == 0) continue;
+        GatherSeg& s = t.seg[used++];
+        s.src = static_cast<const uint32_t*>(a.src);
+        s.dst = static_cast<uint32_t*>(a.dst);
+        s.row_words = (uint32_t)a.row_words;
+        s.magic = a.row_words >= 2 ? (uint32_t)(0x100000000ull / (uint32_t)a.row_words) + 1u : 0u;
+        s.role = (uint32_t)a.role;
+        s.rows_per_chunk = a.row_words <= kDfChunkWords ? (uint32_t)(kDfChunkWords / a.row_words) : 1u;
+        s.first_chunk = (uint32_t)chunks;
+        chunks += (t.rows_out + s.rows_per_chunk - 1) / s.rows_per_chunk;
+    }
+    if (chunks == 0) return hipSuccess;
+    if (chunks >= 0xFFFFFFFFull) return hipErrorInvalidValue;   // (8 tensors of 2^31 rows: beyond P < 2^30)
+    for (int k = used; k < SR_DENSIFY_MAX_SEGMENTS; ++k) t.seg[k].first_chunk = 0xFFFFFFFFu;
+    t.total_chunks = (uint32_t)chunks;
+    const uint32_t grid = t.total_chunks < (uint32_t)kDfMaxBlocks ? t.total_chunks : (uint32_t)kDfMaxBlocks;
+    hipLaunchKernelGGL(densify_gather_kernel, dim3(grid), dim3(kDfThreads), 0, stream, t);
+    return hipGetLastError();
+}
+
+}  // namespace sr

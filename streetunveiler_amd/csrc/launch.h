@@ -1,7 +1,7 @@
 // launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
-// Host-only: nothing in here is a kernel parameter except PostCam and LossImages, which their kernels take by value.
+// Host-only: nothing in here is a kernel parameter except PostCam, LossImages and DensifyRule, which their kernels take by value.
 #pragma once
 #include "common.h"
 
@@ -153,5 +153,18 @@ bool adam_supported(const SrAdamSegment* segments, int n_segments);
 hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t s);
 hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
                                       float* max_radii2D, hipStream_t s);
+
+// ---- densify.hip ---------------------------------------------------------------------------------------------------------------------
+struct DensifyRule {   // a kernel parameter, by value
+    float max_grad, min_opacity, percent_dense_extent, ws_limit;   // ws_limit < 0: no world-size test
+    int select;        // 0: nothing is clone- or split-selected and accum / denom are not read (max_grad is +inf or NaN)
+};
+size_t densify_workspace_bytes(int P);
+// counts_pinned_dev: the device address of four pinned host words the totals kernel stores K, C, S, H into, or NULL
+hipError_t densify_plan(int P, const float* accum, const float* denom, const float* opacity, const float* scaling, const DensifyRule& rule,
+                        const uint8_t* prune_mask, void* workspace, uint32_t* counts_pinned_dev, hipStream_t s);
+const uint32_t* densify_counts_device(int P, const void* workspace);   // the same four words inside the workspace
+hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+                         const SrDensifySegment* segments, int n_segments, const void* workspace, hipStream_t s);
 
 }  // namespace sr
