@@ -482,6 +482,47 @@ int sr_densify_plan(int32_t P, const float* accum, const float* denom, const flo
 int sr_densify_apply(int32_t P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
                      const SrDensifySegment* segments, int32_t n_segments, void* workspace, size_t workspace_bytes, void* stream);
 
+/* TSDF fusion of rendered depth maps on a list of samples or on a regular grid (csrc/tsdf.hip): what the reference's unbounded mesh
+ * export evaluates on its marching-cubes samples (utils/mesh_utils.py:181-234, compute_sdf_perframe + compute_unbounded_tsdf), one thread
+ * per sample with the loop over the V views inside the kernel.
+ * Per sample tsdf = 1, weight = 1, rgb = 0 to begin with (the reference's start values: its running average begins with a phantom
+ * observation of +1); then per view v in view order:
+ *     q = [x y z 1] full_proj[v] (row vector times matrix), zc = q.w, pix = q.xy / zc;
+ *     the view is skipped unless -1 < pix.x < 1, -1 < pix.y < 1 and zc > 0 (strict; a NaN is false);
+ *     depth (and colour) = grid_sample(bilinear, align_corners = True) at pix: ix = (pix.x + 1) / 2 * (W - 1), the four taps summed in the
+ *     order nw, ne, sw, se; an in-bounds tap is multiplied in even with weight 0, a tap with an index out of bounds is not read;
+ *     sdf = depth - zc; the view is skipped unless sdf > -trunc (a NaN is false); else, with s = clamp(sdf / trunc, -1, 1):
+ *     tsdf = (tsdf w + s) / (w + 1), rgb = (rgb w + colour) / (w + 1), w += 1.
+ * trunc = (float)(5 voxel_size).  With space.contract the sample y is in contracted space: its world point is
+ * uncontract(y) radius + center, uncontract(y) = y for |y| < 1, else 1 / (2 - |y|) * (y / |y|); that point is what is projected, and
+ * trunc is multiplied by 1 / (2 - min(|world point|, 1.9)) where |world point| > 1 -- the norm of the un-normalised world point, as the
+ * reference's line 201 takes it.
+ * views.channels == 1: maps is [V,H,W] depths and rgb must be NULL; views.channels == 4: maps is [V,H,W,4] records (depth, r, g, b),
+ * 16-B aligned, one load per tap.  Outputs: tsdf [n], rgb [n,3] or NULL, weight [n] or NULL (weight - 1 = the views that integrated the
+ * sample).  All offsets into maps are 64-bit.
+ * sr_tsdf_fuse reads n samples [n,3].  sr_tsdf_fuse_grid generates them: sample (ix, iy, iz) of a dims[0] x dims[1] x dims[2] grid is
+ * fmaf(i, step[axis], lo[axis]) per axis, for ix in [ix_begin, ix_end); the outputs hold (ix_end - ix_begin) dims[1] dims[2] samples,
+ * sample (ix, iy, iz) at ((ix - ix_begin) dims[1] + iy) dims[2] + iz: the flattening of torch.meshgrid(indexing="ij").
+ * Both check every argument before their first HIP call (SR_ERR_INVALID_ARGUMENT: a NULL pointer, V < 1, H or W < 2, voxel_size <= 0 or
+ * NaN, a slab outside the grid; SR_ERR_UNSUPPORTED: 2^31 samples or more in one call), run on the caller's stream, allocate nothing and
+ * read nothing back; no atomics: equal inputs give equal bits.  n == 0 (an empty slab) is no error and no work.
+ * Added without a new SR_ABI_VERSION: nothing that existed changed. */
+typedef struct SrTsdfViews {
+    const float* maps;        /* device [V,H,W] (channels 1) or [V,H,W,4] (channels 4) */
+    const float* full_proj;   /* device [V,16]: full_proj_transform of every view, row-major as the reference stores it */
+    int32_t V, H, W, channels;
+} SrTsdfViews;
+typedef struct SrTsdfSpace {
+    double voxel_size;
+    int32_t contract;         /* 0: world-space samples, constant truncation (center and radius are not read) */
+    float center[3];
+    float radius;
+} SrTsdfSpace;
+int sr_tsdf_fuse(const SrTsdfViews* views, const SrTsdfSpace* space, int32_t n, const float* samples, float* tsdf, float* rgb, float* weight,
+                 void* stream);
+int sr_tsdf_fuse_grid(const SrTsdfViews* views, const SrTsdfSpace* space, const int32_t* dims, const float* lo, const float* step,
+                      int32_t ix_begin, int32_t ix_end, float* tsdf, float* rgb, float* weight, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

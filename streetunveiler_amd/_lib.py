@@ -74,6 +74,14 @@ class SrDensifySegment(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int32), ("role", C.c_int32)]
 
 
+class SrTsdfViews(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("full_proj", C.c_void_p), ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels", C.c_int32)]
+
+
+class SrTsdfSpace(C.Structure):
+    _fields_ = [("voxel_size", C.c_double), ("contract", C.c_int32), ("center", C.c_float * 3), ("radius", C.c_float)]
+
+
 SR_DENSIFY_MAX_SEGMENTS = 8
 SR_DENSIFY_FLAG_CLONE, SR_DENSIFY_FLAG_SPLIT, SR_DENSIFY_FLAG_KEEP_SELF, SR_DENSIFY_FLAG_KEEP_CHILD = 1, 2, 4, 8
 SR_DENSIFY_KIND_ORIGINAL, SR_DENSIFY_KIND_CLONE, SR_DENSIFY_KIND_CHILD0, SR_DENSIFY_KIND_CHILD1 = 0, 1, 2, 3
@@ -86,7 +94,7 @@ EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_e
            "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
            "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
            "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius",
-           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply"]
+           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply", "sr_tsdf_fuse", "sr_tsdf_fuse_grid"]
 
 _lib = None
 
@@ -178,6 +186,9 @@ def load():
                                                                                       C.POINTER(C.c_uint32), C.c_void_p]
     lib.sr_densify_apply.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrDensifySegment),
                                      C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.sr_tsdf_fuse.argtypes = [C.POINTER(SrTsdfViews), C.POINTER(SrTsdfSpace), C.c_int32] + [C.c_void_p] * 5
+    lib.sr_tsdf_fuse_grid.argtypes = [C.POINTER(SrTsdfViews), C.POINTER(SrTsdfSpace), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.c_int32, C.c_int32] + [C.c_void_p] * 4
     lib.sr_debug_radix_sort_temp_bytes.argtypes = [C.c_uint32]
     lib.sr_debug_radix_sort_temp_bytes.restype = C.c_size_t
     lib.sr_debug_radix_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]

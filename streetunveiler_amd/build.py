@@ -38,6 +38,7 @@ SOURCES = [
     ("knn.hip", ["-ffp-contract=off"]),         # squared distances bit-identical to the brute-force oracle
     ("cluster.hip", ["-ffp-contract=off"]),     # the distance predicate is bit-identical to the float32 expression it restates
     ("densify.hip", ["-ffp-contract=off"]),     # the order of the child position and the child scale is what the tests hold
+    ("tsdf.hip", ["-ffp-contract=off"]),        # the fmaf()s written out in it are the only fused operations: one expression in every instantiation
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -1,7 +1,8 @@
 // launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
-// Host-only: nothing in here is a kernel parameter except PostCam, LossImages and DensifyRule, which their kernels take by value.
+// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, DensifyRule and the three Tsdf structs, which their
+// kernels take by value.
 #pragma once
 #include "common.h"
 
@@ -166,5 +167,24 @@ hipError_t densify_plan(int P, const float* accum, const float* denom, const flo
 const uint32_t* densify_counts_device(int P, const void* workspace);   // the same four words inside the workspace
 hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
                          const SrDensifySegment* segments, int n_segments, const void* workspace, hipStream_t s);
+
+// ---- tsdf.hip ------------------------------------------------------------------------------------------------------------------------
+struct TsdfViewsDev {      // kernel parameters, by value
+    const float* maps;     // device [V,H,W] depths (channels 1) or [V,H,W,4] (depth, r, g, b) records (channels 4)
+    const float* full_proj;   // device [V,16]
+    int V, H, W, channels;
+};
+struct TsdfSpace {
+    float trunc;           // (float)(5 * voxel_size)
+    int contract;          // 1: the samples are in contracted space (center, radius), the truncation is adaptive
+    float center[3], radius;
+};
+struct TsdfGrid {          // sample (ix, iy, iz) = fmaf(index, step, lo) per axis; thread i is ix - ix0 = i / (ny nz), iy, iz
+    float lo[3], step[3];
+    int ny, nz, ix0;
+};
+// grid == nullptr: the n samples are read from `samples` [n,3]; rgb (with channels 4) and weight may be nullptr
+hipError_t launch_tsdf_fuse(const TsdfViewsDev& views, const TsdfSpace& space, const TsdfGrid* grid, int n, const float* samples, float* tsdf,
+                            float* rgb, float* weight, hipStream_t s);
 
 }  // namespace sr
