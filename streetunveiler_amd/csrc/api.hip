@@ -134,13 +134,8 @@ int rank_mode(hipStream_t s, bool force_ballot, RankMode* mode) {
 
 // ---- buffer layouts ------------------------------------------------------------------------------
 // A layout = the byte offsets of a state buffer's regions (every region 256-B aligned) + its total; a view = the typed pointers of one
-// buffer carved by that layout.  Every entry point carves once, through these.
+// buffer carved by that layout.  Every entry point carves once, through these (launch.h: Carver, at<T>).
 constexpr int kMaxTilesPerAxis = SR_MAX_TILES_PER_AXIS;   // binning.hip kXpMaxBins: 10-bit row / column fields, 1024-entry LDS histograms
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
 
 struct GeomLayout {
     size_t recs, depth_keys, tiles_touched, rect, clamped, sorted_keys, sorted_gid, rect_sorted, first, sh_jac, block_base, base_bytes,
@@ -230,9 +225,10 @@ struct ImgLayout { size_t final_T, n_contrib, total; };
 ImgLayout img_layout(int W, int H) {
     ImgLayout L{};
     const size_t hw = (size_t)(W > 0 ? W : 1) * (size_t)(H > 0 ? H : 1);
-    L.final_T = 0;
-    L.n_contrib = align_up(hw * 3 * 4, 256);
-    L.total = align_up(L.n_contrib + hw * 2 * 4, 256);
+    Carver c;
+    L.final_T = c.take(hw * 3 * 4);
+    L.n_contrib = c.take(hw * 2 * 4);
+    L.total = c.off;
     return L;
 }
 struct ImgView { float* final_T; uint32_t* n_contrib; };
@@ -242,17 +238,20 @@ ImgView img_view(void* image, const ImgLayout& L) { return ImgView{at<float>(ima
 // emission order (a Gaussian's duplicates are contiguous).  K7 writes a record -- and sets the slot's byte in `written` -- only where some
 // pixel contributed; K8 looks at the byte before it touches the record, so neither the records nor anything but these D bytes need clearing.
 size_t record_bytes(int color_channels) { return (size_t)(color_channels == 9 ? kGradFloats + 4 : kGradFloats) * 4; }
-struct WorkspaceLayout { size_t written, total; };
+struct WorkspaceLayout { size_t records, written, total; };
 WorkspaceLayout workspace_layout(uint32_t D, int color_channels) {
     const size_t n = (size_t)(D > 0 ? D : 1);
     WorkspaceLayout L{};
-    L.written = align_up(n * record_bytes(color_channels), 256);
-    L.total = L.written + align_up(n, 256);
+    Carver c;
+    L.records = c.take(n * record_bytes(color_channels));
+    L.written = c.take(n);
+    L.total = c.off;
     return L;
 }
 struct WorkspaceView { float4* records; uint8_t* written; };
 WorkspaceView workspace_view(void* workspace, uint32_t D, int color_channels) {
-    return WorkspaceView{static_cast<float4*>(workspace), at<uint8_t>(workspace, workspace_layout(D, color_channels).written)};
+    const WorkspaceLayout L = workspace_layout(D, color_channels);
+    return WorkspaceView{at<float4>(workspace, L.records), at<uint8_t>(workspace, L.written)};
 }
 
 struct TileShape { int w, h; };
@@ -546,11 +545,12 @@ ClassLayout class_layout(int W, int H, int n_classes) {
     ClassLayout L{};
     const size_t hw = (size_t)(W > 0 ? W : 1) * (size_t)(H > 0 ? H : 1), n = (size_t)(n_classes > 0 ? n_classes : 1);
     const size_t tiles = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);   // (sized for the smallest tile of the sweep, 8x8)
-    L.state = 0;
-    L.last = align_up(n * 3 * hw * 4, 256);
-    L.tile_total = L.last + align_up(n * hw * 4, 256);
-    L.ranges = L.tile_total + align_up((tiles > 0 ? tiles : 1) * n * 4, 256);
-    L.total = L.ranges + align_up((tiles > 0 ? tiles : 1) * n * 8, 256);
+    Carver c;
+    L.state = c.take(n * 3 * hw * 4);
+    L.last = c.take(n * hw * 4);
+    L.tile_total = c.take((tiles > 0 ? tiles : 1) * n * 4);
+    L.ranges = c.take((tiles > 0 ? tiles : 1) * n * 8);
+    L.total = c.off;
     return L;
 }
 struct ClassView { float* state; uint32_t* last; uint32_t* tile_total; uint2* ranges; };
@@ -678,9 +678,10 @@ struct ClassSharedLayout { ClassLayout C; size_t ids, hit, total; };
 ClassSharedLayout class_shared_layout(int P, int W, int H, int n_classes, uint32_t D) {
     ClassSharedLayout L{};
     L.C = class_layout(W, H, n_classes);
-    L.ids = L.C.total;                                                   // class byte per Gaussian (the colour pass owns the sh_jac region here)
-    L.hit = L.ids + align_up((size_t)(P > 0 ? P : 1), 256);              // this pass's own (entry, quadrant) hit masks: the colour pass keeps the binning buffer's
-    L.total = L.hit + align_up((size_t)(D > 0 ? D : 1) * 2, 256);
+    Carver c{L.C.total};                           // behind the stand-alone pass's regions
+    L.ids = c.take((size_t)(P > 0 ? P : 1));       // class byte per Gaussian (the colour pass owns the sh_jac region here)
+    L.hit = c.take((size_t)(D > 0 ? D : 1) * 2);   // this pass's own (entry, quadrant) hit masks: the colour pass keeps the binning buffer's
+    L.total = c.off;
     return L;
 }
 }  // namespace

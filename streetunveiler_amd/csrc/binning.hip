@@ -13,6 +13,7 @@
 //      exclusive scan of 8 160 counters.
 // Stability of every step makes (tile, depth, id) the final order.  Integer work only.
 #include "launch.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -39,20 +40,6 @@ constexpr int kXpBatch = 2048;     // expanded slots ranked + reordered in LDS a
 constexpr int kXpMaxBins = 1024;   // tiles per image axis
 // column item: x = gaussian id, y = first row | rows << 10 | column << 21
 __device__ inline uint32_t pack_column(int miny, int h, int tx) { return (uint32_t)miny | ((uint32_t)h << 10) | ((uint32_t)tx << 21); }
-
-// exclusive prefix of x over the block's threads (+ the block total); s_w: kXpWaves words of scratch
-__device__ inline uint32_t block_exclusive_scan(uint32_t x, uint32_t* s_w, uint32_t& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = wave_inclusive_scan(x);
-    __syncthreads();   // s_w may still be in use from the previous scan
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kXpWaves; ++k) { const uint32_t c = s_w[k]; if (k < w) off += c; tot += c; }
-    total = tot;
-    return off + incl - x;
-}
 
 template <int AXIS> __device__ inline void expansion_of(uint2 item, int& start, int& len) {
     if (AXIS == 0) { start = (int)(item.x & 0xFFFFu); len = (int)(item.y & 0xFFFFu); }            // rect: minx | miny << 16, w | h << 16
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(kXpThreads) void expand_hist_kernel(const uint2* __
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int b = 4 * tid + j; sum += b < bins ? s_diff[b] : 0u; v[j] = sum; }
         uint32_t total;
-        const uint32_t excl = block_exclusive_scan(sum, s_w, total);
+        const uint32_t excl = block_exclusive_scan<kXpWaves>(sum, s_w, total);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int b = 4 * tid + j; if (b < bins) hist[(size_t)b * stride + blockIdx.x] = excl + v[j]; }
     }
@@ -118,26 +105,6 @@ __global__ __launch_bounds__(kXpThreads) void expand_hist_kernel(const uint2* __
             carry += (uint32_t)__shfl((int)incl, 63);
         }
     }
-}
-
-// Exclusive scan of every histogram row (one block per digit) + the row totals.
-__global__ __launch_bounds__(kXpThreads) void expand_scan_rows_kernel(uint32_t* __restrict__ hist, int stride, uint32_t n_host,
-                                                                      const uint32_t* __restrict__ n_dev, int inputs_per_block,
-                                                                      uint32_t* __restrict__ row_total) {
-    __shared__ uint32_t s_w[kXpWaves];
-    const uint32_t n = n_dev ? *n_dev : n_host;
-    const int nblocks = (int)((n + (uint32_t)inputs_per_block - 1) / (uint32_t)inputs_per_block);
-    uint32_t* row = hist + (size_t)blockIdx.x * stride;
-    uint32_t carry = 0;
-    for (int c = 0; c < nblocks; c += kXpThreads) {
-        const int i = c + (int)threadIdx.x;
-        const uint32_t x = i < nblocks ? row[i] : 0u;
-        uint32_t total;
-        const uint32_t excl = block_exclusive_scan(x, s_w, total);
-        if (i < nblocks) row[i] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) row_total[blockIdx.x] = carry;
 }
 
 template <int AXIS, int kBits, bool kAtomicRank>
@@ -183,7 +150,7 @@ __global__ __launch_bounds__(kXpThreads) void expand_scatter_kernel(
             incl[i] = sum;
         }
         for (int k = tid; k < kXpBatch / 4; k += kXpThreads) reinterpret_cast<uint32_t*>(s_start)[k] = 0;
-        const uint32_t excl = block_exclusive_scan(sum, s_w, E);
+        const uint32_t excl = block_exclusive_scan<kXpWaves>(sum, s_w, E);
 #pragma unroll
         for (int i = 0; i < kXpPerThread; ++i) {
             s_prefix[tid * kXpPerThread + i + 1] = excl + incl[i];
@@ -196,7 +163,7 @@ __global__ __launch_bounds__(kXpThreads) void expand_scatter_kernel(
 #pragma unroll
         for (int j = 0; j < kPer; ++j) { const int d = tid * kPer + j; const uint32_t c = (d < bins) ? row_total[d] : 0u; v[j] = sum; sum += c; }
         uint32_t total;
-        const uint32_t excl = block_exclusive_scan(sum, s_w, total);
+        const uint32_t excl = block_exclusive_scan<kXpWaves>(sum, s_w, total);
 #pragma unroll
         for (int j = 0; j < kPer; ++j) { const int d = tid * kPer + j; if (d < kBins) s_goff[d] = d < bins ? excl + v[j] + hist[(size_t)d * stride + blockIdx.x] : 0u; }
         if (AXIS == 0 && blockIdx.x == 0 && tid == 0) *n_columns_out = total;   // number of column items = pass Y's input size
@@ -256,7 +223,7 @@ __global__ __launch_bounds__(kXpThreads) void expand_scatter_kernel(
                 sum += tot[j];
             }
             uint32_t total;
-            uint32_t run = block_exclusive_scan(sum, s_w, total);
+            uint32_t run = block_exclusive_scan<kXpWaves>(sum, s_w, total);
 #pragma unroll
             for (int j = 0; j < kPer; ++j) {
                 const int d = tid * kPer + j;
@@ -370,6 +337,7 @@ __global__ __launch_bounds__(kOrderThreads) void tile_ranges_order_kernel(int n_
         }
         __syncthreads();
         // prefix over the waves: 16 classes x 16 waves on 256 threads (a 16-lane row per class), the wave totals on 16 more
+        // (not scan.h's block scan: a 16 x 16 shape on row_inclusive_scan16, and the wave totals share its two barriers)
         if (tid < kOrderClasses * kWaves) {
             const uint32_t v = s_cls[tid >> 4][tid & 15], in = row_inclusive_scan16(v);
             s_off[tid >> 4][tid & 15] = in - v;
@@ -408,8 +376,7 @@ __global__ __launch_bounds__(kOrderThreads) void tile_ranges_order_kernel(int n_
 
 // temp-storage sizes (pure host arithmetic) --------------------------------------------------------
 size_t depth_sort_temp_bytes(int P) {
-    const uint32_t n = (uint32_t)(P > 0 ? P : 1);
-    return align_up(radix_sort_temp_bytes(n), 256);
+    return radix_sort_temp_bytes((uint32_t)(P > 0 ? P : 1));   // (a multiple of 256: RadixLayout)
 }
 size_t tile_scan_temp_bytes(int P) { return tile_count_scan_temp_bytes((uint32_t)(P > 0 ? P : 1)); }
 
@@ -463,7 +430,7 @@ hipError_t run_expand_columns(int P, int tiles_x, int n_tiles, const uint2* rect
     // (n_visible: the depth sort compacted -- only the first *n_visible sorted entries exist; the grid is sized for P, surplus blocks leave at once)
     hipLaunchKernelGGL(expand_hist_kernel<0>, dim3(nb), dim3(kXpThreads), 0, s, rect_sorted, (uint32_t)P, n_visible, tiles_x, hist, nb,
                        tiles_x, tile_counts, n_tiles);
-    hipLaunchKernelGGL(expand_scan_rows_kernel, dim3(tiles_x), dim3(kXpThreads), 0, s, hist, nb, (uint32_t)P, n_visible, kXpInputsX, row_total);
+    launch_scan_rows(tiles_x, hist, nb, (uint32_t)P, n_visible, kXpInputsX, row_total, s);
     launch_expand_scatter<0>(rank_mode, tiles_x, nb, s, rect_sorted, (uint32_t)P, n_visible, tiles_x, (const uint32_t*)hist, nb,
                              (const uint32_t*)row_total, sorted_gid, columns, n_columns, (uint32_t*)nullptr);
     return hipGetLastError();
@@ -478,7 +445,7 @@ hipError_t run_expand_rows(uint32_t D, int tiles_x, int tiles_y, const uint2* co
     const int nb = (int)((D + kXpInputsY - 1) / kXpInputsY);
     hipLaunchKernelGGL(expand_hist_kernel<1>, dim3(nb), dim3(kXpThreads), 0, s, columns, D, n_columns, tiles_y, hist, nb, tiles_x, tile_counts,
                        tiles_x * tiles_y);
-    hipLaunchKernelGGL(expand_scan_rows_kernel, dim3(tiles_y), dim3(kXpThreads), 0, s, hist, nb, D, n_columns, kXpInputsY, row_total);
+    launch_scan_rows(tiles_y, hist, nb, D, n_columns, kXpInputsY, row_total, s);
     launch_expand_scatter<1>(rank_mode, tiles_y, nb, s, columns, D, n_columns, tiles_y, (const uint32_t*)hist, nb, (const uint32_t*)row_total,
                              (const uint32_t*)nullptr, (uint2*)nullptr, (uint32_t*)nullptr, point_list);
     return hipGetLastError();

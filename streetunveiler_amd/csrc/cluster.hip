@@ -15,11 +15,11 @@
 #include <cmath>
 #include <cstdint>
 
+#include "cloud.h"
 #include "launch.h"
 
 namespace sr {
 
-constexpr int kWave = 64;
 constexpr int kClusterThreads = 256;
 
 // parent[] is shared by every wave of the edge kernel: relaxed agent-scope accesses, so that a retry reads memory again and not a register
@@ -58,30 +58,6 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
 __global__ __launch_bounds__(kClusterThreads) void cluster_init_kernel(int n, int* __restrict__ parent) {
     const long long i = (long long)blockIdx.x * kClusterThreads + threadIdx.x;
     if (i < n) parent[i] = (int)i;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = kWave / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-
-// The squared distance of the predicate, in its operation order (-ffp-contract=off: build.py)
-__device__ __forceinline__ float dist2(const float4 a, const float4 b) {
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-// A box (or a point: lo == hi) against a box, with the same operations on the gaps: a gap is no larger than the coordinate difference of
-// any pair of points from the two, and subtraction, multiplication and addition of float32 are monotone, so a pair whose dist2 is below
-// a bound has boxes whose gap2 is below it.  Needs no slack.  (An empty box is (FLT_MAX, -FLT_MAX): its gap2 is inf.)
-__device__ __forceinline__ float gap2(const float4 alo, const float4 ahi, const float (&blo)[3], const float (&bhi)[3]) {
-    const float gx = fmaxf(0.f, fmaxf(alo.x - bhi[0], blo[0] - ahi.x));
-    const float gy = fmaxf(0.f, fmaxf(alo.y - bhi[1], blo[1] - ahi.y));
-    const float gz = fmaxf(0.f, fmaxf(alo.z - bhi[2], blo[2] - ahi.z));
-    return (gx * gx + gy * gy) + gz * gz;
 }
 
 // One wave = 64 curve-consecutive queries.  sorted[] holds the points that take part first, in Morton order, and every other point behind
@@ -147,21 +123,19 @@ struct ClusterLayout {
 
 static ClusterLayout cluster_layout(int n) {
     ClusterLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 1, 256); return o; };
+    Carver c;
     L.n_boxes = (int)(((long long)n + kKnnBox - 1) / kKnnBox);
-    L.partial = take(cloud_bounds_partial_bytes(n));
-    L.bounds = take(6 * 4);
-    L.codes = take((size_t)n * 4); L.codes_sorted = take((size_t)n * 4); L.order = take((size_t)n * 4);
-    L.sorted = take((size_t)n * 16);
-    L.boxes = take((size_t)L.n_boxes * 32);
-    L.parent = take((size_t)n * 4);
-    L.sort_temp = take(radix_sort_temp_bytes((uint32_t)n));
-    L.total = off;
+    const size_t points = n > 0 ? n : 1, boxes = L.n_boxes > 0 ? L.n_boxes : 1;   // (an empty cloud's regions take 256 B each all the same)
+    L.partial = c.take(cloud_bounds_partial_bytes(n));
+    L.bounds = c.take(6 * 4);
+    L.codes = c.take(points * 4); L.codes_sorted = c.take(points * 4); L.order = c.take(points * 4);
+    L.sorted = c.take(points * 16);
+    L.boxes = c.take(boxes * 32);
+    L.parent = c.take(points * 4);
+    L.sort_temp = c.take(radix_sort_temp_bytes((uint32_t)n));
+    L.total = c.off;
     return L;
 }
-
-template <class T> static T* wat(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 // sqrtf(d2) < r  <=>  d2 < T, with T the smallest float32 whose root is not below r: sqrtf is correctly rounded, hence monotone, so the
 // float32 values split into those below T, whose root is below r, and the rest.  r * r lies within a few steps of T; the two loops walk
@@ -180,18 +154,18 @@ hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float 
                           RankMode rank_mode, hipStream_t s) {
     const ClusterLayout L = cluster_layout(n);
     if (ws_bytes < L.total) return hipErrorInvalidValue;
-    float* bounds = wat<float>(ws, L.bounds);
-    const CloudOrder o{wat<uint32_t>(ws, L.codes), wat<uint32_t>(ws, L.codes_sorted), wat<uint32_t>(ws, L.order), wat<float4>(ws, L.sorted)};
-    int* parent = wat<int>(ws, L.parent);
+    float* bounds = at<float>(ws, L.bounds);
+    const CloudOrder o{at<uint32_t>(ws, L.codes), at<uint32_t>(ws, L.codes_sorted), at<uint32_t>(ws, L.order), at<float4>(ws, L.sorted)};
+    int* parent = at<int>(ws, L.parent);
     const dim3 grid((unsigned)(((long long)n + kClusterThreads - 1) / kClusterThreads)), block(kClusterThreads);
-    hipError_t e = cloud_bounds_masked(xyz, active, n, wat<float>(ws, L.partial), bounds, s);
+    hipError_t e = cloud_bounds_masked(xyz, active, n, at<float>(ws, L.partial), bounds, s);
     if (e != hipSuccess) return e;
-    e = cloud_order(xyz, active, true, n, bounds, o, wat<void>(ws, L.sort_temp), radix_sort_temp_bytes((uint32_t)n), rank_mode, s);
+    e = cloud_order(xyz, active, true, n, bounds, o, at<void>(ws, L.sort_temp), radix_sort_temp_bytes((uint32_t)n), rank_mode, s);
     if (e != hipSuccess) return e;
-    e = cloud_boxes(o.sorted, n, wat<float4>(ws, L.boxes), s);
+    e = cloud_boxes(o.sorted, n, at<float4>(ws, L.boxes), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(cluster_init_kernel, grid, block, 0, s, n, parent);
-    hipLaunchKernelGGL(cluster_edges_kernel, grid, block, 0, s, o.sorted, n, wat<float4>(ws, L.boxes), cluster_d2_below(radius), parent);
+    hipLaunchKernelGGL(cluster_edges_kernel, grid, block, 0, s, o.sorted, n, at<float4>(ws, L.boxes), cluster_d2_below(radius), parent);
     hipLaunchKernelGGL(cluster_labels_kernel, grid, block, 0, s, o.sorted, active, n, parent, reinterpret_cast<long long*>(labels));
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "launch.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -26,11 +27,12 @@ static DensifyLayout densify_layout(int P) {
     DensifyLayout L;
     const size_t n = P > 0 ? (size_t)P : 0;
     L.nblocks = (int)((n + kDfThreads - 1) / kDfThreads);
-    L.flags = 0;
-    L.map = align_up(n, 256);
-    L.child_rank = L.map + align_up(8 * n, 256);
-    L.totals = L.child_rank + align_up(4 * n, 256);
-    L.total = L.totals + align_up(16 * ((size_t)L.nblocks + 1), 256);
+    Carver c;
+    L.flags = c.take(n);
+    L.map = c.take(8 * n);
+    L.child_rank = c.take(4 * n);
+    L.totals = c.take(16 * ((size_t)L.nblocks + 1));
+    L.total = c.off;
     return L;
 }
 size_t densify_workspace_bytes(int P) { return densify_layout(P).total; }
@@ -69,68 +71,46 @@ __device__ __forceinline__ uint32_t packed_counts(uint32_t f) {
     return keep | ((keep & f) << 8) | (((f >> 1) & 1u) << 16) | (((f >> 3) & 1u) << 24);
 }
 __device__ __forceinline__ uint4 unpack_counts(uint32_t p) { return make_uint4(p & 255u, (p >> 8) & 255u, (p >> 16) & 255u, p >> 24); }
-__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// The scan of the packed word inside a wave, its four counts across the waves (a block holds 256: a byte would overflow): the exclusive
+// prefix of the four counts over the block + the block's totals
+__device__ __forceinline__ uint4 block_exclusive_counts(uint32_t packed, uint4* s_w, uint4& total) {
+    return block_exclusive_from_waves<kDfThreads / 64>(unpack_counts(wave_inclusive_scan(packed)), unpack_counts(packed), s_w, total);
+}
 
 __global__ __launch_bounds__(kDfThreads) void densify_decide_kernel(int P, const float* __restrict__ accum, const float* __restrict__ denom,
                                                                     const float* __restrict__ opacity, const float* __restrict__ scaling,
                                                                     const uint8_t* __restrict__ prune_mask, const DensifyRule rule,
                                                                     uint8_t* __restrict__ flags, uint4* __restrict__ block_total) {
-    __shared__ uint32_t s_w[kDfThreads / 64];
+    __shared__ uint4 s_w[kDfThreads / 64];
     const int tid = threadIdx.x, i = blockIdx.x * kDfThreads + tid;
     uint32_t f = 0;
     if (i < P) {
         f = densify_flags(i, accum, denom, opacity, scaling, prune_mask, rule);
         flags[i] = (uint8_t)f;
     }
-    const uint32_t incl = wave_inclusive_scan(packed_counts(f));
-    if ((tid & 63) == 63) s_w[tid >> 6] = incl;
-    __syncthreads();
-    if (tid == 0) {
-        uint4 t = make_uint4(0, 0, 0, 0);
-        for (int k = 0; k < kDfThreads / 64; ++k) t = add4(t, unpack_counts(s_w[k]));
-        block_total[blockIdx.x] = t;
-    }
+    uint4 total;
+    block_exclusive_counts(packed_counts(f), s_w, total);   // (only the totals are used)
+    if (tid == 0) block_total[blockIdx.x] = total;
 }
 
 // exclusive scan of block_total[0 .. nblocks) in place, one block; block_total[nblocks] = the four totals, also stored straight into the
 // caller's pinned host words when given
 __global__ __launch_bounds__(kDfThreads) void densify_totals_kernel(uint4* __restrict__ block_total, int nblocks, uint4* __restrict__ total_host) {
     __shared__ uint4 s_w[kDfThreads / 64];
-    __shared__ uint4 s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_carry = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    for (int c = 0; c < nblocks; c += kDfThreads) {
-        const int i = c + tid;
-        const uint4 x = i < nblocks ? block_total[i] : make_uint4(0, 0, 0, 0);
-        const uint4 incl = make_uint4(wave_inclusive_scan(x.x), wave_inclusive_scan(x.y), wave_inclusive_scan(x.z), wave_inclusive_scan(x.w));
-        if (lane == 63) s_w[w] = incl;
-        __syncthreads();
-        uint4 off = s_carry;
-        for (int k = 0; k < w; ++k) off = add4(off, s_w[k]);
-        const uint4 mine = add4(off, incl);
-        if (i < nblocks) block_total[i] = make_uint4(mine.x - x.x, mine.y - x.y, mine.z - x.z, mine.w - x.w);
-        __syncthreads();
-        if (tid == kDfThreads - 1) s_carry = mine;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        block_total[nblocks] = s_carry;
-        if (total_host) *total_host = s_carry;
+    const uint4 total = carried_exclusive_scan<kDfThreads / 64>(block_total, nblocks, s_w);
+    if (threadIdx.x == 0) {
+        block_total[nblocks] = total;
+        if (total_host) *total_host = total;
     }
 }
 
 __global__ __launch_bounds__(kDfThreads) void densify_map_kernel(int P, const uint8_t* __restrict__ flags, const uint4* __restrict__ block_base,
                                                                  int nblocks, uint32_t* __restrict__ map, uint32_t* __restrict__ child_rank) {
-    __shared__ uint32_t s_w[kDfThreads / 64];
-    const int tid = threadIdx.x, w = tid >> 6, i = blockIdx.x * kDfThreads + tid;
+    __shared__ uint4 s_w[kDfThreads / 64];
+    const int tid = threadIdx.x, i = blockIdx.x * kDfThreads + tid;
     const uint32_t f = i < P ? flags[i] : 0u;
-    const uint32_t packed = packed_counts(f);
-    const uint32_t incl = wave_inclusive_scan(packed);
-    if ((tid & 63) == 63) s_w[w] = incl;
-    __syncthreads();
-    uint4 at = add4(block_base[blockIdx.x], unpack_counts(incl - packed));
-    for (int k = 0; k < w; ++k) at = add4(at, unpack_counts(s_w[k]));
+    uint4 block_counts;   // (not used: the totals of all blocks are what places the output rows)
+    const uint4 at = block_base[blockIdx.x] + block_exclusive_counts(packed_counts(f), s_w, block_counts);
     const uint4 total = block_base[nblocks];   // K, C, S, H
     if (f & SR_DENSIFY_FLAG_KEEP_SELF) {
         map[at.x] = (uint32_t)i;
@@ -147,13 +127,12 @@ __global__ __launch_bounds__(kDfThreads) void densify_map_kernel(int P, const ui
 hipError_t densify_plan(int P, const float* accum, const float* denom, const float* opacity, const float* scaling, const DensifyRule& rule,
                         const uint8_t* prune_mask, void* workspace, uint32_t* counts_pinned_dev, hipStream_t s) {
     const DensifyLayout L = densify_layout(P);
-    char* ws = static_cast<char*>(workspace);
-    uint8_t* flags = reinterpret_cast<uint8_t*>(ws + L.flags);
-    uint4* totals = reinterpret_cast<uint4*>(ws + L.totals);
+    uint8_t* flags = at<uint8_t>(workspace, L.flags);
+    uint4* totals = at<uint4>(workspace, L.totals);
     hipLaunchKernelGGL(densify_decide_kernel, dim3(L.nblocks), dim3(kDfThreads), 0, s, P, accum, denom, opacity, scaling, prune_mask, rule, flags, totals);
     hipLaunchKernelGGL(densify_totals_kernel, dim3(1), dim3(kDfThreads), 0, s, totals, L.nblocks, reinterpret_cast<uint4*>(counts_pinned_dev));
     hipLaunchKernelGGL(densify_map_kernel, dim3(L.nblocks), dim3(kDfThreads), 0, s, P, flags, totals, L.nblocks,
-                       reinterpret_cast<uint32_t*>(ws + L.map), reinterpret_cast<uint32_t*>(ws + L.child_rank));
+                       at<uint32_t>(workspace, L.map), at<uint32_t>(workspace, L.child_rank));
     return hipGetLastError();
 }
 

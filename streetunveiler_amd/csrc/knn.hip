@@ -14,11 +14,11 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "cloud.h"
 #include "launch.h"
 
 namespace sr {
 
-constexpr int kWave = 64;
 constexpr int kKnnThreads = 256;
 
 // ---- ordering a cloud ---------------------------------------------------------------------------------------
@@ -145,24 +145,10 @@ __global__ __launch_bounds__(kKnnThreads) void knn_boxes_kernel(const float4* __
 }
 
 // ---- search --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dist2(const float4 a, const float4 b) {
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
 template <int K>
 __device__ __forceinline__ void insert_best(float (&best)[K], float d) {   // keeps best[] ascending; branch-free; d is never NaN (knn_gather_kernel)
 #pragma unroll
     for (int k = 0; k < K; ++k) { const float lo = fminf(best[k], d); d = fmaxf(best[k], d); best[k] = lo; }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-    for (int o = kWave / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
 }
 
 // kSelf: queries ARE the reference points (same sorted array); a point is not its own neighbour.
@@ -204,27 +190,19 @@ __global__ __launch_bounds__(kKnnThreads) void knn_search_kernel(const float4* _
     const float big = FLT_MAX;
     const float wlo[3] = {wave_min(live ? q.x : big), wave_min(live ? q.y : big), wave_min(live ? q.z : big)};
     const float whi[3] = {wave_max(live ? q.x : -big), wave_max(live ? q.y : -big), wave_max(live ? q.z : -big)};
+    const float qp[3] = {q.x, q.y, q.z};
 
     for (int g = 0; g < n_boxes; g += kWave) {
         // the worst bound any lane still has: a box farther than that from the wave's AABB cannot matter to anyone
         const float bound = wave_max(live ? fminf(reject, best[K - 1]) : 0.f);
         bool need = false;
-        if (g + lane < n_boxes) {
-            const float4 bl = boxes[2 * (g + lane)], bh = boxes[2 * (g + lane) + 1];
-            const float gx = fmaxf(0.f, fmaxf(bl.x - whi[0], wlo[0] - bh.x));
-            const float gy = fmaxf(0.f, fmaxf(bl.y - whi[1], wlo[1] - bh.y));
-            const float gz = fmaxf(0.f, fmaxf(bl.z - whi[2], wlo[2] - bh.z));
-            need = !(((gx * gx + gy * gy) + gz * gz) > bound);
-        }
+        if (g + lane < n_boxes) need = !(gap2(boxes[2 * (g + lane)], boxes[2 * (g + lane) + 1], wlo, whi) > bound);
         unsigned long long todo = ballot64(need);
         while (todo) {
             const int b = g + __builtin_ctzll(todo);
             todo &= todo - 1;
             // per-lane test as in the published algorithm: skip when the box is farther than this lane's bounds
-            const float4 bl = boxes[2 * b], bh = boxes[2 * b + 1];
-            const float px = fmaxf(0.f, fmaxf(bl.x - q.x, q.x - bh.x)), py = fmaxf(0.f, fmaxf(bl.y - q.y, q.y - bh.y)),
-                        pz = fmaxf(0.f, fmaxf(bl.z - q.z, q.z - bh.z));
-            const float pd = (px * px + py * py) + pz * pz;
+            const float pd = gap2(boxes[2 * b], boxes[2 * b + 1], qp, qp);
             const bool mine = live && !(pd > reject) && !(pd > best[K - 1]);
             if (ballot64(mine) == 0) continue;
             const int first = b * kKnnBox, last = min(nr, first + kKnnBox);
@@ -283,25 +261,24 @@ hipError_t cloud_boxes(const float4* sorted, int n, float4* boxes, hipStream_t s
 
 KnnLayout knn_layout(int nq, int nr) {   // nq == 0: self search
     KnnLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 1, 256); return o; };
+    Carver c;
     L.blocks_r = bounds_blocks(nr); L.blocks_q = nq > 0 ? bounds_blocks(nq) : 0;
     L.n_boxes = (nr + kKnnBox - 1) / kKnnBox;
-    L.partial = take((size_t)(L.blocks_r + L.blocks_q) * 6 * 4);
-    L.bounds = take(6 * 4);
-    L.r_codes = take((size_t)nr * 4); L.r_codes_sorted = take((size_t)nr * 4); L.r_order = take((size_t)nr * 4);
-    L.r_sorted = take((size_t)nr * 16);
-    L.boxes = take((size_t)L.n_boxes * 32);
-    L.q_codes = take((size_t)nq * 4); L.q_codes_sorted = take((size_t)nq * 4); L.q_order = take((size_t)nq * 4);
-    L.q_sorted = take((size_t)nq * 16);
-    L.sort_temp = take(radix_sort_temp_bytes((uint32_t)(nq > nr ? nq : nr)));
-    L.total = off;
+    // (the self search has no query regions, an empty cloud no points: such a region takes 256 B all the same)
+    const size_t r = nr > 0 ? nr : 1, q = nq > 0 ? nq : 1, boxes = L.n_boxes > 0 ? L.n_boxes : 1;
+    L.partial = c.take((size_t)(L.blocks_r + L.blocks_q) * 6 * 4);
+    L.bounds = c.take(6 * 4);
+    L.r_codes = c.take(r * 4); L.r_codes_sorted = c.take(r * 4); L.r_order = c.take(r * 4);
+    L.r_sorted = c.take(r * 16);
+    L.boxes = c.take(boxes * 32);
+    L.q_codes = c.take(q * 4); L.q_codes_sorted = c.take(q * 4); L.q_order = c.take(q * 4);
+    L.q_sorted = c.take(q * 16);
+    L.sort_temp = c.take(radix_sort_temp_bytes((uint32_t)(nq > nr ? nq : nr)));
+    L.total = c.off;
     return L;
 }
 
 size_t knn_workspace_bytes(int nq, int nr) { return knn_layout(nq, nr).total; }
-
-template <class T> static T* wat(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 // query == nullptr / nq == 0: every reference point against the others
 hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
@@ -310,19 +287,19 @@ hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* refer
     if (self) nq = 0;
     const KnnLayout L = knn_layout(nq, nr);
     if (ws_bytes < L.total) return hipErrorInvalidValue;
-    float* partial = wat<float>(ws, L.partial); float* bounds = wat<float>(ws, L.bounds);
+    float* partial = at<float>(ws, L.partial); float* bounds = at<float>(ws, L.bounds);
     const uint8_t* const all = nullptr;   // the kNN's clouds carry no mask
     hipLaunchKernelGGL(knn_bounds_partial_kernel<false>, dim3(L.blocks_r), dim3(kKnnThreads), 0, s, reference, all, nr, partial);
     if (!self) hipLaunchKernelGGL(knn_bounds_partial_kernel<false>, dim3(L.blocks_q), dim3(kKnnThreads), 0, s, query, all, nq, partial + 6 * L.blocks_r);
     hipLaunchKernelGGL(knn_bounds_final_kernel, dim3(1), dim3(64), 0, s, partial, L.blocks_r + L.blocks_q, bounds);
     const size_t temp_bytes = radix_sort_temp_bytes((uint32_t)(nq > nr ? nq : nr));
     auto order = [&](const float* pts, int n, size_t codes, size_t codes_sorted, size_t order, size_t sorted) {
-        const CloudOrder o{wat<uint32_t>(ws, codes), wat<uint32_t>(ws, codes_sorted), wat<uint32_t>(ws, order), wat<float4>(ws, sorted)};
-        return cloud_order(pts, all, false, n, bounds, o, wat<void>(ws, L.sort_temp), temp_bytes, rank_mode, s);
+        const CloudOrder o{at<uint32_t>(ws, codes), at<uint32_t>(ws, codes_sorted), at<uint32_t>(ws, order), at<float4>(ws, sorted)};
+        return cloud_order(pts, all, false, n, bounds, o, at<void>(ws, L.sort_temp), temp_bytes, rank_mode, s);
     };
     hipError_t e = order(reference, nr, L.r_codes, L.r_codes_sorted, L.r_order, L.r_sorted);
     if (e != hipSuccess) return e;
-    e = cloud_boxes(wat<float4>(ws, L.r_sorted), nr, wat<float4>(ws, L.boxes), s);
+    e = cloud_boxes(at<float4>(ws, L.r_sorted), nr, at<float4>(ws, L.boxes), s);
     if (e != hipSuccess) return e;
     if (!self) {
         e = order(query, nq, L.q_codes, L.q_codes_sorted, L.q_order, L.q_sorted);
@@ -330,11 +307,11 @@ hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* refer
     }
     const int n_search = self ? nr : nq;
     const dim3 grid((n_search + kKnnThreads - 1) / kKnnThreads), block(kKnnThreads);
-    const float4* rs = wat<float4>(ws, L.r_sorted);
-    const float4* qs = self ? rs : wat<float4>(ws, L.q_sorted);
-    const uint32_t* rc = wat<uint32_t>(ws, L.r_codes_sorted);
-    const uint32_t* qc = self ? rc : wat<uint32_t>(ws, L.q_codes_sorted);
-    const float4* boxes = wat<float4>(ws, L.boxes);
+    const float4* rs = at<float4>(ws, L.r_sorted);
+    const float4* qs = self ? rs : at<float4>(ws, L.q_sorted);
+    const uint32_t* rc = at<uint32_t>(ws, L.r_codes_sorted);
+    const uint32_t* qc = self ? rc : at<uint32_t>(ws, L.q_codes_sorted);
+    const float4* boxes = at<float4>(ws, L.boxes);
 #define SR_KNN_LAUNCH(KK, SELF) \
     hipLaunchKernelGGL((knn_search_kernel<KK, SELF>), grid, block, 0, s, qs, n_search, rs, rc, qc, nr, boxes, L.n_boxes, take_sqrt, out)
     if (K == 3) { if (self) SR_KNN_LAUNCH(3, true); else SR_KNN_LAUNCH(3, false); }

@@ -33,6 +33,16 @@ struct BlendChoice {
     bool cull;   // quadrant culling on (SR_FLAG_NO_QUADRANT_CULL clear)
 };
 
+// ---- workspace carving ---------------------------------------------------------------------------------------------------------------
+// A layout = the byte offsets of a buffer's regions, every region 256-B aligned, + its total: one Carver walk per layout function, so a
+// size and the pointers into it cannot drift apart.  A zero-byte region takes no room (callers that rely on distinct regions clamp their
+// counts to 1).  at<T>: the typed pointer of a region.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
+template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
 // ---- preprocess.hip ------------------------------------------------------------------------------------------------------------------
 hipError_t launch_preprocess_forward(int P, const FrameDev& f, const SrGaussians& g, float4* recs, uint32_t* depth_keys,
                                      uint32_t* tiles_touched, uint2* rect, uint8_t* clamped, int32_t* radii, hipStream_t s);
@@ -51,6 +61,10 @@ size_t radix_sort_temp_bytes(uint32_t n);
 hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t n,
                             int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, RankMode rank_mode,
                             bool one_sweep, int rect_bx = 0, int rect_by = 0, const uint32_t* n_live = nullptr);
+// exclusive scan of `rows` histogram rows of `stride` words in place (a block per row) + the row totals; a row ends with the blocks of
+// items_per_block items that hold the min(*n_dev, n_host) items (n_dev == nullptr: n_host)
+hipError_t launch_scan_rows(int rows, uint32_t* hist, int stride, uint32_t n_host, const uint32_t* n_dev, int items_per_block, uint32_t* row_total,
+                            hipStream_t s);
 size_t tile_count_scan_temp_bytes(uint32_t n);
 hipError_t tile_count_scan(const uint32_t* counts, uint32_t* out, uint32_t n, void* temp, size_t temp_bytes, uint32_t* total_host, hipStream_t s);
 hipError_t launch_rank_selfcheck(uint32_t* result, hipStream_t s);

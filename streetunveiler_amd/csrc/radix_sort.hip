@@ -11,6 +11,7 @@
 // phase below).  No atomics on global memory, integer work only, no MFMA.
 #include <cstdlib>
 #include "launch.h"
+#include "scan.h"
 
 namespace sr {
 
@@ -103,32 +104,20 @@ __global__ __launch_bounds__(kRsThreads) void rs_hist_all_kernel(const uint32_t*
     }
 }
 
-// Exclusive scan of every row (one block per digit), row totals out.
-__global__ __launch_bounds__(kRsThreads) void rs_scan_rows_kernel(uint32_t* __restrict__ hist, int stride, const uint32_t* __restrict__ n_dev, uint32_t n_host,
-                                                                  int items_per_block, uint32_t* __restrict__ row_total) {
+// Exclusive scan of every histogram row (one block per digit) + the row totals: the row scan of a sort pass and of both passes of the
+// expanding partition (binning.hip).  n_dev != NULL: the item count lives on the device; the row ends with the blocks that hold items.
+__global__ __launch_bounds__(kRsThreads) void scan_rows_kernel(uint32_t* __restrict__ hist, int stride, uint32_t n_host, const uint32_t* __restrict__ n_dev,
+                                                               int items_per_block, uint32_t* __restrict__ row_total) {
     __shared__ uint32_t s_w[kRsThreads / 64];
-    __shared__ uint32_t s_carry;
     const uint32_t n = n_dev ? min(*n_dev, n_host) : n_host;
-    const int nblocks = (int)((n + (uint32_t)items_per_block - 1) / (uint32_t)items_per_block);   // (<= stride: the blocks that hold items)
-    uint32_t* row = hist + (size_t)blockIdx.x * stride;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int c = 0; c < nblocks; c += kRsThreads) {
-        const int i = c + tid;
-        const uint32_t x = i < nblocks ? row[i] : 0u;
-        uint32_t incl = wave_inclusive_scan(x);
-        if (lane == 63) s_w[w] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        for (int k = 0; k < w; ++k) wbase += s_w[k];
-        const uint32_t carry = s_carry;
-        if (i < nblocks) row[i] = carry + wbase + incl - x;
-        __syncthreads();
-        if (tid == kRsThreads - 1) s_carry = carry + wbase + incl;
-        __syncthreads();
-    }
-    if (tid == 0) row_total[blockIdx.x] = s_carry;
+    const int nblocks = (int)((n + (uint32_t)items_per_block - 1) / (uint32_t)items_per_block);   // (<= stride)
+    const uint32_t total = carried_exclusive_scan<kRsThreads / 64>(hist + (size_t)blockIdx.x * stride, nblocks, s_w);
+    if (threadIdx.x == 0) row_total[blockIdx.x] = total;
+}
+hipError_t launch_scan_rows(int rows, uint32_t* hist, int stride, uint32_t n_host, const uint32_t* n_dev, int items_per_block, uint32_t* row_total,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(scan_rows_kernel, dim3(rows), dim3(kRsThreads), 0, s, hist, stride, n_host, n_dev, items_per_block, row_total);
+    return hipGetLastError();
 }
 
 // The 8-B payload of the depth sort (the tile rectangle, preprocess.hip: minx | miny << 16, width | height << 16) as ONE word that
@@ -195,6 +184,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_scatter_kernel(const uint32_t* 
     }
     __syncthreads();
     // block-local exclusive scan over digits (thread t <-> digit t), then per-wave run starts
+    // (not scan.h's block scan: the two scans below share s_wsum over three barriers; two block_exclusive_scan calls take four)
     {
         uint32_t tot = 0;
         if (tid < bins) {
@@ -295,6 +285,8 @@ __global__ __launch_bounds__(kRsThreads) void rs_scatter_kernel(const uint32_t* 
 // kernels: an exclusive scan inside every block of 2048 Gaussians + the block totals; then an exclusive scan of the totals.  Consumers
 // add the block base themselves (common.h first_index()); totals[nblocks] = D, the number of duplicates, is what the host reads back.
 // ---------------------------------------------------------------------------------------------
+// (Both kernels of this stage keep their own scans, not scan.h's: measured with block_exclusive_scan / carried_exclusive_scan the stage took
+// 15.4 .. 15.6 us against 15.0 .. 15.3 us at 3 M Gaussians -- tools/notes_shared_scan.md.)
 __global__ __launch_bounds__(kRsThreads) void scan_blocks_kernel(const uint32_t* __restrict__ counts, uint32_t n, uint32_t* __restrict__ out,
                                                                  uint32_t* __restrict__ block_total) {
     __shared__ uint32_t s_w[kRsThreads / 64], s_nz[kRsThreads / 64];
@@ -439,12 +431,22 @@ __global__ __launch_bounds__(kRsThreads) void rs_zero_words_kernel(uint32_t* __r
 static inline int rs_blocks(uint32_t n, int items = kRsItems) { return (int)((n + (uint32_t)(kRsThreads * items) - 1) / (uint32_t)(kRsThreads * items)); }
 static inline int scan_blocks(uint32_t n) { return (int)((n + kRsTile - 1) / kRsTile); }
 
-// scratch: ping-pong (keys, vals) + histogram table + row totals
-size_t radix_sort_temp_bytes(uint32_t n) {
-    const size_t nb = (size_t)rs_blocks(n > 0 ? n : 1);
-    // (keys, vals, ride) | histogram table = the one-sweep status table | row totals, the four passes' digit totals, four tickets
-    return align_up((size_t)(n > 0 ? n : 1) * 4, 256) * 3 + align_up(nb * kRsMaxBins * 4, 256) + align_up(kRsMaxBins * 4 * 5 + 64, 256);
+// scratch: ping-pong (keys, vals, ride) | histogram table = the one-sweep status table | row totals, the four passes' digit totals, four
+// tickets.  The size and the pointers come from this one walk.
+struct RadixLayout { size_t keys, vals, ride, hist, row_total, total; };
+static RadixLayout radix_layout(uint32_t n) {
+    const size_t items = n > 0 ? n : 1;
+    RadixLayout L{};
+    Carver c;
+    L.keys = c.take(items * 4);
+    L.vals = c.take(items * 4);
+    L.ride = c.take(items * 4);
+    L.hist = c.take((size_t)rs_blocks((uint32_t)items) * kRsMaxBins * 4);
+    L.row_total = c.take(kRsMaxBins * 4 * 5 + 64);
+    L.total = c.off;
+    return L;
 }
+size_t radix_sort_temp_bytes(uint32_t n) { return radix_layout(n).total; }
 
 // Sorts by key bits [0, total_bits) in passes of <= 8 bits (as even as possible); stable; result in keys_out/vals_out.
 // vals_in == nullptr means "value = index".  keys_in / vals_in are not modified.  If aux_out != nullptr the sort also delivers
@@ -456,19 +458,19 @@ hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, ui
                             int total_bits, void* temp, size_t temp_bytes, hipStream_t s, const uint2* aux_src, uint2* aux_out, RankMode rank_mode,
                             bool one_sweep, int rect_bx, int rect_by, const uint32_t* n_live) {
     if (n == 0) return hipSuccess;
-    if (temp_bytes < radix_sort_temp_bytes(n) || (rank_mode != kRankAtomic && rank_mode != kRankBallot)) return hipErrorInvalidValue;
+    const RadixLayout L = radix_layout(n);
+    if (temp_bytes < L.total || (rank_mode != kRankAtomic && rank_mode != kRankBallot)) return hipErrorInvalidValue;
     int passes = (total_bits + 7) / 8;
     if (passes < 1) passes = 1;
     if (passes & 1) ++passes;   // even pass count: the ping-pong ends in keys_out/vals_out (an extra pass on zero bits is a stable copy)
     const int nb8 = rs_blocks(n);
-    char* t = static_cast<char*>(temp);
-    uint32_t* tk = reinterpret_cast<uint32_t*>(t); t += align_up((size_t)n * 4, 256);
-    uint32_t* tv = reinterpret_cast<uint32_t*>(t); t += align_up((size_t)n * 4, 256);
-    uint32_t* tr = reinterpret_cast<uint32_t*>(t); t += align_up((size_t)n * 4, 256);
+    uint32_t* tk = at<uint32_t>(temp, L.keys);
+    uint32_t* tv = at<uint32_t>(temp, L.vals);
+    uint32_t* tr = at<uint32_t>(temp, L.ride);
     // the ride's other buffer is the first half of aux_out itself: written by odd passes, read by the next one; the last pass reads `tr`
     const bool wide = aux_out && !vals_in && rect_bx > 0 && rect_by > 0 && 2 * (rect_bx + rect_by) <= 32 && passes >= 2 && n >= kSortRideFrom;
-    uint32_t* hist = reinterpret_cast<uint32_t*>(t); t += align_up((size_t)nb8 * kRsMaxBins * 4, 256);
-    uint32_t* row_total = reinterpret_cast<uint32_t*>(t);
+    uint32_t* hist = at<uint32_t>(temp, L.hist);
+    uint32_t* row_total = at<uint32_t>(temp, L.row_total);
     uint32_t* ghist = row_total + kRsMaxBins;          // [4][256] digit totals of the four passes (one-sweep)
     uint32_t* tickets = ghist + 4 * kRsMaxBins;        // [4] block counters, one per pass
     const uint32_t* ki = keys_in; const uint32_t* vi = vals_in;
@@ -499,7 +501,7 @@ hipError_t radix_sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in, ui
         if (!sweep) {
             if (big) hipLaunchKernelGGL(rs_hist_kernel<kSortItemsBig>, dim3(nb), dim3(kRsThreads), 0, s, ki, n, nd, drop, shift, bits, hist, nb);
             else hipLaunchKernelGGL(rs_hist_kernel<kRsItems>, dim3(nb), dim3(kRsThreads), 0, s, ki, n, nd, drop, shift, bits, hist, nb);
-            hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1 << bits), dim3(kRsThreads), 0, s, hist, nb, nd, n, kRsThreads * (big ? kSortItemsBig : kRsItems), row_total);
+            hipLaunchKernelGGL(scan_rows_kernel, dim3(1 << bits), dim3(kRsThreads), 0, s, hist, nb, n, nd, kRsThreads * (big ? kSortItemsBig : kRsItems), row_total);
         }
 #define SR_SCATTER_W(B, A, I, Wd) do { if (sweep && B == 8) hipLaunchKernelGGL((rs_scatter_kernel<B == 8 ? 8 : 0, A, I, Wd, B == 8>), dim3(nb), dim3(kRsThreads), 0, s, ki, vi, ko, vo, n, nd, drop, shift, bits, \
                                                  (const uint32_t*)nullptr, (const uint32_t*)(ghist + p * kRsMaxBins), nb, (Wd ? p == 0 : last) ? aux_src : nullptr, last ? aux_out : nullptr, ri, ro, rect_bx, rect_by, \

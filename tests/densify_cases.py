@@ -136,6 +136,8 @@ for _P in SIZES:
 # the two loops only a large model enters: more than 256 blocks of 256 Gaussians (the carry of the totals scan), and more than 4096 chunks
 # of 4096 words in one gather launch (its grid stride: f_rest with both moments, nothing pruned)
 CASES["P70000_rest0_nostate"] = functools.partial(make_case, 70000, 0, False, seed=11)
+for _P in (65536, 65537):      # 256 and 257 blocks: the last item of the totals scan's first chunk, the first of its second
+    CASES[f"P{_P}_rest0_nostate"] = functools.partial(make_case, _P, 0, False, seed=13)
 CASES["P131073_rest45_state"] = functools.partial(make_case, 131073, 45, True, seed=12, scale_range=(0.005, 0.4), logit_range=(-4.0, 4.0))
 MIXES = [n for n in CASES if not n.startswith("P")]
 

@@ -149,6 +149,31 @@ def test_state_buffer_sizes_are_the_recorded_ones(lib):
             assert lib.sr_class_image_bytes(W, H, n) == CLASS_IMAGE_BYTES[(W, H, n)], (W, H, n)
 
 
+def test_workspace_sizes_are_the_recorded_ones(lib):
+    """Every *_bytes function over the table tools/record_workspace_sizes.py recorded from the library of commit 88b8564, before all
+    layouts were carved by one Carver: byte for byte the same."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "workspace_sizes.json")) as f:
+        recorded = json.load(f)
+    lib.sr_source_digest.restype = ctypes.c_char_p
+    assert recorded["recorded_from_source_digest"] != lib.sr_source_digest().decode()      # not recorded from the library under test
+    assert {0, 1} <= set(recorded["counts"])
+    for b in (256, 2048, 65536, 262144, 524288):
+        assert {b - 1, b, b + 1} <= set(recorded["counts"]), b
+    assert sorted(recorded["sizes"]) == sorted(
+        ["sr_geom_bytes", "sr_binning_bytes", "sr_image_bytes", "sr_backward_workspace_bytes", "sr_class_image_bytes", "sr_class_shared_bytes",
+         "sr_knn_workspace_bytes", "sr_cluster_workspace_bytes", "sr_densify_workspace_bytes", "sr_debug_radix_sort_temp_bytes"])
+    for name, arg in (("sr_geom_bytes", 0), ("sr_knn_workspace_bytes", 1), ("sr_cluster_workspace_bytes", 0),
+                      ("sr_densify_workspace_bytes", 0), ("sr_debug_radix_sort_temp_bytes", 0), ("sr_backward_workspace_bytes", 1),
+                      ("sr_binning_bytes", 1)):
+        assert {row[arg] for row in recorded["sizes"][name]} == set(recorded["counts"]), name
+    assert {row[0] for row in recorded["sizes"]["sr_knn_workspace_bytes"]} == set(recorded["counts"])   # nq, 0 = the self search
+    assert {row[1] for row in recorded["sizes"]["sr_knn_workspace_bytes"] if row[0] == 0} == set(recorded["counts"])
+    for name, rows in recorded["sizes"].items():
+        for *args, size in rows:
+            assert getattr(lib, name)(*args) == size, (name, args)
+
+
 def _view_offsets(view, base):
     return tuple(getattr(view, name) - base for name, _ in view._fields_)
 

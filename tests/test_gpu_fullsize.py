@@ -174,17 +174,18 @@ def test_clustered_street_scene_against_oracle():
     assert rep["list_length"]["p99"] > 6 * rep["list_length"]["p50"] and rep["deepest_contributor"]["max"] > 1500
 
 
-def _properties(P, W, H, check_linearity=True):
+def _forward_properties(g, cam, W, H, **forward_options):
+    """One forward of scene `g` (forward_options: keyword arguments of _C.rasterize_gaussians, e.g. ballot_ranking=True) and the list /
+    image properties of the module docstring.  -> (D, tiles_touched, frame_counts)"""
     from diff_surfel_rasterization import _C
-    from tests.gpu_util import DEV, run_hip, settings_for
-    cam = synthetic_camera(W, H)
-    g = synthetic_gaussians(P, W, H, seed=0)
+    from tests.gpu_util import DEV, settings_for
+    P = g["means3D"].shape[0]
     s = settings_for(cam, [0, 0, 0], 3)
     e = torch.empty(0, device=DEV)
     d = {k: v.to(DEV) for k, v in g.items()}
     D, color, allmap, radii, geom, binning, img = _C.rasterize_gaussians(
         s.bg, d["means3D"], e, d["opacities"], d["scales"], d["rotations"], 1.0, e, s.viewmatrix, s.projmatrix, s.tanfovx,
-        s.tanfovy, H, W, d["shs"], 3, s.campos, False, False)
+        s.tanfovy, H, W, d["shs"], 3, s.campos, False, False, **forward_options)
     gv, bv = _C.geom_view(geom, P), _C.binning_view(binning, P, D, W, H)
     tiles_touched = gv["tiles_touched"].long()
     assert int(tiles_touched.sum()) == D                                   # every duplicate emitted exactly once
@@ -213,7 +214,14 @@ def _properties(P, W, H, check_linearity=True):
     assert (color >= -bar("value_range_slack")).all()                                          # clamped colours, bg 0
     nc = _C.image_view(img, W, H)["n_contrib"].long()
     assert (nc[0] <= lens.view((H + 15) // 16, (W + 15) // 16).repeat_interleave(16, 0).repeat_interleave(16, 1)[:H, :W]).all()
-    del geom, binning, img
+    return D, tiles_touched.cpu(), gv["frame_counts"].cpu()
+
+
+def _properties(P, W, H, check_linearity=True):
+    from tests.gpu_util import run_hip
+    cam = synthetic_camera(W, H)
+    g = synthetic_gaussians(P, W, H, seed=0)
+    D = _forward_properties(g, cam, W, H)[0]
     # determinism and linearity of the backward
     dc, da = synthetic_upstream_grads(W, H, seed=1)
     a = run_hip(g, cam, [0, 0, 0], 3, dc, da)
