@@ -415,6 +415,78 @@ typedef struct SrAdamSegment {
 } SrAdamSegment;
 int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream);
 
+/* sr_adam_step restricted to the rows a mask selects: the optimizer step of the masked re-optimisation model (the reference's
+ * MaskGaussianModel, scene/mask_gaussian.py:195-209), whose six trainable deltas move only around the removed object.  Each tensor is
+ * n = P * row_len contiguous floats (row_len >= 1, below 2^30); mask is uint8 [P] (torch.bool storage), one for all tensors of the call.
+ * An element whose row has mask == 0 is neither read nor written -- not param, grad, exp_avg or exp_avg_sq: a 16-B group that straddles
+ * a selected and an unselected row leaves the unselected elements bit for bit as they were, and what an unselected row of grad holds
+ * (NaN included) is never seen.  Every other element goes through the very update of sr_adam_step (one function in csrc/optimizer.hip).
+ * CONTRACT: this equals the dense step wherever the skipped rows have zero gradient and zero moments and eps > 0 -- Adam then leaves
+ * such a row's parameter, exp_avg and exp_avg_sq exactly as they are (m = 0, v = 0, p - step_size * (0 / eps) = p).  In the reference
+ * that is every masked-out row: set_mask precedes training_setup, which creates the moments as zeros; a masked-out row's gradient is
+ * delta-gradient * 0; and reset_mask builds a new optimizer.  A caller that changes the mask under a live optimizer state freezes the
+ * moments of the rows it switches off instead of letting them decay.
+ * SR_ERR_INVALID_ARGUMENT for P < 0, a NULL mask with P > 0, a row_len outside [1, 2^30), n != P * row_len and everything sr_adam_step
+ * refuses; P == 0 (every n == 0) is no error and no work.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+typedef struct SrAdamRowSegment {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t n;
+    float step_size;
+    float bc2_sqrt;
+    int64_t row_len;
+} SrAdamRowSegment;
+int sr_adam_step_rows(const SrAdamRowSegment* segments, int32_t n_segments, int32_t P, const uint8_t* mask, double beta1, double beta2,
+                      double eps, void* stream);
+
+/* The getters of the masked re-optimisation model == MaskGaussianModel.get_xyz / get_features / get_opacity / get_scaling / get_rotation
+ * of the reference (scene/mask_gaussian.py:139-176) BEFORE their activations, for all six properties in one launch, and their adjoint in
+ * one more (csrc/mask_model.hip).  base and delta are the six tensors of P Gaussians with M = sh_coeffs SH coefficients: xyz [P,3],
+ * features_dc [P,1,3], features_rest [P,M-1,3] (zero-sized and never read for M == 1), opacity [P,1], scaling [P,2], rotation [P,4];
+ * mask is uint8 [P]; fixed_bits has the reference's MASK_PROPERTY bit order (SR_MASK_FIXED_*).
+ * sr_mask_compose writes the effective raw tensors xyz [P,3], features [P,M,3] (the concatenation of the two SH parts), opacity, scaling,
+ * rotation:  a row with mask != 0 gets base + delta; a row with mask == 0 gets base + 0.0f and its delta row is NOT read; a fixed property
+ * gets its base bit for bit and its delta pointer is not read (each half of features on its own).  An output pointer may be NULL where
+ * its property is fixed (features: where both halves are): the caller then uses the base tensor itself.
+ * Two deliberate differences from the reference's `base + delta * mask`: a non-finite delta in a masked-out row does not reach the output
+ * (the reference yields NaN there), and a zero may differ in sign (-0.0f + 0.0f is +0.0f; the reference adds delta * 0, which is -0.0f
+ * for a negative delta).
+ * sr_mask_compose_backward writes the gradients of the deltas from the upstream gradients of the five outputs: a row with mask != 0 gets
+ * the upstream row (features split back into dc and rest), a row with mask == 0 gets zeros and its upstream row is NOT read.  A d_delta
+ * pointer may be NULL (not wanted); one that is given needs its upstream gradient and a property that is not fixed.  base gets no
+ * gradient here (the model freezes it; it would be the upstream gradient itself).
+ * float32, contiguous, 4-B aligned (16-B aligned tensors move 16 B per lane where their rows allow it); no LDS, no atomics, no workspace:
+ * equal inputs give equal bits.  Both check every argument before their first HIP call: SR_ERR_INVALID_ARGUMENT for P < 0,
+ * sh_coeffs < 1, fixed_bits above 63, a missing struct, mask or tensor; SR_ERR_UNSUPPORTED for P * 3 * sh_coeffs >= 2^31.  P == 0 is no
+ * error and no work.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+#define SR_MASK_FIXED_XYZ 1
+#define SR_MASK_FIXED_FEATURES_DC 2
+#define SR_MASK_FIXED_FEATURES_REST 4
+#define SR_MASK_FIXED_SCALING 8
+#define SR_MASK_FIXED_ROTATION 16
+#define SR_MASK_FIXED_OPACITY 32
+typedef struct SrMaskTensors {    /* the six per-Gaussian tensors, in the order of the reference's training_setup */
+    float* xyz;
+    float* features_dc;
+    float* features_rest;
+    float* opacity;
+    float* scaling;
+    float* rotation;
+} SrMaskTensors;
+typedef struct SrMaskEffective {  /* the five tensors the renderer reads */
+    float* xyz;
+    float* features;
+    float* opacity;
+    float* scaling;
+    float* rotation;
+} SrMaskEffective;
+int sr_mask_compose(int32_t P, int32_t sh_coeffs, const SrMaskTensors* base, const SrMaskTensors* delta, const uint8_t* mask,
+                    uint32_t fixed_bits, const SrMaskEffective* out, void* stream);
+int sr_mask_compose_backward(int32_t P, int32_t sh_coeffs, const SrMaskEffective* upstream, const uint8_t* mask, uint32_t fixed_bits,
+                             const SrMaskTensors* d_delta, void* stream);
+
 /* Densification statistics of one rendered view == train.py:168-169 + scene/gaussian_model.py:555-557 of the reference, with
  * visibility_filter = radii > 0.  For every i < P with radii[i] > 0:
  *     xyz_gradient_accum[i] += sqrt(gx^2 + gy^2 + gz^2) of viewspace_grad[i] ([P,3]);   denom[i] += 1;

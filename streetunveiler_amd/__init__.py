@@ -11,10 +11,11 @@ _OPTIM = ("SurfelAdam", "adam_step", "adam_step_float64", "densification_stats",
 _CLUSTER = ("radius_components", "cluster_instance_with_mask", "cluster_semantic_instance")
 _DENSIFY = ("densify_and_prune", "prune_points", "densify_and_prune_tensors", "densify_and_prune_torch")
 _TSDF = ("TsdfViews", "unbounded_tsdf", "unbounded_tsdf_grid", "unbounded_tsdf_torch", "sdf_function", "grid_coordinates")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF)
+_MASK_MODEL = ("MaskedSurfelModel", "compose_masked", "compose_masked_torch")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL)
 
 
-def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune and the TSDF fusion, imported on first use (this package does not import torch by itself)
+def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
     if name in _IMAGE_LOSS:
         from . import image_loss
         return getattr(image_loss, name)
@@ -30,4 +31,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _TSDF:
         from . import tsdf
         return getattr(tsdf, name)
+    if name in _MASK_MODEL:
+        from . import mask_model
+        return getattr(mask_model, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -67,7 +67,24 @@ class SrAdamSegment(C.Structure):
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
 
 
+class SrAdamRowSegment(C.Structure):   # sr_adam_step_rows: SrAdamSegment (its layout is frozen) + the elements per row of the mask
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("row_len", C.c_int64)]
+
+
+class SrMaskTensors(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("features_dc", C.c_void_p), ("features_rest", C.c_void_p), ("opacity", C.c_void_p),
+                ("scaling", C.c_void_p), ("rotation", C.c_void_p)]
+
+
+class SrMaskEffective(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("features", C.c_void_p), ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p)]
+
+
 SR_ADAM_MAX_SEGMENTS, SR_ADAM_CHUNK = 8, 4096
+# the reference's MASK_PROPERTY bit order [REF scene/mask_gaussian.py:29-30]
+SR_MASK_FIXED_XYZ, SR_MASK_FIXED_FEATURES_DC, SR_MASK_FIXED_FEATURES_REST, SR_MASK_FIXED_SCALING, SR_MASK_FIXED_ROTATION, SR_MASK_FIXED_OPACITY = \
+    1, 2, 4, 8, 16, 32
 
 
 class SrDensifySegment(C.Structure):
@@ -94,7 +111,8 @@ EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_e
            "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
            "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
            "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius",
-           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply", "sr_tsdf_fuse", "sr_tsdf_fuse_grid"]
+           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply", "sr_tsdf_fuse", "sr_tsdf_fuse_grid",
+           "sr_adam_step_rows", "sr_mask_compose", "sr_mask_compose_backward"]
 
 _lib = None
 
@@ -179,6 +197,11 @@ def load():
     lib.sr_image_loss_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]
     lib.sr_image_loss_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5
     lib.sr_adam_step.argtypes = [C.POINTER(SrAdamSegment), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.sr_adam_step_rows.argtypes = [C.POINTER(SrAdamRowSegment), C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.sr_mask_compose.argtypes = [C.c_int32, C.c_int32, C.POINTER(SrMaskTensors), C.POINTER(SrMaskTensors), C.c_void_p, C.c_uint32,
+                                    C.POINTER(SrMaskEffective), C.c_void_p]
+    lib.sr_mask_compose_backward.argtypes = [C.c_int32, C.c_int32, C.POINTER(SrMaskEffective), C.c_void_p, C.c_uint32, C.POINTER(SrMaskTensors),
+                                             C.c_void_p]
     lib.sr_densification_stats.argtypes = [C.c_int32] + [C.c_void_p] * 6
     lib.sr_densify_workspace_bytes.argtypes = [C.c_int32]
     lib.sr_densify_workspace_bytes.restype = C.c_size_t

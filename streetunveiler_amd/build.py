@@ -35,6 +35,7 @@ SOURCES = [
     ("postprocess.hip", []),
     ("image_loss.hip", []),
     ("optimizer.hip", ["-ffp-contract=off"]),   # the Adam step's operation order is the one torch's single-tensor path states
+    ("mask_model.hip", ["-ffp-contract=off"]),  # the effective value is ONE float32 add: base + delta, never part of a fused operation
     ("knn.hip", ["-ffp-contract=off"]),         # squared distances bit-identical to the brute-force oracle
     ("cluster.hip", ["-ffp-contract=off"]),     # the distance predicate is bit-identical to the float32 expression it restates
     ("densify.hip", ["-ffp-contract=off"]),     # the order of the child position and the child scale is what the tests hold

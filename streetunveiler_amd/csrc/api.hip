@@ -1003,6 +1003,106 @@ int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1
     return SR_OK;
 }
 
+int sr_adam_step_rows(const SrAdamRowSegment* segments, int32_t n_segments, int32_t P, const uint8_t* mask, double beta1, double beta2,
+                      double eps, void* stream) {
+    if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 1..%d", n_segments, SR_ADAM_MAX_SEGMENTS);
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P > 0 && !mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta1 %g not in [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta2 %g not in [0, 1)", beta2);
+    if (!(eps >= 0.0)) return fail(SR_ERR_INVALID_ARGUMENT, "eps %g is negative", eps);
+    for (int k = 0; k < n_segments; ++k) {
+        const SrAdamRowSegment& a = segments[k];
+        if (a.row_len < 1 || a.row_len >= (1ll << 30)) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: row_len %lld not in [1, 2^30)", k, (long long)a.row_len);
+        if (a.n != (int64_t)P * a.row_len)
+            return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: n %lld is not P * row_len = %d * %lld", k, (long long)a.n, P, (long long)a.row_len);
+        if (a.n == 0) continue;
+        const void* ptrs[4] = {a.param, a.grad, a.exp_avg, a.exp_avg_sq};
+        const char* names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+        for (int j = 0; j < 4; ++j) {
+            if (!ptrs[j]) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is NULL", k, names[j]);
+            if ((uintptr_t)ptrs[j] & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is not 4-B aligned", k, names[j]);
+        }
+    }
+    if (P == 0) return SR_OK;
+    if (!adam_rows_supported(segments, n_segments)) return fail(SR_ERR_UNSUPPORTED, "the segments hold more than 2^31 chunks of %d elements", SR_ADAM_CHUNK);
+    SR_HIP(launch_adam_step_rows(segments, n_segments, mask, beta1, beta2, eps, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+namespace {
+
+// shared refusals of the two masked-model calls; *work = 0: nothing to do
+int mask_model_args(int32_t P, int32_t sh_coeffs, const uint8_t* mask, uint32_t fixed_bits, int* work) {
+    *work = 0;
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (sh_coeffs < 1) return fail(SR_ERR_INVALID_ARGUMENT, "sh_coeffs %d < 1", sh_coeffs);
+    if (fixed_bits > 63u) return fail(SR_ERR_INVALID_ARGUMENT, "fixed_bits %u has bits beyond the six properties", fixed_bits);
+    if (P == 0) return SR_OK;
+    if (!mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (!mask_model_supported(P, sh_coeffs)) return fail(SR_ERR_UNSUPPORTED, "P * 3 * sh_coeffs = %d * 3 * %d reaches 2^31", P, sh_coeffs);
+    *work = 1;
+    return SR_OK;
+}
+
+int mask_pointer(const char* group, const char* name, const void* p, bool required) {
+    if (!p && required) return fail(SR_ERR_INVALID_ARGUMENT, "%s.%s is NULL", group, name);
+    if ((uintptr_t)p & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "%s.%s is not 4-B aligned", group, name);
+    return SR_OK;
+}
+
+const char* const kMaskNames[6] = {"xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"};
+const uint32_t kMaskBits[6] = {SR_MASK_FIXED_XYZ, SR_MASK_FIXED_FEATURES_DC, SR_MASK_FIXED_FEATURES_REST, SR_MASK_FIXED_OPACITY, SR_MASK_FIXED_SCALING,
+                               SR_MASK_FIXED_ROTATION};
+
+}  // namespace
+
+int sr_mask_compose(int32_t P, int32_t sh_coeffs, const SrMaskTensors* base, const SrMaskTensors* delta, const uint8_t* mask,
+                    uint32_t fixed_bits, const SrMaskEffective* out, void* stream) {
+    int work;
+    if (int rc = mask_model_args(P, sh_coeffs, mask, fixed_bits, &work)) return rc;
+    if (!work) return SR_OK;
+    if (!base || !delta || !out) return fail(SR_ERR_INVALID_ARGUMENT, "base / delta / out is NULL");
+    const float* b[6] = {base->xyz, base->features_dc, base->features_rest, base->opacity, base->scaling, base->rotation};
+    const float* d[6] = {delta->xyz, delta->features_dc, delta->features_rest, delta->opacity, delta->scaling, delta->rotation};
+    for (int k = 0; k < 6; ++k) {
+        const bool empty = k == 2 && sh_coeffs == 1;   // features_rest of SH degree 0
+        if (int rc = mask_pointer("base", kMaskNames[k], b[k], !empty)) return rc;
+        if (int rc = mask_pointer("delta", kMaskNames[k], d[k], !empty && !(fixed_bits & kMaskBits[k]))) return rc;
+    }
+    const uint32_t both = SR_MASK_FIXED_FEATURES_DC | SR_MASK_FIXED_FEATURES_REST;
+    const float* o[5] = {out->xyz, out->features, out->opacity, out->scaling, out->rotation};
+    const char* names[5] = {"xyz", "features", "opacity", "scaling", "rotation"};
+    const bool fixed[5] = {(fixed_bits & SR_MASK_FIXED_XYZ) != 0, (fixed_bits & both) == both, (fixed_bits & SR_MASK_FIXED_OPACITY) != 0,
+                           (fixed_bits & SR_MASK_FIXED_SCALING) != 0, (fixed_bits & SR_MASK_FIXED_ROTATION) != 0};
+    for (int k = 0; k < 5; ++k)
+        if (int rc = mask_pointer("out", names[k], o[k], !fixed[k])) return rc;
+    SR_HIP(launch_mask_compose(P, sh_coeffs, *base, *delta, mask, fixed_bits, *out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_mask_compose_backward(int32_t P, int32_t sh_coeffs, const SrMaskEffective* upstream, const uint8_t* mask, uint32_t fixed_bits,
+                             const SrMaskTensors* d_delta, void* stream) {
+    int work;
+    if (int rc = mask_model_args(P, sh_coeffs, mask, fixed_bits, &work)) return rc;
+    if (!work) return SR_OK;
+    if (!upstream || !d_delta) return fail(SR_ERR_INVALID_ARGUMENT, "upstream / d_delta is NULL");
+    const float* d[6] = {d_delta->xyz, d_delta->features_dc, d_delta->features_rest, d_delta->opacity, d_delta->scaling, d_delta->rotation};
+    const float* g[6] = {upstream->xyz, upstream->features, upstream->features, upstream->opacity, upstream->scaling, upstream->rotation};
+    const char* from[6] = {"xyz", "features", "features", "opacity", "scaling", "rotation"};
+    for (int k = 0; k < 6; ++k) {
+        if (int rc = mask_pointer("d_delta", kMaskNames[k], d[k], false)) return rc;
+        if (int rc = mask_pointer("upstream", from[k], g[k], false)) return rc;
+        if (!d[k] || (k == 2 && sh_coeffs == 1)) continue;
+        if (fixed_bits & kMaskBits[k]) return fail(SR_ERR_INVALID_ARGUMENT, "d_delta.%s is asked for, but the property is fixed", kMaskNames[k]);
+        if (!g[k]) return fail(SR_ERR_INVALID_ARGUMENT, "d_delta.%s is asked for without upstream.%s", kMaskNames[k], from[k]);
+    }
+    SR_HIP(launch_mask_compose_backward(P, sh_coeffs, *upstream, mask, *d_delta, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii, float* xyz_gradient_accum, float* denom,
                            float* max_radii2D, void* stream) {
     if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");

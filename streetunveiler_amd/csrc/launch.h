@@ -166,8 +166,19 @@ hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace
 // ---- optimizer.hip -------------------------------------------------------------------------------------------------------------------
 bool adam_supported(const SrAdamSegment* segments, int n_segments);
 hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t s);
+bool adam_rows_supported(const SrAdamRowSegment* segments, int n_segments);
+hipError_t launch_adam_step_rows(const SrAdamRowSegment* segments, int n_segments, const uint8_t* mask, double beta1, double beta2, double eps,
+                                 hipStream_t s);
 hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
                                       float* max_radii2D, hipStream_t s);
+
+// ---- mask_model.hip ------------------------------------------------------------------------------------------------------------------
+bool mask_model_supported(int P, int sh_coeffs);
+// a NULL output / gradient pointer is skipped; a delta whose SR_MASK_FIXED_* bit is set is not read
+hipError_t launch_mask_compose(int P, int sh_coeffs, const SrMaskTensors& base, const SrMaskTensors& delta, const uint8_t* mask,
+                               uint32_t fixed_bits, const SrMaskEffective& out, hipStream_t s);
+hipError_t launch_mask_compose_backward(int P, int sh_coeffs, const SrMaskEffective& upstream, const uint8_t* mask, const SrMaskTensors& d_delta,
+                                        hipStream_t s);
 
 // ---- densify.hip ---------------------------------------------------------------------------------------------------------------------
 struct DensifyRule {   // a kernel parameter, by value

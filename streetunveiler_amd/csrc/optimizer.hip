@@ -1,5 +1,7 @@
 // optimizer.hip -- the tail of a training iteration of the reference (train.py:165-200, scene/gaussian_model.py:166-180, 555-557):
-//   adam_step_kernel            one launch for up to 8 parameter tensors of a torch.optim.Adam step (no weight decay, no amsgrad)
+//   adam_step_kernel<false>     one launch for up to 8 parameter tensors of a torch.optim.Adam step (no weight decay, no amsgrad)
+//   adam_step_kernel<true>      the same step for the rows a per-Gaussian mask selects (the masked re-optimisation model: only the Gaussians
+//                               around the removed object move); the other rows are neither read nor written
 //   densification_stats_kernel  xyz_gradient_accum / denom / max_radii2D of the visible Gaussians, without boolean indexing
 //
 // Adam, per element and in float32, in the order of torch's single-tensor path (this file is built with -ffp-contract=off: the order
@@ -36,9 +38,11 @@ struct AdamSeg {
     float step_size, bc2_sqrt;
     uint32_t first_chunk;   // chunks of the launch in front of this tensor; 0xFFFFFFFF for an unused slot
     uint32_t vec;           // all four pointers 16-B aligned
+    uint32_t row_len;       // adam_step_kernel<true>: elements per row of the mask
 };
 struct AdamTable {
     AdamSeg seg[SR_ADAM_MAX_SEGMENTS];
+    const uint8_t* mask;    // adam_step_kernel<true>: [n / row_len] for every tensor; a row with mask == 0 is neither read nor written
     uint32_t total_chunks;
     float beta2, one_minus_beta1, one_minus_beta2, eps;
 };
@@ -50,15 +54,54 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
     p = p - step_size * __fdiv_rn(m, denom);
 }
 
-// one chunk of a 16-B aligned tensor; FULL: every group of four lies inside the tensor
-template <bool FULL>
+__device__ __forceinline__ void adam_update_at(const AdamSeg& s, const AdamTable& t, long long i) {
+    float pe = s.p[i], me = s.m[i], ve = s.v[i];
+    adam_update(pe, s.g[i], me, ve, t, s.step_size, s.bc2_sqrt);
+    s.p[i] = pe; s.m[i] = me; s.v[i] = ve;
+}
+
+// Where a chunk begins in the rows of the mask.  ROWS = false (the dense step): nothing is computed and every element is selected.
+struct AdamChunkRows {
+    long long row;   // row of the chunk's first element
+    uint32_t col;    // its column
+};
+template <bool ROWS>
+__device__ __forceinline__ AdamChunkRows adam_chunk_rows(const AdamSeg& s, long long base) {
+    if (!ROWS) return AdamChunkRows{0, 0u};
+    const long long row = base / s.row_len;     // wave-uniform: once per chunk
+    return AdamChunkRows{row, (uint32_t)(base - row * s.row_len)};
+}
+// bit j: element `off + j` of the chunk lies in a selected row, for the first `count` (<= 4) elements behind `off`
+template <bool ROWS>
+__device__ __forceinline__ uint32_t adam_selected(const AdamSeg& s, const AdamTable& t, AdamChunkRows at, uint32_t off, int count) {
+    if (!ROWS) return (1u << count) - 1u;
+    const uint32_t x = at.col + off;            // row_len < 2^30 and off < kAdamChunk: no overflow
+    uint32_t r = x / s.row_len, c = x - r * s.row_len, bits = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < count && t.mask[at.row + r] != 0) bits |= 1u << j;
+        if (++c == s.row_len) { c = 0; ++r; }
+    }
+    return bits;
+}
+
+// one chunk of a 16-B aligned tensor; FULL: every group of four lies inside the tensor.  A group whose four elements are all selected
+// moves as dwordx4; of any other group (the n mod 4 tail; ROWS: a group that straddles a selected and an unselected row) only the
+// selected elements are touched, as scalars.
+template <bool FULL, bool ROWS>
 __device__ __forceinline__ void adam_chunk_vec(const AdamSeg& s, const AdamTable& t, long long base) {
     float4 p[kAdamUnroll], g[kAdamUnroll], m[kAdamUnroll], v[kAdamUnroll];
     long long at[kAdamUnroll];
+    uint32_t sel[kAdamUnroll];
+    const AdamChunkRows rows = adam_chunk_rows<ROWS>(s, base);
 #pragma unroll
     for (int u = 0; u < kAdamUnroll; ++u) {
-        at[u] = base + 4ll * (u * kAdamThreads + (int)threadIdx.x);
-        if (FULL || at[u] + 4 <= s.n) {
+        const uint32_t off = 4u * (u * kAdamThreads + threadIdx.x);
+        at[u] = base + off;
+        const long long left = s.n - at[u];
+        const int count = (FULL || left >= 4) ? 4 : left > 0 ? (int)left : 0;
+        sel[u] = adam_selected<ROWS>(s, t, rows, off, count);
+        if (sel[u] == 0xFu) {
             p[u] = *reinterpret_cast<const float4*>(s.p + at[u]);
             g[u] = *reinterpret_cast<const float4*>(s.g + at[u]);
             m[u] = *reinterpret_cast<const float4*>(s.m + at[u]);
@@ -67,7 +110,7 @@ __device__ __forceinline__ void adam_chunk_vec(const AdamSeg& s, const AdamTable
     }
 #pragma unroll
     for (int u = 0; u < kAdamUnroll; ++u) {
-        if (FULL || at[u] + 4 <= s.n) {
+        if (sel[u] == 0xFu) {
             adam_update(p[u].x, g[u].x, m[u].x, v[u].x, t, s.step_size, s.bc2_sqrt);
             adam_update(p[u].y, g[u].y, m[u].y, v[u].y, t, s.step_size, s.bc2_sqrt);
             adam_update(p[u].z, g[u].z, m[u].z, v[u].z, t, s.step_size, s.bc2_sqrt);
@@ -75,29 +118,28 @@ __device__ __forceinline__ void adam_chunk_vec(const AdamSeg& s, const AdamTable
             *reinterpret_cast<float4*>(s.p + at[u]) = p[u];
             *reinterpret_cast<float4*>(s.m + at[u]) = m[u];
             *reinterpret_cast<float4*>(s.v + at[u]) = v[u];
-        } else {
-            for (long long i = at[u]; i < s.n; ++i) {   // the n mod 4 tail: one thread, at most three elements
-                float pe = s.p[i], me = s.m[i], ve = s.v[i];
-                adam_update(pe, s.g[i], me, ve, t, s.step_size, s.bc2_sqrt);
-                s.p[i] = pe; s.m[i] = me; s.v[i] = ve;
-            }
+        } else if ((!FULL || ROWS) && sel[u]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (sel[u] >> j & 1u) adam_update_at(s, t, at[u] + j);
         }
     }
 }
 
 // one chunk of a tensor that is only 4-B aligned: consecutive lanes, consecutive elements
+template <bool ROWS>
 __device__ __forceinline__ void adam_chunk_scalar(const AdamSeg& s, const AdamTable& t, long long base) {
+    const AdamChunkRows rows = adam_chunk_rows<ROWS>(s, base);
 #pragma unroll 4
     for (int k = 0; k < kAdamChunk / kAdamThreads; ++k) {
-        const long long i = base + k * kAdamThreads + (int)threadIdx.x;
-        if (i < s.n) {
-            float pe = s.p[i], me = s.m[i], ve = s.v[i];
-            adam_update(pe, s.g[i], me, ve, t, s.step_size, s.bc2_sqrt);
-            s.p[i] = pe; s.m[i] = me; s.v[i] = ve;
-        }
+        const uint32_t off = k * kAdamThreads + threadIdx.x;
+        if (base + off < s.n && adam_selected<ROWS>(s, t, rows, off, 1)) adam_update_at(s, t, base + off);
     }
 }
 
+// ROWS: the same step for the rows the table's mask selects (include/surfel_raster.h, sr_adam_step_rows, states when that equals the
+// dense step).  (One template, the loop in the kernel itself: behind a reference to the by-value table the segment selects go to scratch.)
+template <bool ROWS>
 __global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const AdamTable t) {
     for (uint32_t c = blockIdx.x; c < t.total_chunks; c += gridDim.x) {
         AdamSeg s = t.seg[0];
@@ -105,39 +147,69 @@ __global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(const AdamTable
         for (int k = 1; k < SR_ADAM_MAX_SEGMENTS; ++k)
             if (c >= t.seg[k].first_chunk) s = t.seg[k];   // first_chunk ascends; unused slots hold 0xFFFFFFFF
         const long long base = (long long)(c - s.first_chunk) * kAdamChunk;
-        if (!s.vec) adam_chunk_scalar(s, t, base);
-        else if (base + kAdamChunk <= s.n) adam_chunk_vec<true>(s, t, base);
-        else adam_chunk_vec<false>(s, t, base);
+        if (!s.vec) adam_chunk_scalar<ROWS>(s, t, base);
+        else if (base + kAdamChunk <= s.n) adam_chunk_vec<true, ROWS>(s, t, base);
+        else adam_chunk_vec<false, ROWS>(s, t, base);
     }
 }
 
-bool adam_supported(const SrAdamSegment* segments, int n_segments) {
+namespace {
+
+struct AdamLaunch {
+    AdamTable t{};
+    int used = 0;
+    uint32_t chunks = 0;
+    void add(float* p, const float* g, float* m, float* v, long long n, float step_size, float bc2_sqrt, uint32_t row_len) {
+        if (n == 0) return;
+        AdamSeg& s = t.seg[used++];
+        s.p = p; s.g = g; s.m = m; s.v = v;
+        s.n = n; s.step_size = step_size; s.bc2_sqrt = bc2_sqrt; s.row_len = row_len;
+        s.first_chunk = chunks;
+        s.vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0;
+        chunks += (uint32_t)((n + kAdamChunk - 1) / kAdamChunk);
+    }
+    hipError_t launch(const uint8_t* mask, double beta1, double beta2, double eps, hipStream_t stream) {
+        if (chunks == 0) return hipSuccess;
+        for (int k = used; k < SR_ADAM_MAX_SEGMENTS; ++k) t.seg[k].first_chunk = 0xFFFFFFFFu;
+        t.mask = mask;
+        t.total_chunks = chunks;
+        t.beta2 = (float)beta2; t.one_minus_beta1 = (float)(1.0 - beta1); t.one_minus_beta2 = (float)(1.0 - beta2); t.eps = (float)eps;
+        const uint32_t grid = chunks < (uint32_t)kAdamMaxBlocks ? chunks : (uint32_t)kAdamMaxBlocks;
+        if (mask) hipLaunchKernelGGL(adam_step_kernel<true>, dim3(grid), dim3(kAdamThreads), 0, stream, t);
+        else hipLaunchKernelGGL(adam_step_kernel<false>, dim3(grid), dim3(kAdamThreads), 0, stream, t);
+        return hipGetLastError();
+    }
+};
+
+template <class Segment>
+bool adam_chunks_fit(const Segment* segments, int n_segments) {
     unsigned long long chunks = 0;
     for (int k = 0; k < n_segments; ++k) chunks += ((unsigned long long)segments[k].n + kAdamChunk - 1) / kAdamChunk;
     return chunks < 0x7FFFFFFFull;
 }
 
+}  // namespace
+
+bool adam_supported(const SrAdamSegment* segments, int n_segments) { return adam_chunks_fit(segments, n_segments); }
+bool adam_rows_supported(const SrAdamRowSegment* segments, int n_segments) { return adam_chunks_fit(segments, n_segments); }
+
 hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t stream) {
-    AdamTable t{};
-    uint32_t chunks = 0;
-    int used = 0;
+    AdamLaunch l;
     for (int k = 0; k < n_segments; ++k) {
         const SrAdamSegment& a = segments[k];
-        if (a.n == 0) continue;
-        AdamSeg& s = t.seg[used++];
-        s.p = a.param; s.g = a.grad; s.m = a.exp_avg; s.v = a.exp_avg_sq;
-        s.n = a.n; s.step_size = a.step_size; s.bc2_sqrt = a.bc2_sqrt;
-        s.first_chunk = chunks;
-        s.vec = (((uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq) & 15u) == 0;
-        chunks += (uint32_t)((a.n + kAdamChunk - 1) / kAdamChunk);
+        l.add(a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n, a.step_size, a.bc2_sqrt, 1u);
     }
-    if (chunks == 0) return hipSuccess;
-    for (int k = used; k < SR_ADAM_MAX_SEGMENTS; ++k) t.seg[k].first_chunk = 0xFFFFFFFFu;
-    t.total_chunks = chunks;
-    t.beta2 = (float)beta2; t.one_minus_beta1 = (float)(1.0 - beta1); t.one_minus_beta2 = (float)(1.0 - beta2); t.eps = (float)eps;
-    const uint32_t grid = chunks < (uint32_t)kAdamMaxBlocks ? chunks : (uint32_t)kAdamMaxBlocks;
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(kAdamThreads), 0, stream, t);
-    return hipGetLastError();
+    return l.launch(nullptr, beta1, beta2, eps, stream);
+}
+
+hipError_t launch_adam_step_rows(const SrAdamRowSegment* segments, int n_segments, const uint8_t* mask, double beta1, double beta2,
+                                 double eps, hipStream_t stream) {
+    AdamLaunch l;
+    for (int k = 0; k < n_segments; ++k) {
+        const SrAdamRowSegment& a = segments[k];
+        l.add(a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n, a.step_size, a.bc2_sqrt, (uint32_t)a.row_len);
+    }
+    return l.launch(mask, beta1, beta2, eps, stream);
 }
 
 // [REF train.py:168-169, scene/gaussian_model.py:555-557] with visibility_filter = radii > 0: rows of invisible Gaussians are neither

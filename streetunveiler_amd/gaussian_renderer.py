@@ -130,28 +130,42 @@ def _plain_getters(pc):
     """True only for models whose opacity / scaling / rotation getters are exactly sigmoid / exp / normalize of `_opacity` /
     `_scaling` / `_rotation`: a SurfelModel with raw=True, or the reference's GaussianModel
     [REF scene/gaussian_model.py:63-75, 101-123].  NOT MaskGaussianModel: its getters activate `_x + _new_x * mask`
-    [REF scene/mask_gaussian.py:140-176], so the raw tensors are not what it renders (and are frozen there)."""
+    [REF scene/mask_gaussian.py:140-176], so the raw tensors are not what it renders (and are frozen there); mask_model.MaskedSurfelModel
+    serves that model and hands over what it renders through `raw_parameters()` (_offers_raw_parameters)."""
     if isinstance(pc, SurfelModel):
         return pc.raw
     return type(pc).__name__ == "GaussianModel" and getattr(pc, "fused_activations_ok", True)
 
 
+def _offers_raw_parameters(pc):
+    """A model whose getters are sigmoid / exp / normalize of something OTHER than `_opacity` / `_scaling` / `_rotation` says so with a
+    `raw_parameters()` that returns those three pre-activation tensors with their graph (mask_model.MaskedSurfelModel: base + masked delta)."""
+    return callable(getattr(pc, "raw_parameters", None))
+
+
 def _fused_activations(pc, pipe):
-    """Raw parameters go straight to the operator when asked for and when the model's getters are the plain activations;
-    any other model (MaskGaussianModel, subclasses with extra terms) silently keeps the getter path."""
-    return (getattr(pipe, "fused_activations", False) and not pipe.compute_cov3D_python and _plain_getters(pc)
-            and all(hasattr(pc, a) for a in ("_opacity", "_scaling", "_rotation")))
+    """Raw parameters go straight to the operator when asked for and when the model's getters are the plain activations of `_opacity` /
+    `_scaling` / `_rotation` or of what its `raw_parameters()` returns; any other model (the reference's MaskGaussianModel, subclasses
+    with extra terms) silently keeps the getter path."""
+    if not getattr(pipe, "fused_activations", False) or pipe.compute_cov3D_python:
+        return False
+    return _offers_raw_parameters(pc) or (_plain_getters(pc) and all(hasattr(pc, a) for a in ("_opacity", "_scaling", "_rotation")))
+
+
+def _raw_parameters(pc):
+    return pc.raw_parameters() if _offers_raw_parameters(pc) else (pc._opacity, pc._scaling, pc._rotation)
 
 
 def _geometry_inputs(pc, pipe, screenspace_points, mask, scaling_modifier):
     fused = _fused_activations(pc, pipe)
+    raw_opacity, raw_scaling, raw_rotation = _raw_parameters(pc) if fused else (None, None, None)
     means3D, means2D = _sel(pc.get_xyz, mask), _sel(screenspace_points, mask)
-    opacity = _sel(pc._opacity if fused else pc.get_opacity, mask)
+    opacity = _sel(raw_opacity if fused else pc.get_opacity, mask)
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = _sel(pc.get_covariance(scaling_modifier), mask)
     elif fused:
-        scales, rotations = _sel(pc._scaling, mask), _sel(pc._rotation, mask)
+        scales, rotations = _sel(raw_scaling, mask), _sel(raw_rotation, mask)
     else:
         scales, rotations = _sel(pc.get_scaling, mask), _sel(pc.get_rotation, mask)
     try:

@@ -2,13 +2,16 @@
 scene/gaussian_model.py:166-180, 555-557]:
 
     SurfelAdam            drop-in for the `torch.optim.Adam(l, lr=0.0, eps=1e-15)` of `training_setup`: the same `param_groups`, the same
-                          per-parameter state (`step`, `exp_avg`, `exp_avg_sq`), one kernel launch per step for up to 8 tensors
+                          per-parameter state (`step`, `exp_avg`, `exp_avg_sq`), one kernel launch per step for up to 8 tensors;
+                          `row_mask=`: the step restricted to the rows a per-Gaussian mask selects (the masked re-optimisation model)
     adam_step             the raw call under it;  adam_step_float64: the same update in plain float64 torch, the checker
     densification_stats   `max_radii2D`, `xyz_gradient_accum` and `denom` of the visible Gaussians in one kernel, no boolean indexing;
                           densification_stats_torch: the reference's three lines, checker and timing baseline
 
 The step is dense on purpose: Adam's moments decay and the parameters keep moving for Gaussians a view does not see (their gradient is
-zero, their exp_avg is not), so skipping invisible rows would change the trajectory."""
+zero, their exp_avg is not), so skipping invisible rows would change the trajectory.  `row_mask` is for rows whose gradient AND moments
+are zero for as long as the optimizer lives -- the masked-out rows of the reference's MaskGaussianModel -- where skipping changes nothing
+(include/surfel_raster.h, sr_adam_step_rows, states the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -40,12 +43,33 @@ def _check_adam_tensor(what, k, t, like=None):
         raise ValueError(f"{what}[{k}]: {tuple(t.shape)} on {t.device} does not match its parameter ({tuple(like.shape)} on {like.device})")
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, eps):
+def row_mask_bytes(mask):
+    """A per-row mask as the kernels read it: uint8 [P], non-zero = selected.  bool is reinterpreted (no copy); anything else is taken
+    as `!= 0` (the reference only ever builds 0 / 1 masks, as bool or as float)."""
+    if mask.dim() != 1:
+        raise ValueError(f"a row mask must be [P]; got {tuple(mask.shape)}")
+    if mask.dtype != torch.bool:
+        mask = mask != 0
+    return mask.contiguous().view(torch.uint8)
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, eps, row_mask=None):
     """One Adam update of `params`, `exp_avgs` and `exp_avg_sqs` in place, on the current stream of each tensor's device: one launch per
     device and 8 tensors.  `lrs[i]` is tensor i's learning rate and `steps[i]` its step count with this step included (1 for the first
     update); the bias corrections are formed from them in double.  float32, contiguous parameters and state; a non-contiguous
-    gradient is made contiguous."""
+    gradient is made contiguous.
+    The step writes through raw pointers, so it bumps the in-place version of every parameter and state tensor itself, as a torch
+    in-place operation would: autograd and version-keyed caches (mask_model.MaskedSurfelModel's compose) see that they have changed.
+    `row_mask` ([P], bool or 0 / 1): every tensor is [P, ...] and only the rows with a non-zero mask are updated; the other rows of the
+    parameters and the state are neither read nor written, and what their gradient rows hold is never seen (sr_adam_step_rows)."""
     n = len(params)
+    if row_mask is not None:
+        row_mask = row_mask_bytes(row_mask)
+        for k, p in enumerate(params):
+            if p.dim() < 1 or p.shape[0] != row_mask.numel():
+                raise ValueError(f"params[{k}] is {tuple(p.shape)}: with row_mask its leading dimension must be the mask's length {row_mask.numel()}")
+            if p.device != row_mask.device:
+                raise ValueError(f"params[{k}] is on {p.device}, row_mask on {row_mask.device}")
     if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(lrs) == len(steps) == n):
         raise ValueError("params, grads, exp_avgs, exp_avg_sqs, lrs and steps must have one entry per tensor")
     by_device = {}
@@ -64,15 +88,27 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, ep
             raise ValueError(f"steps[{k}] = {steps[k]}: the step count includes this step, so it starts at 1")
         step_size, bc2_sqrt = _bias_terms(lrs[k], steps[k], beta1, beta2)
         g = g.contiguous()
-        seg = L.SrAdamSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step_size, bc2_sqrt)
-        by_device.setdefault(p.device, []).append((seg, g))      # (g: a contiguous copy stays alive until the launch is enqueued)
+        if row_mask is None:
+            seg = L.SrAdamSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step_size, bc2_sqrt)
+        else:
+            seg = L.SrAdamRowSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step_size, bc2_sqrt,
+                                     p.numel() // max(1, p.shape[0]))
+        by_device.setdefault(p.device, []).append((seg, g, (p, m, v)))      # (g: a contiguous copy stays alive until the launch is enqueued)
     lib = L.load()
     for dev, entries in by_device.items():
         with torch.cuda.device(dev):
             for at in range(0, len(entries), ADAM_MAX_SEGMENTS):
                 part = entries[at:at + ADAM_MAX_SEGMENTS]
-                table = (L.SrAdamSegment * len(part))(*[e[0] for e in part])
-                L.check(lib.sr_adam_step(table, len(part), float(beta1), float(beta2), float(eps), _stream(dev)), "sr_adam_step")
+                if row_mask is None:
+                    table = (L.SrAdamSegment * len(part))(*[e[0] for e in part])
+                    L.check(lib.sr_adam_step(table, len(part), float(beta1), float(beta2), float(eps), _stream(dev)), "sr_adam_step")
+                else:
+                    table = (L.SrAdamRowSegment * len(part))(*[e[0] for e in part])
+                    L.check(lib.sr_adam_step_rows(table, len(part), row_mask.numel(), C.c_void_p(row_mask.data_ptr()), float(beta1), float(beta2),
+                                                  float(eps), _stream(dev)), "sr_adam_step_rows")
+                for e in part:
+                    for t in e[2]:
+                        torch.autograd.graph.increment_version(t)
 
 
 def adam_step_float64(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, eps):
@@ -100,10 +136,18 @@ class SurfelAdam(torch.optim.Optimizer):
     (they pick one of torch's implementations of the same step).  CPU tensors raise SurfelRasterError: there is no CPU path.
 
     The learning rate and the bias corrections travel BY VALUE in each launch: `step()` is not meant to be captured into a HIP graph (a
-    replay would repeat the captured step's step size)."""
+    replay would repeat the captured step's step size).
+
+    `row_mask` (not an Adam option; it is no part of `param_groups` or `state_dict`, so `load_state_dict` leaves it alone and a
+    rebuilt optimizer has to be given it again; with a callable that is a lambda or closes over its model, as MaskedSurfelModel's does,
+    the optimizer cannot be pickled and a deep copy keeps reading the ORIGINAL model's mask): a [P] tensor, or a callable returning the
+    current one, read at every step.  Every parameter's leading dimension must then be P, and only the rows with a non-zero mask are stepped
+    (sr_adam_step_rows): equal to the dense step as long as the other rows have zero gradients and zero moments, which is what the
+    masked re-optimisation model guarantees (streetunveiler_amd.mask_model).  Without it nothing changes."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
-                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, row_mask=None):
+        self.row_mask = row_mask
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -145,6 +189,7 @@ class SurfelAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        row_mask = self.row_mask() if callable(self.row_mask) else self.row_mask
         calls = {}          # (beta1, beta2, eps) -> the argument lists of one adam_step call
         for group in self.param_groups:
             self._check_group(group)
@@ -174,7 +219,7 @@ class SurfelAdam(torch.optim.Optimizer):
         for (beta1, beta2, eps), (params, grads, exp_avgs, exp_avg_sqs, lrs, steps) in calls.items():
             for s in steps:
                 s += 1
-            adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, [float(s) for s in steps], beta1, beta2, eps)
+            adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, [float(s) for s in steps], beta1, beta2, eps, row_mask=row_mask)
         return loss
 
 
