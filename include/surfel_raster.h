@@ -390,6 +390,50 @@ int sr_image_loss_backward(int32_t image_width, int32_t image_height, int32_t ch
                            const float* gt, const float* sky, const float* alpha, const void* workspace, size_t workspace_bytes,
                            const float* g_loss, float* g_image, float* g_sky, float* g_alpha, void* stream);
 
+/* The other losses of a training iteration == train.py:87-88 and :124-143 of the reference (and 1_optimization.py:249-256 of its
+ * unveiling stage), csrc/aux_loss.hip.  Every forward is one kernel of per-workgroup partial sums + one workgroup that adds them in a
+ * fixed order; every backward is one kernel that reads the upstream scalar g_loss from DEVICE memory.  The arithmetic is float64 on
+ * float32 data: each loss and each gradient element is the float64 value of its expression rounded to float32 once.  No atomics (two
+ * calls give the same bits), no host read-back, nothing allocated: the caller owns the workspace of sr_aux_loss_workspace_bytes(n)
+ * bytes, n = the pixels (W * H) or Gaussians (P) of the call; only the forwards use it, and nothing in it is kept for the backward.
+ *
+ * sr_semantic_ce_*: logits x [C,H,W], C <= SR_CE_MAX_CLASSES; weight = C HOST floats read during the call (NULL: all ones) and carried
+ * in the launch, so a captured graph replays them.  label_bytes selects the target: 0 = probabilities t [C,H,W] float32, term
+ * -sum_c w_c t_c (x_c - lse(x)); 1 / 4 / 8 = an [H,W] label map of uint8 / int32 / int64, term -w[l] (x[l] - lse(x)), where a label
+ * outside 0..C-1 gives 0 * lse(x) (the all-zero one-hot row of the reference).  out1[0] = (sum of terms) / (W * H) ==
+ * F.cross_entropy(x[None], t[None], weight=w): with probability targets torch divides by the pixel count, not by the weights' sum.
+ * g_logits[c] = (g / N) (softmax_c S - w_c t_c), S = sum_k w_k t_k (labels: w[l], or 0 outside the range).
+ * Differences from torch, on purpose: with LABELS an -inf logit of another class leaves the term finite (torch's one-hot product forms
+ * 0 * -inf = NaN; the probability form does that too); a NaN logit of any class makes the loss NaN in both forms.
+ *
+ * sr_surface_reg_*: rend_normal, surf_normal [3,H,W], rend_dist [1,H,W]; normal = mean(1 - sum_c rn_c sn_c), dist = mean(rend_dist);
+ * out3 = {lambda_normal normal + lambda_dist dist, lambda_normal normal, lambda_dist dist}.  The backward writes the gradients whose
+ * pointers are given: g_rend_normal = -(g lambda_normal / N) surf_normal, g_surf_normal = -(g lambda_normal / N) rend_normal,
+ * g_rend_dist = g lambda_dist / N; the two normal maps are needed only where one of their gradients is asked for, rend_dist never.  A
+ * weight of 0 is not special: the maps are read and multiplied by it.
+ *
+ * sr_opacity_shrink_*: out1[0] = mean(sigmoid(opacity[P])) of RAW opacities, g = (g / P) s (1 - s); activated != 0: the values are
+ * opacities already, mean(opacity) and g / P.
+ *
+ * SR_ERR_INVALID_ARGUMENT before any launch for W, H or P < 1, C outside 1..SR_CE_MAX_CLASSES, a label_bytes other than 0, 1, 4, 8 and
+ * a missing pointer; SR_ERR_BUFFER_TOO_SMALL for a short workspace; SR_ERR_UNSUPPORTED for more than 2^31 - 1 workgroups of 256
+ * elements.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+#define SR_CE_MAX_CLASSES 8
+size_t sr_aux_loss_workspace_bytes(int64_t n);
+int sr_semantic_ce_forward(int32_t image_width, int32_t image_height, int32_t classes, const float* logits, const void* target,
+                           int32_t label_bytes, const float* weight, void* workspace, size_t workspace_bytes, float* out1, void* stream);
+int sr_semantic_ce_backward(int32_t image_width, int32_t image_height, int32_t classes, const float* logits, const void* target,
+                            int32_t label_bytes, const float* weight, const float* g_loss, float* g_logits, void* stream);
+int sr_surface_reg_forward(int32_t image_width, int32_t image_height, const float* rend_normal, const float* surf_normal,
+                           const float* rend_dist, double lambda_normal, double lambda_dist, void* workspace, size_t workspace_bytes,
+                           float* out3, void* stream);
+int sr_surface_reg_backward(int32_t image_width, int32_t image_height, const float* rend_normal, const float* surf_normal,
+                            double lambda_normal, double lambda_dist, const float* g_loss, float* g_rend_normal, float* g_surf_normal,
+                            float* g_rend_dist, void* stream);
+int sr_opacity_shrink_forward(int64_t P, const float* opacity, int32_t activated, void* workspace, size_t workspace_bytes, float* out1,
+                              void* stream);
+int sr_opacity_shrink_backward(int64_t P, const float* opacity, int32_t activated, const float* g_loss, float* g_opacity, void* stream);
+
 /* One Adam step over up to SR_ADAM_MAX_SEGMENTS float32 tensors in ONE launch == torch.optim.Adam (no weight decay, no amsgrad, not
  * maximising) as the reference builds it in scene/gaussian_model.py:171-180 and steps it in train.py:197.  Per element, in float32 and
  * in the order of torch's single-tensor path, with correctly rounded division and square root and no contraction:

@@ -12,7 +12,9 @@ _CLUSTER = ("radius_components", "cluster_instance_with_mask", "cluster_semantic
 _DENSIFY = ("densify_and_prune", "prune_points", "densify_and_prune_tensors", "densify_and_prune_torch")
 _TSDF = ("TsdfViews", "unbounded_tsdf", "unbounded_tsdf_grid", "unbounded_tsdf_torch", "sdf_function", "grid_coordinates")
 _MASK_MODEL = ("MaskedSurfelModel", "compose_masked", "compose_masked_torch")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL)
+_AUX_LOSS = ("semantic_cross_entropy", "surface_regularisers", "opacity_shrink", "SemanticCrossEntropy", "semantic_cross_entropy_torch",
+             "surface_regularisers_torch", "opacity_shrink_torch")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -34,4 +36,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _MASK_MODEL:
         from . import mask_model
         return getattr(mask_model, name)
+    if name in _AUX_LOSS:
+        from . import aux_loss
+        return getattr(aux_loss, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

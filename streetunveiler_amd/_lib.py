@@ -112,7 +112,9 @@ EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_e
            "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
            "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius",
            "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply", "sr_tsdf_fuse", "sr_tsdf_fuse_grid",
-           "sr_adam_step_rows", "sr_mask_compose", "sr_mask_compose_backward"]
+           "sr_adam_step_rows", "sr_mask_compose", "sr_mask_compose_backward",
+           "sr_aux_loss_workspace_bytes", "sr_semantic_ce_forward", "sr_semantic_ce_backward", "sr_surface_reg_forward",
+           "sr_surface_reg_backward", "sr_opacity_shrink_forward", "sr_opacity_shrink_backward"]
 
 _lib = None
 
@@ -196,6 +198,16 @@ def load():
     lib.sr_image_loss_workspace_bytes.restype = C.c_size_t
     lib.sr_image_loss_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]
     lib.sr_image_loss_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5
+    lib.sr_aux_loss_workspace_bytes.argtypes = [C.c_int64]
+    lib.sr_aux_loss_workspace_bytes.restype = C.c_size_t
+    lib.sr_semantic_ce_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t,
+                                                             C.c_void_p, C.c_void_p]
+    lib.sr_semantic_ce_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 3
+    lib.sr_surface_reg_forward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_size_t,
+                                                                                      C.c_void_p, C.c_void_p]
+    lib.sr_surface_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 5
+    lib.sr_opacity_shrink_forward.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.sr_opacity_shrink_backward.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sr_adam_step.argtypes = [C.POINTER(SrAdamSegment), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.sr_adam_step_rows.argtypes = [C.POINTER(SrAdamRowSegment), C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.sr_mask_compose.argtypes = [C.c_int32, C.c_int32, C.POINTER(SrMaskTensors), C.POINTER(SrMaskTensors), C.c_void_p, C.c_uint32,

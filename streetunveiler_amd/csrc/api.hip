@@ -981,6 +981,101 @@ int sr_image_loss_backward(int32_t W, int32_t H, int32_t C, float lambda_dssim, 
     return SR_OK;
 }
 
+size_t sr_aux_loss_workspace_bytes(int64_t n) { return n > 0 ? aux_loss_workspace_bytes((size_t)n) : 0; }
+
+namespace {
+
+// shared refusals of the auxiliary losses: the element count, then (forwards only: workspace_bytes != nullptr) the workspace
+int aux_count(const char* what, int64_t n, const void* workspace, const size_t* workspace_bytes) {
+    if (!aux_loss_supported((size_t)n)) return fail(SR_ERR_UNSUPPORTED, "%s: %lld elements are beyond the launch limits", what, (long long)n);
+    if (!workspace_bytes) return SR_OK;
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "%s: workspace is NULL", what);
+    if (*workspace_bytes < aux_loss_workspace_bytes((size_t)n))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "%s: workspace %zu < %zu", what, *workspace_bytes, aux_loss_workspace_bytes((size_t)n));
+    return SR_OK;
+}
+
+int semantic_ce_args(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                     CeArgs* a, CeTarget* form) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (C < 1 || C > SR_CE_MAX_CLASSES) return fail(SR_ERR_INVALID_ARGUMENT, "%d classes: not in 1..%d", C, SR_CE_MAX_CLASSES);
+    if (label_bytes != 0 && label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail(SR_ERR_INVALID_ARGUMENT, "label_bytes %d: not 0 (probabilities), 1, 4 or 8", label_bytes);
+    if (!logits || !target) return fail(SR_ERR_INVALID_ARGUMENT, "logits / target is NULL");
+    static_assert(SR_CE_MAX_CLASSES == kCeMaxClasses, "the header's class limit is the kernels'");
+    *form = static_cast<CeTarget>(label_bytes);
+    a->C = C;
+    a->N = (size_t)W * (size_t)H;
+    for (int c = 0; c < kCeMaxClasses; ++c) a->w[c] = c < C ? (weight ? weight[c] : 1.f) : 0.f;
+    a->x = logits;
+    a->target = target;
+    return SR_OK;
+}
+
+}  // namespace
+
+int sr_semantic_ce_forward(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                           void* workspace, size_t workspace_bytes, float* out1, void* stream) {
+    CeArgs a;
+    CeTarget form;
+    if (int rc = semantic_ce_args(W, H, C, logits, target, label_bytes, weight, &a, &form)) return rc;
+    if (!out1) return fail(SR_ERR_INVALID_ARGUMENT, "out1 is NULL");
+    if (int rc = aux_count("sr_semantic_ce_forward", (int64_t)a.N, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_semantic_ce_forward(a, form, workspace, out1, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_semantic_ce_backward(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                            const float* g_loss, float* g_logits, void* stream) {
+    CeArgs a;
+    CeTarget form;
+    if (int rc = semantic_ce_args(W, H, C, logits, target, label_bytes, weight, &a, &form)) return rc;
+    if (!g_loss || !g_logits) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_logits is NULL");
+    if (int rc = aux_count("sr_semantic_ce_backward", (int64_t)a.N, nullptr, nullptr)) return rc;
+    SR_HIP(launch_semantic_ce_backward(a, form, g_loss, g_logits, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_surface_reg_forward(int32_t W, int32_t H, const float* rend_normal, const float* surf_normal, const float* rend_dist, double lambda_normal,
+                           double lambda_dist, void* workspace, size_t workspace_bytes, float* out3, void* stream) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (!rend_normal || !surf_normal || !rend_dist || !out3) return fail(SR_ERR_INVALID_ARGUMENT, "rend_normal / surf_normal / rend_dist / out3 is NULL");
+    const SurfaceRegArgs a{(size_t)W * (size_t)H, lambda_normal, lambda_dist, rend_normal, surf_normal, rend_dist};
+    if (int rc = aux_count("sr_surface_reg_forward", (int64_t)a.N, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_surface_reg_forward(a, workspace, out3, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_surface_reg_backward(int32_t W, int32_t H, const float* rend_normal, const float* surf_normal, double lambda_normal, double lambda_dist,
+                            const float* g_loss, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist, void* stream) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (!g_loss) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss is NULL");
+    if (g_rend_normal && !surf_normal) return fail(SR_ERR_INVALID_ARGUMENT, "g_rend_normal is asked for without surf_normal");
+    if (g_surf_normal && !rend_normal) return fail(SR_ERR_INVALID_ARGUMENT, "g_surf_normal is asked for without rend_normal");
+    const SurfaceRegArgs a{(size_t)W * (size_t)H, lambda_normal, lambda_dist, rend_normal, surf_normal, nullptr};
+    if (int rc = aux_count("sr_surface_reg_backward", (int64_t)a.N, nullptr, nullptr)) return rc;
+    if (!g_rend_normal && !g_surf_normal && !g_rend_dist) return SR_OK;
+    SR_HIP(launch_surface_reg_backward(a, g_loss, g_rend_normal, g_surf_normal, g_rend_dist, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_opacity_shrink_forward(int64_t P, const float* opacity, int32_t activated, void* workspace, size_t workspace_bytes, float* out1, void* stream) {
+    if (P < 1) return fail(SR_ERR_INVALID_ARGUMENT, "P %lld < 1", (long long)P);
+    if (!opacity || !out1) return fail(SR_ERR_INVALID_ARGUMENT, "opacity / out1 is NULL");
+    if (int rc = aux_count("sr_opacity_shrink_forward", P, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_opacity_shrink_forward((size_t)P, opacity, activated != 0, workspace, out1, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_opacity_shrink_backward(int64_t P, const float* opacity, int32_t activated, const float* g_loss, float* g_opacity, void* stream) {
+    if (P < 1) return fail(SR_ERR_INVALID_ARGUMENT, "P %lld < 1", (long long)P);
+    if (!g_loss || !g_opacity) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_opacity is NULL");
+    if (!activated && !opacity) return fail(SR_ERR_INVALID_ARGUMENT, "opacity is NULL");
+    if (int rc = aux_count("sr_opacity_shrink_backward", P, nullptr, nullptr)) return rc;
+    SR_HIP(launch_opacity_shrink_backward((size_t)P, opacity, activated != 0, g_loss, g_opacity, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream) {
     if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
     if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)

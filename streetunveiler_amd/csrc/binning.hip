@@ -131,6 +131,9 @@ __global__ __launch_bounds__(kXpThreads) void expand_scatter_kernel(
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t n = n_dev ? *n_dev : n_host;
     const uint32_t base = blockIdx.x * (uint32_t)kInputs;
+    // no item at all (nothing visible, or the capacity guard zeroed the count of an overflowed frame): no block reaches the store of
+    // the column count below, and pass Y would take its item count from whatever the caller's buffer held
+    if (AXIS == 0 && n == 0 && blockIdx.x == 0 && tid == 0) *n_columns_out = 0;
     if (base >= n) return;
     const int n_items = (int)min((uint32_t)kInputs, n - base);
     uint32_t E;   // expanded slots of this block

@@ -1,8 +1,8 @@
 // launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
-// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, DensifyRule and the three Tsdf structs, which their
-// kernels take by value.
+// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, DensifyRule and the three Tsdf
+// structs, which their kernels take by value.
 #pragma once
 #include "common.h"
 
@@ -162,6 +162,34 @@ size_t image_loss_partial_bytes();
 hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s);
 hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
                                       float* g_alpha, hipStream_t s);
+
+// ---- aux_loss.hip --------------------------------------------------------------------------------------------------------------------
+constexpr int kCeMaxClasses = 8;
+enum class CeTarget { kProbabilities = 0, kLabelsU8 = 1, kLabelsI32 = 4, kLabelsI64 = 8 };   // the labels' values are their widths in bytes
+struct CeArgs {            // a kernel parameter, by value: the class weights travel in the launch
+    int C;
+    size_t N;              // H * W
+    float w[kCeMaxClasses];
+    const float* x;        // [C,H,W] logits
+    const void* target;    // [H,W] labels or [C,H,W] float probabilities
+};
+struct SurfaceRegArgs {    // a kernel parameter, by value
+    size_t N;
+    double lambda_normal, lambda_dist;
+    const float* rend_normal;   // [3,H,W]
+    const float* surf_normal;   // [3,H,W]
+    const float* rend_dist;     // [1,H,W]
+};
+bool aux_loss_supported(size_t n);              // the element counts the launches below can address
+size_t aux_loss_workspace_bytes(size_t n);      // per-block partial sums of n pixels / Gaussians
+hipError_t launch_semantic_ce_forward(const CeArgs& a, CeTarget form, void* workspace, float* out1, hipStream_t s);
+hipError_t launch_semantic_ce_backward(const CeArgs& a, CeTarget form, const float* g_loss, float* g_x, hipStream_t s);
+hipError_t launch_surface_reg_forward(const SurfaceRegArgs& a, void* workspace, float* out3, hipStream_t s);
+// a NULL gradient pointer is skipped
+hipError_t launch_surface_reg_backward(const SurfaceRegArgs& a, const float* g_loss, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist,
+                                       hipStream_t s);
+hipError_t launch_opacity_shrink_forward(size_t P, const float* opacity, bool activated, void* workspace, float* out1, hipStream_t s);
+hipError_t launch_opacity_shrink_backward(size_t P, const float* opacity, bool activated, const float* g_loss, float* g_opacity, hipStream_t s);
 
 // ---- optimizer.hip -------------------------------------------------------------------------------------------------------------------
 bool adam_supported(const SrAdamSegment* segments, int n_segments);
