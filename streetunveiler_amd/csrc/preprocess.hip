@@ -6,20 +6,13 @@
 // (one thread per Gaussian, ~230 B in / ~90 B out), the extra non-fused ops are free.
 //
 // Behavioural contract: SURVEY.md Appendix A.2 / A.6; operator inputs
-// [REF /root/reference/gaussian_renderer/__init__.py:56-138]; SH polynomial
+// [REF /root/reference/gaussian_renderer/__init__.py:56-138]; SH polynomial (sh.h)
 // [REF /root/reference/utils/sh_utils.py:57-112]; quaternion convention
 // [REF /root/reference/utils/general_utils.py:85-98].
 #include "launch.h"
+#include "sh.h"
 
 namespace sr {
-
-__device__ __constant__ float kSH_C0 = 0.28209479177387814f;
-__device__ __constant__ float kSH_C1 = 0.4886025119029199f;
-__device__ __constant__ float kSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                            -1.0925484305920792f, 0.5462742152960396f};
-__device__ __constant__ float kSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                            0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                            -0.5900435899266435f};
 
 __device__ __forceinline__ void quat_to_R(const float4 q, float R[9]) {
     const float r = q.x, x = q.y, y = q.z, z = q.w;
@@ -98,40 +91,11 @@ __device__ __forceinline__ void sh_rows_from_lds(float* __restrict__ out, int ba
     }
 }
 
-// colour = SH(deg, sh, dir) + 0.5, clamped at 0 (flags recorded)  [REF utils/sh_utils.py:57-112]
-template <class Row>
-__device__ __forceinline__ void sh_to_rgb(int deg, const Row sh, float dx, float dy, float dz, float rgb[3], uint8_t& clamped) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float res = kSH_C0 * sh[c];
-        if (deg > 0) {
-            const float x = dx, y = dy, z = dz;
-            res = res - kSH_C1 * y * sh[3 + c] + kSH_C1 * z * sh[6 + c] - kSH_C1 * x * sh[9 + c];
-            if (deg > 1) {
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                res = res + kSH_C2[0] * xy * sh[12 + c] + kSH_C2[1] * yz * sh[15 + c] +
-                      kSH_C2[2] * (2.f * zz - xx - yy) * sh[18 + c] + kSH_C2[3] * xz * sh[21 + c] +
-                      kSH_C2[4] * (xx - yy) * sh[24 + c];
-                if (deg > 2) {
-                    res = res + kSH_C3[0] * y * (3.f * xx - yy) * sh[27 + c] + kSH_C3[1] * xy * z * sh[30 + c] +
-                          kSH_C3[2] * y * (4.f * zz - xx - yy) * sh[33 + c] +
-                          kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * sh[36 + c] +
-                          kSH_C3[4] * x * (4.f * zz - xx - yy) * sh[39 + c] +
-                          kSH_C3[5] * z * (xx - yy) * sh[42 + c] + kSH_C3[6] * x * (xx - 3.f * yy) * sh[45 + c];
-                }
-            }
-        }
-        res += 0.5f;
-        if (res < 0.f) clamped |= (uint8_t)(1u << c);
-        rgb[c] = fmaxf(res, 0.f);
-    }
-}
-
 // ---- K1's SH rows in two halves ---------------------------------------------------------------------------------------------
 // K1 is bound by how many waves fit beside its LDS (26 KB per block of 128 rows: three waves per SIMD; with half of that it runs
 // 40 % slower).  So the rows go through LDS one half at a time -- coefficients 0..7, then 8..15, 96 B each -- and the colour (and
-// the direction Jacobian) are accumulated across the two halves.  The colour keeps the exact operation order of sh_to_rgb(): the
-// cut falls between two terms of its left-to-right sum.
+// the direction Jacobian) are accumulated across the two halves (sh.h: the cut falls between two terms of the colour's left-to-right
+// sum).  The path without staging evaluates the same two halves on its row in global memory: the two paths are one function.
 constexpr int kShHalfFloats = 24, kShHalfStride = 28;   // 7 quads per row: an odd quad stride keeps per-thread ds_read_b128 conflict-free
 // `skip[row]` != 0: the row is not fetched (a Gaussian behind the near plane or masked out: its colour is never evaluated)
 __device__ __forceinline__ void sh_half_load(const float* __restrict__ shs, int base, int P, int half, int tid, const uint8_t* skip, float4 (&r)[6]) {
@@ -150,149 +114,6 @@ __device__ __forceinline__ void sh_half_store(float* s_sh, int tid, const float4
         const int f = tid + k * kPreBlock, row = f / 6, c4 = f - row * 6;
         dst[row * (kShHalfStride / 4) + c4] = r[k];
     }
-}
-// first half of sh_to_rgb(): coefficients 0..7 (lo[3 k + c])
-__device__ __forceinline__ void sh_to_rgb_lo(int deg, const float* lo, float x, float y, float z, float res[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float r = kSH_C0 * lo[c];
-        if (deg > 0) {
-            r = r - kSH_C1 * y * lo[3 + c] + kSH_C1 * z * lo[6 + c] - kSH_C1 * x * lo[9 + c];
-            if (deg > 1) {
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                r = r + kSH_C2[0] * xy * lo[12 + c] + kSH_C2[1] * yz * lo[15 + c] + kSH_C2[2] * (2.f * zz - xx - yy) * lo[18 + c] +
-                    kSH_C2[3] * xz * lo[21 + c];
-            }
-        }
-        res[c] = r;
-    }
-}
-// second half: coefficients 8..15 (hi[3 (k - 8) + c]), then the offset and the clamp
-__device__ __forceinline__ void sh_to_rgb_hi(int deg, const float* hi, float x, float y, float z, const float res[3], float rgb[3], uint8_t& clamped) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float r = res[c];
-        if (deg > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y;
-            r = r + kSH_C2[4] * (xx - yy) * hi[c];
-            if (deg > 2) {
-                r = r + kSH_C3[0] * y * (3.f * xx - yy) * hi[3 + c] + kSH_C3[1] * xy * z * hi[6 + c] +
-                    kSH_C3[2] * y * (4.f * zz - xx - yy) * hi[9 + c] +
-                    kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * hi[12 + c] +
-                    kSH_C3[4] * x * (4.f * zz - xx - yy) * hi[15 + c] +
-                    kSH_C3[5] * z * (xx - yy) * hi[18 + c] + kSH_C3[6] * x * (xx - 3.f * yy) * hi[21 + c];
-            }
-        }
-        r += 0.5f;
-        if (r < 0.f) clamped |= (uint8_t)(1u << c);
-        rgb[c] = fmaxf(r, 0.f);
-    }
-}
-// the two halves of sh_dir_jacobian(): d[3 c + axis] accumulates d rgb[c] / d dir; the second half projects and scales
-__device__ __forceinline__ void sh_dir_jacobian_lo(int deg, const float* lo, float x, float y, float z, float d[9]) {
-#pragma clang fp contract(fast)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float dx = 0.f, dy = 0.f, dz = 0.f;
-        if (deg > 0) {
-            dx = -kSH_C1 * lo[9 + c]; dy = -kSH_C1 * lo[3 + c]; dz = kSH_C1 * lo[6 + c];
-            if (deg > 1) {
-                dx += (kSH_C2[0] * y) * lo[12 + c] + (-2.f * kSH_C2[2] * x) * lo[18 + c] + (kSH_C2[3] * z) * lo[21 + c];
-                dy += (kSH_C2[0] * x) * lo[12 + c] + (kSH_C2[1] * z) * lo[15 + c] + (-2.f * kSH_C2[2] * y) * lo[18 + c];
-                dz += (kSH_C2[1] * y) * lo[15 + c] + (4.f * kSH_C2[2] * z) * lo[18 + c] + (kSH_C2[3] * x) * lo[21 + c];
-            }
-        }
-        d[3 * c] = dx; d[3 * c + 1] = dy; d[3 * c + 2] = dz;
-    }
-}
-__device__ __forceinline__ void sh_dir_jacobian_hi(int deg, const float* hi, float x, float y, float z, float len, const float d[9], float J[9]) {
-#pragma clang fp contract(fast)
-    const float inv_len = 1.f / len;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float dx = d[3 * c], dy = d[3 * c + 1], dz = d[3 * c + 2];
-        if (deg > 1) {
-            dx += (2.f * kSH_C2[4] * x) * hi[c];
-            dy += (-2.f * kSH_C2[4] * y) * hi[c];
-            if (deg > 2) {
-                dx += (6.f * kSH_C3[0] * xy) * hi[3 + c] + (kSH_C3[1] * yz) * hi[6 + c] + (-2.f * kSH_C3[2] * xy) * hi[9 + c] +
-                      (-6.f * kSH_C3[3] * xz) * hi[12 + c] + (kSH_C3[4] * (-3.f * xx + 4.f * zz - yy)) * hi[15 + c] +
-                      (2.f * kSH_C3[5] * xz) * hi[18 + c] + (3.f * kSH_C3[6] * (xx - yy)) * hi[21 + c];
-                dy += (3.f * kSH_C3[0] * (xx - yy)) * hi[3 + c] + (kSH_C3[1] * xz) * hi[6 + c] + (kSH_C3[2] * (-3.f * yy + 4.f * zz - xx)) * hi[9 + c] +
-                      (-6.f * kSH_C3[3] * yz) * hi[12 + c] + (-2.f * kSH_C3[4] * xy) * hi[15 + c] + (-2.f * kSH_C3[5] * yz) * hi[18 + c] +
-                      (-6.f * kSH_C3[6] * xy) * hi[21 + c];
-                dz += (kSH_C3[1] * xy) * hi[6 + c] + (8.f * kSH_C3[2] * yz) * hi[9 + c] + (3.f * kSH_C3[3] * (2.f * zz - xx - yy)) * hi[12 + c] +
-                      (8.f * kSH_C3[4] * xz) * hi[15 + c] + (kSH_C3[5] * (xx - yy)) * hi[18 + c];
-            }
-        }
-        const float nd = (x * dx + y * dy) + z * dz;
-        J[3 * c + 0] = (dx - x * nd) * inv_len; J[3 * c + 1] = (dy - y * nd) * inv_len; J[3 * c + 2] = (dz - z * nd) * inv_len;
-    }
-}
-
-// d rgb[c] / d centre through the SH view direction, J[3 c + k] = ((d_c - dir (dir . d_c)) / len)[k] with d_c = d rgb[c] / d dir
-// [REF the direction half of computeColorFromSH's backward, Appendix A.6].  K1 evaluates it next to the colour, from the SH row it
-// holds anyway, so that K8 needs 36 B per Gaussian instead of reading the 192-B row again.
-template <class Row>
-__device__ __forceinline__ void sh_dir_jacobian(int deg, const Row sh, float x, float y, float z, float len, float J[9]) {
-#pragma clang fp contract(fast)   // not part of the bit-exact contract with the oracle (gradients are compared with a tolerance)
-    const float inv_len = 1.f / len;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float dx = 0.f, dy = 0.f, dz = 0.f;
-        if (deg > 0) {
-            dx = -kSH_C1 * sh[9 + c]; dy = -kSH_C1 * sh[3 + c]; dz = kSH_C1 * sh[6 + c];
-            if (deg > 1) {
-                dx += (kSH_C2[0] * y) * sh[12 + c] + (-2.f * kSH_C2[2] * x) * sh[18 + c] + (kSH_C2[3] * z) * sh[21 + c] + (2.f * kSH_C2[4] * x) * sh[24 + c];
-                dy += (kSH_C2[0] * x) * sh[12 + c] + (kSH_C2[1] * z) * sh[15 + c] + (-2.f * kSH_C2[2] * y) * sh[18 + c] + (-2.f * kSH_C2[4] * y) * sh[24 + c];
-                dz += (kSH_C2[1] * y) * sh[15 + c] + (4.f * kSH_C2[2] * z) * sh[18 + c] + (kSH_C2[3] * x) * sh[21 + c];
-                if (deg > 2) {
-                    dx += (6.f * kSH_C3[0] * xy) * sh[27 + c] + (kSH_C3[1] * yz) * sh[30 + c] + (-2.f * kSH_C3[2] * xy) * sh[33 + c] +
-                          (-6.f * kSH_C3[3] * xz) * sh[36 + c] + (kSH_C3[4] * (-3.f * xx + 4.f * zz - yy)) * sh[39 + c] +
-                          (2.f * kSH_C3[5] * xz) * sh[42 + c] + (3.f * kSH_C3[6] * (xx - yy)) * sh[45 + c];
-                    dy += (3.f * kSH_C3[0] * (xx - yy)) * sh[27 + c] + (kSH_C3[1] * xz) * sh[30 + c] + (kSH_C3[2] * (-3.f * yy + 4.f * zz - xx)) * sh[33 + c] +
-                          (-6.f * kSH_C3[3] * yz) * sh[36 + c] + (-2.f * kSH_C3[4] * xy) * sh[39 + c] + (-2.f * kSH_C3[5] * yz) * sh[42 + c] +
-                          (-6.f * kSH_C3[6] * xy) * sh[45 + c];
-                    dz += (kSH_C3[1] * xy) * sh[30 + c] + (8.f * kSH_C3[2] * yz) * sh[33 + c] + (3.f * kSH_C3[3] * (2.f * zz - xx - yy)) * sh[36 + c] +
-                          (8.f * kSH_C3[4] * xz) * sh[39 + c] + (kSH_C3[5] * (xx - yy)) * sh[42 + c];
-                }
-            }
-        }
-        const float nd = (x * dx + y * dy) + z * dz;
-        J[3 * c + 0] = (dx - x * nd) * inv_len; J[3 * c + 1] = (dy - y * nd) * inv_len; J[3 * c + 2] = (dz - z * nd) * inv_len;
-    }
-}
-
-// SH adjoint: dsh[k] = basis_k(dir) * dL/drgb.  Coefficients above the active degree get 0.
-template <class RowOut>
-__device__ __forceinline__ void sh_basis_adjoint(int deg, int M, RowOut dsh, float x, float y, float z, const float gcol[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float g = gcol[c];
-        dsh[c] = kSH_C0 * g;
-        if (deg > 0) {
-            dsh[3 + c] = -kSH_C1 * y * g; dsh[6 + c] = kSH_C1 * z * g; dsh[9 + c] = -kSH_C1 * x * g;
-            if (deg > 1) {
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                dsh[12 + c] = kSH_C2[0] * xy * g; dsh[15 + c] = kSH_C2[1] * yz * g;
-                dsh[18 + c] = kSH_C2[2] * (2.f * zz - xx - yy) * g;
-                dsh[21 + c] = kSH_C2[3] * xz * g; dsh[24 + c] = kSH_C2[4] * (xx - yy) * g;
-                if (deg > 2) {
-                    dsh[27 + c] = kSH_C3[0] * y * (3.f * xx - yy) * g;
-                    dsh[30 + c] = kSH_C3[1] * xy * z * g;
-                    dsh[33 + c] = kSH_C3[2] * y * (4.f * zz - xx - yy) * g;
-                    dsh[36 + c] = kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
-                    dsh[39 + c] = kSH_C3[4] * x * (4.f * zz - xx - yy) * g;
-                    dsh[42 + c] = kSH_C3[5] * z * (xx - yy) * g;
-                    dsh[45 + c] = kSH_C3[6] * x * (xx - 3.f * yy) * g;
-                }
-            }
-        }
-    }
-    const int used = (deg + 1) * (deg + 1);
-    for (int k = used * 3; k < M * 3; ++k) dsh[k] = 0.f;
 }
 
 // The splat -> pixel transform (Appendix A.2 step 3) and the AABB centre (step 5), as K1 evaluates them.  K8 calls the SAME functions on the
@@ -446,10 +267,15 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_forward_kernel(
                     if (kLdsSH) {
                         need_sh = true; sdx = dx; sdy = dy; sdz = dz; slen = len; sradius = radius;   // (q4 is completed below)
                     } else {
-                        float J[9];
-                        sh_to_rgb(f.sh_degree, shs + (size_t)i * f.sh_coeffs * 3, dx, dy, dz, rgb, out_clamped);
+                        const float* row = shs + (size_t)i * f.sh_coeffs * 3;   // (M < 16: nothing above the active degree is read)
+                        float res[3] = {0.f, 0.f, 0.f}, b[16];
+                        sh_basis(f.sh_degree, dx, dy, dz, b);
+                        sh_to_rgb_lo(f.sh_degree, b, row, res);
+                        sh_to_rgb_hi(f.sh_degree, b, row + kShHalfFloats, res, rgb, out_clamped);
                         if (f.sh_jac) {   // (NULL with SR_FLAG_FORWARD_ONLY: K8 is the only reader)
-                            sh_dir_jacobian(f.sh_degree, shs + (size_t)i * f.sh_coeffs * 3, dx, dy, dz, len, J);
+                            float dd[9], J[9];
+                            sh_dir_jacobian_lo(f.sh_degree, row, dx, dy, dz, dd);
+                            sh_dir_jacobian_hi(f.sh_degree, row + kShHalfFloats, dx, dy, dz, len, dd, J);
 #pragma unroll
                             for (int k = 0; k < 9; ++k) f.sh_jac[9 * (size_t)i + k] = J[k];
                         }
@@ -469,10 +295,11 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_forward_kernel(
     }
     if (kLdsSH) {
         const float* row = s_sh + tid * kShHalfStride;
-        float res[3] = {0.f, 0.f, 0.f}, dd[9];
+        float res[3] = {0.f, 0.f, 0.f}, dd[9], b[16];
         const bool want_jac = f.sh_jac != nullptr;   // (NULL with SR_FLAG_FORWARD_ONLY: K8 is the only reader of the 36-B rows)
         if (need_sh) {
-            sh_to_rgb_lo(f.sh_degree, row, sdx, sdy, sdz, res);
+            sh_basis(f.sh_degree, sdx, sdy, sdz, b);
+            sh_to_rgb_lo(f.sh_degree, b, row, res);
             if (want_jac) sh_dir_jacobian_lo(f.sh_degree, row, sdx, sdy, sdz, dd);
         }
         __syncthreads();   // every thread is done with the first halves
@@ -481,7 +308,8 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_forward_kernel(
         float J[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (need_sh) {
             float rgb[3];
-            sh_to_rgb_hi(f.sh_degree, row, sdx, sdy, sdz, res, rgb, out_clamped);
+            sh_basis(f.sh_degree, sdx, sdy, sdz, b);   // again: 15 registers less across the barrier, which keep the fifth wave per SIMD
+            sh_to_rgb_hi(f.sh_degree, b, row, res, rgb, out_clamped);
             if (want_jac) sh_dir_jacobian_hi(f.sh_degree, row, sdx, sdy, sdz, slen, dd, J);
             q3.w = rgb[0];
             q4 = make_float4(rgb[1], rgb[2], q4.z, sradius);
@@ -537,10 +365,47 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_forward_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// K8: per-Gaussian backward (Appendix A.6).  First sums the Gaussian's per-(tile, Gaussian) gradient records: K7 stores
-// them in emission order, where they form the contiguous span [first, first + tiles_touched) (first[] = FrameDev.first, a compact
-// array by Gaussian id written by K3); ascending order -> deterministic.  Slots whose `written` flag is clear got no record from K7 (no pixel
-// contributed) and are skipped without being read.
+// The walk over a Gaussian's per-(tile, Gaussian) gradient records: K7 stores them in emission order, where they form the contiguous
+// span [first, end) (first[] = FrameDev.first, a compact array by Gaussian id written by K3).  g[q - Q0] = the sum of quad q of the
+// span's records (kStride quads each) for q in [Q0, Q1), added in ascending order -> deterministic, and the one order every caller sums
+// in.  K7 writes a record only where some pixel contributed -- about 40 % of a Gaussian's span -- and sets the slot's byte in `written`:
+// the other slots are skipped without being read.  Four records per trip; the flags of the next trip are in flight behind this trip's
+// records.
+// ---------------------------------------------------------------------------------------------
+template <int kStride, int Q0, int Q1>
+__device__ __forceinline__ void sum_gradient_records(uint32_t first, uint32_t end, const uint8_t* __restrict__ written,
+                                                     const float4* __restrict__ inst_grads, float4 (&g)[Q1 - Q0]) {
+    constexpr int kTrip = 4, kQ = Q1 - Q0;
+#pragma unroll
+    for (int k = 0; k < kQ; ++k) g[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto load_flags = [&](uint32_t e, uint8_t (&fl)[kTrip]) {
+#pragma unroll
+        for (int t = 0; t < kTrip; ++t) fl[t] = e + t < end ? written[e + t] : (uint8_t)0;
+    };
+    uint8_t fl[kTrip], fn[kTrip] = {0, 0, 0, 0};
+    load_flags(first, fl);
+    for (uint32_t e = first; e < end; e += kTrip) {
+        if (e + kTrip < end) load_flags(e + kTrip, fn);
+        float4 a[kTrip][kQ];
+#pragma unroll
+        for (int t = 0; t < kTrip; ++t) {
+            const float4* gr = inst_grads + (size_t)(e + t) * kStride + Q0;
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) a[t][k] = fl[t] ? gr[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int t = 0; t < kTrip; ++t) {
+            if (fl[t]) {
+#pragma unroll
+                for (int k = 0; k < kQ; ++k) { g[k].x += a[t][k].x; g[k].y += a[t][k].y; g[k].z += a[t][k].z; g[k].w += a[t][k].w; }
+            }
+            fl[t] = fn[t];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// K8: per-Gaussian backward (Appendix A.6).  First sums the Gaussian's gradient records.
 // ---------------------------------------------------------------------------------------------
 template <bool kLdsSH, int NC>
 __global__ __launch_bounds__(kPreBlock) void preprocess_backward_kernel(
@@ -588,37 +453,8 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_backward_kernel(
             {
                 constexpr int kGQ = NC == 9 ? kGradQuads + 1 : kGradQuads;   // quads per gradient record
                 float4 g[kGQ];
-#pragma unroll
-                for (int k = 0; k < kGQ; ++k) g[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                const uint32_t first = first_index(f, (uint32_t)i), cnt = tiles_touched[i];
-                // Four records per trip.  K7 writes a record only where some pixel contributed -- about 40 % of a Gaussian's span --
-                // and sets the slot's byte in `written`; the flags of the next trip are in flight behind this trip's records.
-                constexpr int kTrip = 4;
-                const uint32_t end = first + cnt;
-                auto load_flags = [&](uint32_t e, uint8_t (&fl)[kTrip]) {
-#pragma unroll
-                    for (int t = 0; t < kTrip; ++t) fl[t] = e + t < end ? written[e + t] : (uint8_t)0;
-                };
-                uint8_t fl[kTrip], fn[kTrip] = {0, 0, 0, 0};
-                load_flags(first, fl);
-                for (uint32_t e = first; e < end; e += kTrip) {
-                    if (e + kTrip < end) load_flags(e + kTrip, fn);
-                    float4 a[kTrip][kGQ];
-#pragma unroll
-                    for (int t = 0; t < kTrip; ++t) {
-                        const float4* gr = inst_grads + (size_t)(e + t) * kGQ;
-#pragma unroll
-                        for (int k = 0; k < kGQ; ++k) a[t][k] = fl[t] ? gr[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-#pragma unroll
-                    for (int t = 0; t < kTrip; ++t) {
-                        if (fl[t]) {
-#pragma unroll
-                            for (int k = 0; k < kGQ; ++k) { g[k].x += a[t][k].x; g[k].y += a[t][k].y; g[k].z += a[t][k].z; g[k].w += a[t][k].w; }
-                        }
-                        fl[t] = fn[t];
-                    }
-                }
+                const uint32_t first = first_index(f, (uint32_t)i);
+                sum_gradient_records<kGQ, 0, kGQ>(first, first + tiles_touched[i], written, inst_grads, g);
                 g0 = g[0]; g1 = g[1]; g2 = g[2]; g3 = g[3]; g4 = g[4]; g5 = g[5];
                 if (NC == 9) { g_col[6] = g[kGQ - 1].x; g_col[7] = g[kGQ - 1].y; g_col[8] = g[kGQ - 1].z; }
             }
@@ -773,8 +609,8 @@ __global__ __launch_bounds__(kPreBlock) void preprocess_backward_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// Colour gradients only (sr_backward_colors): sums slots 18..20 of a Gaussian's written gradient records -- the same records,
-// flags and ascending order as K8, so the sums are the ones K8 forms -- and applies the SH clamp mask.  This is all a
+// Colour gradients only (sr_backward_colors): sums slots 18..20 of a Gaussian's written gradient records -- K8's own walk
+// (sum_gradient_records), so the sums are the ones K8 forms -- and applies the SH clamp mask.  This is all a
 // frame-parallel rank has to ship for the factored SH exchange (12 B per Gaussian), and it is available right after K7: the
 // all-gather can run while K8 does the rest of the backward.
 // ---------------------------------------------------------------------------------------------
@@ -786,30 +622,10 @@ __global__ __launch_bounds__(256) void color_gradient_kernel(int P, const int32_
     if (i >= P) return;
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     if (radii[i] > 0 && !(f.overflow && *f.overflow)) {
-        const uint32_t first = first_index(f, (uint32_t)i), end = first + tiles_touched[i];
-        // four slots per trip, the next trip's flags in flight behind this trip's records (as in K8; same ascending order of the adds)
-        constexpr int kTrip = 4;
-        auto load_flags = [&](uint32_t e, uint8_t (&fl)[kTrip]) {
-#pragma unroll
-            for (int t = 0; t < kTrip; ++t) fl[t] = e + t < end ? written[e + t] : (uint8_t)0;
-        };
-        uint8_t fl[kTrip], fn[kTrip] = {0, 0, 0, 0};
-        load_flags(first, fl);
-        for (uint32_t e = first; e < end; e += kTrip) {
-            if (e + kTrip < end) load_flags(e + kTrip, fn);
-            float4 a4[kTrip]; float a5[kTrip];
-#pragma unroll
-            for (int t = 0; t < kTrip; ++t) {
-                const float4* gr = inst_grads + (size_t)(e + t) * kGradQuads;
-                a4[t] = fl[t] ? gr[4] : make_float4(0.f, 0.f, 0.f, 0.f);
-                a5[t] = fl[t] ? gr[5].x : 0.f;
-            }
-#pragma unroll
-            for (int t = 0; t < kTrip; ++t) {
-                if (fl[t]) { c0 += a4[t].z; c1 += a4[t].w; c2 += a5[t]; }
-                fl[t] = fn[t];
-            }
-        }
+        const uint32_t first = first_index(f, (uint32_t)i);
+        float4 g[2];   // quads 4 and 5: slots 16..23
+        sum_gradient_records<kGradQuads, 4, 6>(first, first + tiles_touched[i], written, inst_grads, g);
+        c0 = g[0].z; c1 = g[0].w; c2 = g[1].x;
         if (mask_clamped) { const uint8_t cl = clamped[i]; if (cl & 1) c0 = 0.f; if (cl & 2) c1 = 0.f; if (cl & 4) c2 = 0.f; }
     }
     dL_dcolors[3 * (size_t)i] = c0; dL_dcolors[3 * (size_t)i + 1] = c1; dL_dcolors[3 * (size_t)i + 2] = c2;
@@ -820,31 +636,8 @@ __global__ __launch_bounds__(256) void color_gradient_kernel(int P, const int32_
 //   dL_dsh[i][k][c] = sum_v basis_k(dir(p_i, campos_v)) * gc[v][i][c]
 // The SH adjoint is linear in gc and its only other per-view input is the camera position, so frame-parallel ranks
 // all-gather 12 B per Gaussian instead of all-reducing the 192-B dL_dsh rows and every rank expands the sum locally.
-// b[k] * g is evaluated exactly as sh_backward does, so V = 1 reproduces K8's dL_dsh bit for bit.
+// The terms are K8's own (sh_basis_adjoint_terms), so V = 1 gives K8's dL_dsh.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, float b[16]) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) b[k] = 0.f;
-    b[0] = kSH_C0;
-    if (deg > 0) {
-        b[1] = -kSH_C1 * y; b[2] = kSH_C1 * z; b[3] = -kSH_C1 * x;
-        if (deg > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            b[4] = kSH_C2[0] * xy; b[5] = kSH_C2[1] * yz; b[6] = kSH_C2[2] * (2.f * zz - xx - yy);
-            b[7] = kSH_C2[3] * xz; b[8] = kSH_C2[4] * (xx - yy);
-            if (deg > 2) {
-                b[9] = kSH_C3[0] * y * (3.f * xx - yy);
-                b[10] = kSH_C3[1] * xy * z;
-                b[11] = kSH_C3[2] * y * (4.f * zz - xx - yy);
-                b[12] = kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
-                b[13] = kSH_C3[4] * x * (4.f * zz - xx - yy);
-                b[14] = kSH_C3[5] * z * (xx - yy);
-                b[15] = kSH_C3[6] * x * (xx - 3.f * yy);
-            }
-        }
-    }
-}
-
 template <bool kLdsSH>
 __global__ __launch_bounds__(kPreBlock) void sh_gradient_expand_kernel(int P, int M, int deg, int V, const float* __restrict__ means3D,
                                                                   const float* __restrict__ campos, const float* __restrict__ gc,
@@ -859,14 +652,13 @@ __global__ __launch_bounds__(kPreBlock) void sh_gradient_expand_kernel(int P, in
         const float px = means3D[3 * (size_t)i], py = means3D[3 * (size_t)i + 1], pz = means3D[3 * (size_t)i + 2];
         for (int v = 0; v < V; ++v) {
             const float* g = gc + ((size_t)v * P + i) * 3;
-            const float g0 = g[0], g1 = g[1], g2 = g[2];
-            if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;   // not visible in this view (or fully clamped): adds +0
+            const float gv[3] = {g[0], g[1], g[2]};
+            if (gv[0] == 0.f && gv[1] == 0.f && gv[2] == 0.f) continue;   // not visible in this view (or fully clamped): adds +0
             const float ox = px - campos[3 * v], oy = py - campos[3 * v + 1], oz = pz - campos[3 * v + 2];
             const float len = sqrtf((ox * ox + oy * oy) + oz * oz);
             float b[16];
             sh_basis(deg, ox / len, oy / len, oz / len, b);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { acc[3 * k] += b[k] * g0; acc[3 * k + 1] += b[k] * g1; acc[3 * k + 2] += b[k] * g2; }
+            sh_basis_adjoint_terms<true>(deg, b, acc, gv);   // (constant indices: acc stays in registers)
         }
         if (kLdsSH) {
             float4* row = reinterpret_cast<float4*>(s_sh + tid * kShLdsStride);
@@ -903,12 +695,12 @@ hipError_t launch_preprocess_forward(int P, const FrameDev& f, const SrGaussians
                                      uint32_t* tiles_touched, uint2* rect, uint8_t* clamped, int32_t* radii, hipStream_t s) {
     if (P == 0) return hipSuccess;
     const dim3 grid((P + kPreBlock - 1) / kPreBlock), block(kPreBlock);
-    if (g.shs && g.sh_coeffs == 16 && aligned16(g.shs))
-        hipLaunchKernelGGL(preprocess_forward_kernel<true>, grid, block, 0, s, P, f, g.means3D, g.opacities, g.scales,
-                           g.rotations, g.shs, g.colors_precomp, g.transMat_precomp, g.mask, recs, depth_keys, tiles_touched, rect, clamped, radii);
-    else
-        hipLaunchKernelGGL(preprocess_forward_kernel<false>, grid, block, 0, s, P, f, g.means3D, g.opacities, g.scales,
-                           g.rotations, g.shs, g.colors_precomp, g.transMat_precomp, g.mask, recs, depth_keys, tiles_touched, rect, clamped, radii);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, P, f, g.means3D, g.opacities, g.scales, g.rotations, g.shs, g.colors_precomp,
+                           g.transMat_precomp, g.mask, recs, depth_keys, tiles_touched, rect, clamped, radii);
+    };
+    if (g.shs && g.sh_coeffs == 16 && aligned16(g.shs)) launch(preprocess_forward_kernel<true>);
+    else launch(preprocess_forward_kernel<false>);
     return hipGetLastError();
 }
 
@@ -917,21 +709,15 @@ hipError_t launch_preprocess_backward(int P, const FrameDev& f, const SrGaussian
                                       const uint32_t* tiles_touched, const SrGradients& out, hipStream_t s) {
     if (P == 0) return hipSuccess;
     const dim3 grid((P + kPreBlock - 1) / kPreBlock), block(kPreBlock);
-    if (f.colors == 9 && g.sh_coeffs == 16 && aligned16(g.shs) && (!out.dL_dsh || aligned16(out.dL_dsh)))
-        hipLaunchKernelGGL((preprocess_backward_kernel<true, 9>), grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs,
-                           g.transMat_precomp, radii, clamped, recs, inst_grads, written, tiles_touched, out);
-    else if (f.colors == 9)
-        hipLaunchKernelGGL((preprocess_backward_kernel<false, 9>), grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs,
-                           g.transMat_precomp, radii, clamped, recs, inst_grads, written, tiles_touched, out);
-    else if (f.colors == 6)
-        hipLaunchKernelGGL((preprocess_backward_kernel<false, 6>), grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs,
-                           g.transMat_precomp, radii, clamped, recs, inst_grads, written, tiles_touched, out);
-    else if (g.shs && g.sh_coeffs == 16 && aligned16(g.shs) && (!out.dL_dsh || aligned16(out.dL_dsh)))
-        hipLaunchKernelGGL((preprocess_backward_kernel<true, 3>), grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs,
-                           g.transMat_precomp, radii, clamped, recs, inst_grads, written, tiles_touched, out);
-    else
-        hipLaunchKernelGGL((preprocess_backward_kernel<false, 3>), grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs,
-                           g.transMat_precomp, radii, clamped, recs, inst_grads, written, tiles_touched, out);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, P, f, g.means3D, g.scales, g.rotations, g.shs, g.transMat_precomp, radii, clamped, recs,
+                           inst_grads, written, tiles_touched, out);
+    };
+    if (f.colors == 9 && g.sh_coeffs == 16 && aligned16(g.shs) && (!out.dL_dsh || aligned16(out.dL_dsh))) launch(preprocess_backward_kernel<true, 9>);
+    else if (f.colors == 9) launch(preprocess_backward_kernel<false, 9>);
+    else if (f.colors == 6) launch(preprocess_backward_kernel<false, 6>);
+    else if (g.shs && g.sh_coeffs == 16 && aligned16(g.shs) && (!out.dL_dsh || aligned16(out.dL_dsh))) launch(preprocess_backward_kernel<true, 3>);
+    else launch(preprocess_backward_kernel<false, 3>);
     return hipGetLastError();
 }
 

@@ -437,6 +437,28 @@ def test_sh_layout_fallbacks_and_scale_modifier():
                 assert_grads_close(out[name], bwd[name], 2e-3, f"{tag} {kernel} {name}")
 
 
+@pytest.mark.parametrize("deg", [2, 3])
+def test_staged_and_unstaged_sh_paths_are_one_function(deg):
+    """K1 / K8 with the SH rows staged through LDS (M = 16, 16-byte aligned) and without (the same values in a view 4 bytes into its
+    storage) evaluate the same SH code (csrc/sh.h): every output and gradient is equal bit for bit.  P = 300: two full blocks of 128
+    Gaussians and a ragged one of 44."""
+    from tests.gpu_util import DEV, run_hip
+    P, W, H = 300, 64, 48
+    cam, g = _scene(P, W, H, 17, 4e-3, 5e-2, 3)
+    dc, da = synthetic_upstream_grads(W, H, seed=9)
+    outs = []
+    for misalign in (False, True):
+        buf = torch.zeros(P * 16 * 3 + 4, device=DEV)
+        shs = buf[1:1 + P * 48] if misalign else buf[:P * 48]
+        shs = shs.view(P, 16, 3)
+        shs.copy_(g["shs"].to(DEV))
+        assert (shs.data_ptr() % 16 != 0) == misalign
+        outs.append(run_hip(dict(g, shs=shs), cam, [0.1, 0.0, 0.2], deg, dc, da))
+    assert np.abs(outs[0]["dL_dmeans3D"]).max() > 0 and np.abs(outs[0]["dL_dsh"]).max() > 0, "nothing was rendered"
+    for name in ("color", "allmap", "radii", "dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dsh", "dL_dmeans2D"):
+        assert torch.equal(torch.from_numpy(outs[0][name]), torch.from_numpy(outs[1][name])), f"deg {deg}: {name} differs between the two paths"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("use_tpre", [False, True])
 def test_six_colour_channels_equal_two_three_channel_passes(use_tpre):
