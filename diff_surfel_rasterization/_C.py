@@ -25,6 +25,7 @@ import os
 import torch
 
 from streetunveiler_amd import _lib as L
+from streetunveiler_amd._call import buf, call, ptr, workspace
 
 
 # Tracing: with SURFEL_ROCTX=1 every operator entry point is bracketed by a roctx range (libroctx64: rocprofv3 --marker-trace
@@ -41,7 +42,7 @@ def _roctx_lib():
         if os.environ.get("SURFEL_ROCTX") == "1":
             for name in ("libroctx64.so", "libroctx64.so.4", "/opt/rocm/lib/libroctx64.so"):
                 try:
-                    lib = C.CDLL(name)
+                    lib = C.CDLL(name)      # (libroctx64's two functions, not the C-ABI of _lib.PROTOTYPES: bound here)
                     lib.roctxRangePushA.argtypes = [C.c_char_p]; lib.roctxRangePushA.restype = C.c_int
                     lib.roctxRangePop.restype = C.c_int
                     _roctx = lib
@@ -68,10 +69,6 @@ class _range:
         return False
 
 
-def _ptr(t: torch.Tensor):
-    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-
-
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     if t is None:
         return None
@@ -80,10 +77,6 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 # SURFEL_EXTRA_FLAGS: SrFrame.flags bits OR-ed into every call of this process (A/B runs of opt-in switches such as SR_FLAG_ONE_SWEEP_SORT
@@ -98,13 +91,13 @@ def _frame(bg, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W,
     if blend_counters is not None and (blend_counters.dtype != torch.int64 or blend_counters.numel() < 16 or not blend_counters.is_cuda):
         raise L.SurfelRasterError("blend_counters must be a CUDA (ROCm) int64 tensor with 16 entries")
     fr = L.SrFrame(int(H), int(W), float(tan_fovx), float(tan_fovy), float(scale_modifier), int(degree),
-                   int(bool(prefiltered)), int(bool(debug)), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]),
+                   int(bool(prefiltered)), int(bool(debug)), ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]),
                    int(tile[0]) if tile else 0, int(tile[1]) if tile else 0, (0 if quadrant_cull else L.SR_FLAG_NO_QUADRANT_CULL) | (L.SR_FLAG_BALLOT_RANKING if ballot_ranking else 0) |
                    (0 if row_mapped is None else (L.SR_FLAG_ROW_MAPPED_FORWARD if row_mapped else L.SR_FLAG_QUADRANT_MAPPED_FORWARD)) |
                    (L.SR_FLAG_FORWARD_ONLY if forward_only else 0) | (L.SR_FLAG_NO_PRECOMP_COLOR_GRAD if no_precomp_color_grad else 0) |
                    (L.SR_FLAG_BINNING_CAPACITY if binning_capacity is not None else 0) |
                    ({None: 0, "one_wave": L.SR_FLAG_ONE_WAVE_BACKWARD, "coop": L.SR_FLAG_COOP_BACKWARD, "rows": L.SR_FLAG_ROW_BACKWARD}[backward_kernel]) | _EXTRA_FLAGS,
-                   _ptr(blend_counters))
+                   ptr(blend_counters))
     return fr, keep
 
 
@@ -139,8 +132,8 @@ def _gaussians(means3D, opacities, scales, rotations, sh, colors_precomp, transM
         NC = 9   # SH colour + six precomputed channels in one pass
     elif M and colors_precomp is not None and colors_precomp.numel():
         raise L.SurfelRasterError("Please provide exactly one of either SHs or precomputed colors!")
-    g = L.SrGaussians(P, M, NC, int(activations), _ptr(means3D), _ptr(opacities), _ptr(scales), _ptr(rotations), _ptr(sh),
-                      _ptr(colors_precomp), _ptr(transMat_precomp), _ptr(mask))
+    g = L.SrGaussians(P, M, NC, int(activations), ptr(means3D), ptr(opacities), ptr(scales), ptr(rotations), ptr(sh),
+                      ptr(colors_precomp), ptr(transMat_precomp), ptr(mask))
     return g
 
 
@@ -166,7 +159,6 @@ def rasterize_gaussians(bg, means3D, colors_precomp, opacities, scales, rotation
     waits for the GPU, and the whole call can be captured into a HIP graph.  Whether the frame fitted is decided on the device:
     `forward_status(geom, P)` -> device int32 [D, visible, overflow]; overflow = 1 means nothing was rendered (background image, zero gradients) and
     the frame has to be rendered again with at least D items.  Results of a frame that fits are bit-identical to the default mode."""
-    lib = L.load()
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise L.SurfelRasterError("means3D must have dimensions (num_points, 3)")
     means3D = _f32c(means3D, "means3D"); opacities = _f32c(opacities, "opacities")
@@ -188,17 +180,13 @@ def rasterize_gaussians(bg, means3D, colors_precomp, opacities, scales, rotation
         color = torch.empty((g.color_channels, H, W), dtype=torch.float32, device=dev)
         allmap = torch.empty((7, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty((lib.sr_geom_bytes(P),), dtype=torch.uint8, device=dev)
-        img = torch.empty((0 if forward_only else lib.sr_image_bytes(W, H),), dtype=torch.uint8, device=dev)
-        stream = _stream(dev)
+        geom = workspace("sr_geom_bytes", dev, P)
+        img = torch.empty((0,), dtype=torch.uint8, device=dev) if forward_only else workspace("sr_image_bytes", dev, W, H)
         D = C.c_uint32(0)
-        L.check(lib.sr_forward_plan(C.byref(fr), C.byref(g), _ptr(geom), geom.numel(), _ptr(radii), C.byref(D), stream),
-                "sr_forward_plan")
+        call("sr_forward_plan", dev, C.byref(fr), C.byref(g), *buf(geom), ptr(radii), C.byref(D))
         num_rendered = int(D.value) if binning_capacity is None else (max(1, int(binning_capacity)) if P else 0)
-        binning = torch.empty((lib.sr_binning_bytes(P, num_rendered, W, H),), dtype=torch.uint8, device=dev)
-        L.check(lib.sr_forward_render(C.byref(fr), C.byref(g), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(),
-                                      _ptr(img), img.numel(), num_rendered, _ptr(color), _ptr(allmap), stream),
-                "sr_forward_render")
+        binning = workspace("sr_binning_bytes", dev, P, num_rendered, W, H)
+        call("sr_forward_render", dev, C.byref(fr), C.byref(g), *buf(geom), *buf(binning), *buf(img), num_rendered, ptr(color), ptr(allmap))
         if classes is not None and int(n_classes) > 0:
             if classes.numel() != P:
                 raise L.SurfelRasterError("classes must have one entry per Gaussian")
@@ -206,10 +194,10 @@ def rasterize_gaussians(bg, means3D, colors_precomp, opacities, scales, rotation
                 raise L.SurfelRasterError("the shared-plan class pass is a training pass: not with forward_only")
             cls = classes.to(device=dev, dtype=torch.int32).contiguous()
             dist = torch.empty((int(n_classes), H, W), dtype=torch.float32, device=dev)
-            cstate = torch.empty((lib.sr_class_shared_bytes(P, W, H, int(n_classes), num_rendered),), dtype=torch.uint8, device=dev)
+            cstate = workspace("sr_class_shared_bytes", dev, P, W, H, int(n_classes), num_rendered)
             with _range("class_forward"):
-                L.check(lib.sr_class_forward_shared(C.byref(fr), C.byref(g), int(n_classes), _ptr(cls), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(),
-                                                    _ptr(cstate), cstate.numel(), num_rendered, _ptr(dist), stream), "sr_class_forward_shared")
+                call("sr_class_forward_shared", dev, C.byref(fr), C.byref(g), int(n_classes), ptr(cls), *buf(geom), *buf(binning), *buf(cstate),
+                     num_rendered, ptr(dist))
             del keep
             return num_rendered, color, allmap, radii, geom, binning, img, dist, cstate
     del keep
@@ -234,7 +222,6 @@ def rasterize_gaussians_backward(bg, means3D, radii, colors_precomp, scales, rot
     with `sh_gradient_expand`.  `after_blend(dL_dcolors)`: with `defer_sh`, called between the two halves of the backward
     (sr_backward_blend -> sr_backward_colors -> HERE -> sr_backward_geometry) with the [P,3] colour gradients already final, so that
     a frame-parallel rank can put its all-gather on the wire while K8 still runs."""
-    lib = L.load()
     means3D = _f32c(means3D, "means3D")
     colors_precomp = _f32c(colors_precomp, "colors_precomp"); scales = _f32c(scales, "scales")
     rotations = _f32c(rotations, "rotations"); transMat_precomp = _f32c(transMat_precomp, "transMat_precomp")
@@ -273,41 +260,31 @@ def rasterize_gaussians_backward(bg, means3D, radii, colors_precomp, scales, rot
             raise L.SurfelRasterError(f"dL_dcolor / bg must have {NC} channels")
         dL_dcolors = e(P, 6 if NC == 9 else NC) if (has(colors_precomp) and not skip_cg) or defer_sh else e(0, 3)
         dL_dtransMat = e(P, 9) if has(transMat_precomp) else e(0, 9)
-        ws = torch.empty((lib.sr_backward_workspace_bytes(P, int(num_rendered), NC),), dtype=torch.uint8, device=dev)
-        grads = L.SrGradients(_ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dtransMat),
-                              _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations))
+        ws = workspace("sr_backward_workspace_bytes", dev, P, int(num_rendered), NC)
+        grads = L.SrGradients(ptr(dL_dmeans2D), ptr(dL_dcolors), ptr(dL_dopacity), ptr(dL_dmeans3D), ptr(dL_dtransMat),
+                              ptr(dL_dsh), ptr(dL_dscales), ptr(dL_drotations))
+        fg, state = (C.byref(fr), C.byref(g)), (*buf(geomBuffer), *buf(binningBuffer), *buf(imgBuffer), int(num_rendered))
+        blend = lambda: call("sr_backward_blend", dev, *fg, *state, ptr(dL_dcolor), ptr(dL_dallmap), *buf(ws))
+        geometry = lambda: call("sr_backward_geometry", dev, *fg, ptr(radii), *state, *buf(ws), C.byref(grads))
         if class_state is not None:   # the shared-plan class pass: K7 -> class backward into the same records -> ONE K8
             if defer_sh or after_blend is not None:
                 # (a frame-parallel caller would get a locally expanded dL_dsh and no exchange hook -- silently)
                 raise L.SurfelRasterError("the shared-plan class pass (class_state) does not combine with the factored SH exchange "
                                           "(defer_sh / after_blend): exchange its gradients with the plain all-reduce")
             dL_ddist = _f32c(dL_ddist, "dL_ddist")
-            L.check(lib.sr_backward_blend(C.byref(fr), C.byref(g), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                          binningBuffer.numel(), _ptr(imgBuffer), imgBuffer.numel(), int(num_rendered), _ptr(dL_dcolor),
-                                          _ptr(dL_dallmap), _ptr(ws), ws.numel(), _stream(dev)), "sr_backward_blend")
+            blend()
             with _range("class_backward"):
-                L.check(lib.sr_class_backward_shared(C.byref(fr), C.byref(g), int(n_classes), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                                     binningBuffer.numel(), _ptr(class_state), class_state.numel(), int(num_rendered), _ptr(dL_ddist),
-                                                     _ptr(ws), ws.numel(), _stream(dev)), "sr_class_backward_shared")
-            L.check(lib.sr_backward_geometry(C.byref(fr), C.byref(g), _ptr(radii), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                             binningBuffer.numel(), _ptr(imgBuffer), imgBuffer.numel(), int(num_rendered), _ptr(ws),
-                                             ws.numel(), C.byref(grads), _stream(dev)), "sr_backward_geometry")
+                call("sr_class_backward_shared", dev, *fg, int(n_classes), *buf(geomBuffer), *buf(binningBuffer), *buf(class_state), int(num_rendered),
+                     ptr(dL_ddist), *buf(ws))
+            geometry()
         elif after_blend is not None and defer_sh and NC == 3:
-            L.check(lib.sr_backward_blend(C.byref(fr), C.byref(g), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                          binningBuffer.numel(), _ptr(imgBuffer), imgBuffer.numel(), int(num_rendered), _ptr(dL_dcolor),
-                                          _ptr(dL_dallmap), _ptr(ws), ws.numel(), _stream(dev)), "sr_backward_blend")
-            L.check(lib.sr_backward_colors(C.byref(fr), C.byref(g), _ptr(radii), _ptr(geomBuffer), geomBuffer.numel(), int(num_rendered),
-                                           _ptr(ws), ws.numel(), _ptr(dL_dcolors), _stream(dev)), "sr_backward_colors")
+            blend()
+            call("sr_backward_colors", dev, *fg, ptr(radii), *buf(geomBuffer), int(num_rendered), *buf(ws), ptr(dL_dcolors))
             after_blend(dL_dcolors)
             grads.dL_dcolors = None      # already final; K8 need not write it again
-            L.check(lib.sr_backward_geometry(C.byref(fr), C.byref(g), _ptr(radii), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                             binningBuffer.numel(), _ptr(imgBuffer), imgBuffer.numel(), int(num_rendered), _ptr(ws),
-                                             ws.numel(), C.byref(grads), _stream(dev)), "sr_backward_geometry")
+            geometry()
         else:
-            L.check(lib.sr_backward(C.byref(fr), C.byref(g), _ptr(radii), _ptr(geomBuffer), geomBuffer.numel(),
-                                    _ptr(binningBuffer), binningBuffer.numel(), _ptr(imgBuffer), imgBuffer.numel(),
-                                    int(num_rendered), _ptr(dL_dcolor), _ptr(dL_dallmap), _ptr(ws), ws.numel(),
-                                    C.byref(grads), _stream(dev)), "sr_backward")
+            call("sr_backward", dev, *fg, ptr(radii), *state, ptr(dL_dcolor), ptr(dL_dallmap), *buf(ws), C.byref(grads))
     del keep
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations
 
@@ -316,7 +293,6 @@ def class_distortions(bg, means3D, classes, opacities, scales, rotations, scale_
                       image_height, image_width, campos, n_classes, debug=False, activations=0, mask=None, tile=None):
     """Per-class distortion pass, forward (sr_forward_plan + sr_class_forward_render): `classes` [P] integer class of every
     Gaussian (negative or >= n_classes: in no class).  -> (num_rendered, dist[n_classes,H,W], radii, class_cols, geom, binning, class_image)."""
-    lib = L.load()
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise L.SurfelRasterError("means3D must have dimensions (num_points, 3)")
     means3D = _f32c(means3D, "means3D"); opacities = _f32c(opacities, "opacities"); scales = _f32c(scales, "scales"); rotations = _f32c(rotations, "rotations")
@@ -332,15 +308,13 @@ def class_distortions(bg, means3D, classes, opacities, scales, rotations, scale_
         g = _gaussians(means3D, opacities, scales, rotations, None, cols, None, activations, mask)
         dist = torch.empty((int(n_classes), H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty((lib.sr_geom_bytes(P),), dtype=torch.uint8, device=dev)
-        cimg = torch.empty((lib.sr_class_image_bytes(W, H, int(n_classes)),), dtype=torch.uint8, device=dev)
-        stream = _stream(dev)
+        geom = workspace("sr_geom_bytes", dev, P)
+        cimg = workspace("sr_class_image_bytes", dev, W, H, int(n_classes))
         D = C.c_uint32(0)
-        L.check(lib.sr_forward_plan(C.byref(fr), C.byref(g), _ptr(geom), geom.numel(), _ptr(radii), C.byref(D), stream), "sr_forward_plan")
+        call("sr_forward_plan", dev, C.byref(fr), C.byref(g), *buf(geom), ptr(radii), C.byref(D))
         num_rendered = int(D.value)
-        binning = torch.empty((lib.sr_binning_bytes(P, num_rendered, W, H),), dtype=torch.uint8, device=dev)
-        L.check(lib.sr_class_forward_render(C.byref(fr), C.byref(g), int(n_classes), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(),
-                                            _ptr(cimg), cimg.numel(), num_rendered, _ptr(dist), stream), "sr_class_forward_render")
+        binning = workspace("sr_binning_bytes", dev, P, num_rendered, W, H)
+        call("sr_class_forward_render", dev, C.byref(fr), C.byref(g), int(n_classes), *buf(geom), *buf(binning), *buf(cimg), num_rendered, ptr(dist))
     del keep
     return num_rendered, dist, radii, cols, geom, binning, cimg
 
@@ -348,7 +322,6 @@ def class_distortions(bg, means3D, classes, opacities, scales, rotations, scale_
 def class_distortions_backward(bg, means3D, radii, cols, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                dL_ddist, campos, n_classes, geom, num_rendered, binning, cimg, debug=False, activations=0, tile=None):
     """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dscales[P,2], dL_drotations[P,4]) of the per-class pass."""
-    lib = L.load()
     means3D = _f32c(means3D, "means3D"); scales = _f32c(scales, "scales"); rotations = _f32c(rotations, "rotations")
     dL_ddist = _f32c(dL_ddist, "dL_ddist")
     dev = means3D.device
@@ -361,11 +334,10 @@ def class_distortions_backward(bg, means3D, radii, cols, scales, rotations, scal
         dL_dmeans3D, dL_dopacity = flat[:3 * P].view(P, 3), flat[3 * P:4 * P].view(P, 1)
         dL_dscales, dL_drotations = flat[4 * P:6 * P].view(P, 2), flat[6 * P:].view(P, 4)
         dL_dmeans2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.sr_backward_workspace_bytes(P, int(num_rendered), 3),), dtype=torch.uint8, device=dev)
-        grads = L.SrGradients(_ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dmeans3D), None, None, _ptr(dL_dscales), _ptr(dL_drotations))
-        L.check(lib.sr_class_backward(C.byref(fr), C.byref(g), int(n_classes), _ptr(radii), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(),
-                                      _ptr(cimg), cimg.numel(), int(num_rendered), _ptr(dL_ddist), _ptr(ws), ws.numel(), C.byref(grads),
-                                      _stream(dev)), "sr_class_backward")
+        ws = workspace("sr_backward_workspace_bytes", dev, P, int(num_rendered), 3)
+        grads = L.SrGradients(ptr(dL_dmeans2D), None, ptr(dL_dopacity), ptr(dL_dmeans3D), None, None, ptr(dL_dscales), ptr(dL_drotations))
+        call("sr_class_backward", dev, C.byref(fr), C.byref(g), int(n_classes), ptr(radii), *buf(geom), *buf(binning), *buf(cimg), int(num_rendered),
+             ptr(dL_ddist), *buf(ws), C.byref(grads))
     del keep
     return dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_dscales, dL_drotations
 
@@ -373,52 +345,42 @@ def class_distortions_backward(bg, means3D, radii, cols, scales, rotations, scal
 def pair_decisions(bg, means3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos,
                    geomBuffer, num_rendered, binningBuffer, tile=None):
     """Test hook (sr_debug_pair_decisions): -> (valid[D, nq] int64, use3d[D, nq] int64) ballots per (list entry, 8x8 quadrant)."""
-    lib = L.load()
     means3D = _f32c(means3D, "means3D")
     dev = means3D.device
     tw, th = tile if tile else (16, 16)
     nq = (tw // 8) * (th // 8)
     valid = torch.zeros((max(int(num_rendered), 1), nq), dtype=torch.int64, device=dev)
     use3d = torch.zeros_like(valid)
-    with torch.cuda.device(dev):
-        fr, keep = _frame(bg, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, False, False, tile)
-        g = L.SrGaussians(int(means3D.shape[0]), 0, 3, 0, _ptr(means3D), _ptr(means3D), None, None, None, _ptr(means3D), _ptr(means3D), None)
-        L.check(lib.sr_debug_pair_decisions(C.byref(fr), C.byref(g), _ptr(geomBuffer), geomBuffer.numel(), _ptr(binningBuffer),
-                                            binningBuffer.numel(), int(num_rendered), _ptr(valid), _ptr(use3d), _stream(dev)),
-                "sr_debug_pair_decisions")
+    fr, keep = _frame(bg, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, degree, campos, False, False, tile)
+    g = L.SrGaussians(int(means3D.shape[0]), 0, 3, 0, ptr(means3D), ptr(means3D), None, None, None, ptr(means3D), ptr(means3D), None)
+    call("sr_debug_pair_decisions", dev, C.byref(fr), C.byref(g), *buf(geomBuffer), *buf(binningBuffer), int(num_rendered), ptr(valid), ptr(use3d))
     del keep
     return valid[:int(num_rendered)], use3d[:int(num_rendered)]
 
 
 def sh_gradient_expand(means3D, campos, dL_dcolors, sh_coeffs, degree):
     """dL_dsh [P,M,3] = sum over views v of the SH adjoint of dL_dcolors[v] seen from campos[v] (include/surfel_raster.h)."""
-    lib = L.load()
     means3D = _f32c(means3D, "means3D"); campos = _f32c(campos, "campos").reshape(-1, 3); dL_dcolors = _f32c(dL_dcolors, "dL_dcolors")
     P, V = int(means3D.shape[0]), int(campos.shape[0])
     if dL_dcolors.numel() != V * P * 3:
         raise L.SurfelRasterError(f"dL_dcolors must have {V} x {P} x 3 elements")
     out = torch.empty((P, int(sh_coeffs), 3), dtype=torch.float32, device=means3D.device)
-    with torch.cuda.device(means3D.device):
-        L.check(lib.sr_sh_gradient_expand(P, int(sh_coeffs), int(degree), V, _ptr(means3D), _ptr(campos), _ptr(dL_dcolors),
-                                          _ptr(out), _stream(means3D.device)), "sr_sh_gradient_expand")
+    call("sr_sh_gradient_expand", means3D.device, P, int(sh_coeffs), int(degree), V, ptr(means3D), ptr(campos), ptr(dL_dcolors), ptr(out))
     return out
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
-    lib = L.load()
     means3D = _f32c(means3D, "means3D"); viewmatrix = _f32c(viewmatrix, "viewmatrix"); projmatrix = _f32c(projmatrix, "projmatrix")
     P = int(means3D.shape[0])
     present = torch.empty((P,), dtype=torch.bool, device=means3D.device)
-    with torch.cuda.device(means3D.device):
-        L.check(lib.sr_mark_visible(P, _ptr(means3D), _ptr(viewmatrix), _ptr(projmatrix), _ptr(present),
-                                    _stream(means3D.device)), "sr_mark_visible")
+    call("sr_mark_visible", means3D.device, P, ptr(means3D), ptr(viewmatrix), ptr(projmatrix), ptr(present))
     return present
 
 
 # ---- state-buffer views (tests / profiling) ---------------------------------------------------------
-def _view(buf: torch.Tensor, ptr, nbytes: int, dtype: torch.dtype) -> torch.Tensor:
-    off = int(ptr) - buf.data_ptr()
-    return buf[off:off + nbytes].view(dtype)
+def _view(state: torch.Tensor, address, nbytes: int, dtype: torch.dtype) -> torch.Tensor:
+    off = int(address) - state.data_ptr()
+    return state[off:off + nbytes].view(dtype)
 
 
 def forward_status(geom: torch.Tensor, P: int) -> torch.Tensor:
@@ -426,7 +388,7 @@ def forward_status(geom: torch.Tensor, P: int) -> torch.Tensor:
     by the capacity guard of a `binning_capacity` forward (1 = the frame did not fit: nothing was rendered -- and `visible` was zeroed).  Reading
     it on the host (`.tolist()`) is the caller's choice of when to synchronise."""
     v = L.SrGeomView()
-    L.check(L.load().sr_geom_view(_ptr(geom), geom.numel(), int(P), C.byref(v)), "sr_geom_view")
+    L.check(L.load().sr_geom_view(*buf(geom), int(P), C.byref(v)), "sr_geom_view")
     return _view(geom, v.frame_counts, 12, torch.int32)
 
 
@@ -435,7 +397,7 @@ def geom_view(geom: torch.Tensor, P: int):
     depth order -- are written (the depth sort drops the culled ones).  `splats`: rows with radii == 0 are UNDEFINED (K1 skips the 128-B
     lines whose rows are all culled: whatever torch.empty left there, possibly NaN) -- index with radii > 0."""
     v = L.SrGeomView()
-    L.check(L.load().sr_geom_view(_ptr(geom), geom.numel(), P, C.byref(v)), "sr_geom_view")
+    L.check(L.load().sr_geom_view(*buf(geom), P, C.byref(v)), "sr_geom_view")
     return dict(splats=_view(geom, v.splats, P * 80, torch.float32).view(P, 20),
                 depth_keys=_view(geom, v.depth_keys, P * 4, torch.int32), tiles_touched=_view(geom, v.tiles_touched, P * 4, torch.int32),
                 clamped=_view(geom, v.clamped, P, torch.uint8), sorted_gid=_view(geom, v.sorted_gid, P * 4, torch.int32),
@@ -444,7 +406,7 @@ def geom_view(geom: torch.Tensor, P: int):
 
 def binning_view(binning: torch.Tensor, P: int, D: int, W: int, H: int, tile=(16, 16)):
     v = L.SrBinningView()
-    L.check(L.load().sr_binning_view(_ptr(binning), binning.numel(), P, D, W, H, C.byref(v)), "sr_binning_view")
+    L.check(L.load().sr_binning_view(*buf(binning), P, D, W, H, C.byref(v)), "sr_binning_view")
     tiles = ((W + tile[0] - 1) // tile[0]) * ((H + tile[1] - 1) // tile[1])
     ranges = _view(binning, v.ranges, tiles * 8, torch.int32).view(tiles, 2)
     # tile id of every list entry, rebuilt from the ranges (the partition keeps only the permutation)
@@ -456,6 +418,6 @@ def binning_view(binning: torch.Tensor, P: int, D: int, W: int, H: int, tile=(16
 
 def image_view(img: torch.Tensor, W: int, H: int):
     v = L.SrImageView()
-    L.check(L.load().sr_image_view(_ptr(img), img.numel(), W, H, C.byref(v)), "sr_image_view")
+    L.check(L.load().sr_image_view(*buf(img), W, H, C.byref(v)), "sr_image_view")
     return dict(final_T=_view(img, v.final_T, 3 * H * W * 4, torch.float32).view(3, H, W),
                 n_contrib=_view(img, v.n_contrib, 2 * H * W * 4, torch.int32).view(2, H, W))

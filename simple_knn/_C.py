@@ -12,10 +12,10 @@ import ctypes as C
 import torch
 
 from streetunveiler_amd import _lib as L
+from streetunveiler_amd._call import buf, call, ptr, workspace
 
 
 def _knn(query, reference, K, take_sqrt=False):
-    lib = L.load()
     ref = reference
     if not ref.is_cuda:
         raise L.SurfelRasterError("points must be a CUDA (ROCm) tensor; the kNN ops have no CPU path")
@@ -25,12 +25,11 @@ def _knn(query, reference, K, take_sqrt=False):
     q = None if query is None else query.detach().float().contiguous().to(ref.device)
     n_out = ref.shape[0] if q is None else q.shape[0]
     out = torch.empty((n_out,), dtype=torch.float32, device=ref.device)
-    with torch.cuda.device(ref.device):
-        ws = torch.empty((lib.sr_knn_workspace_bytes(0 if q is None else q.shape[0], ref.shape[0]),), dtype=torch.uint8, device=ref.device)
-        L.check(lib.sr_knn_mean_dist2(0 if q is None else q.shape[0], None if q is None else C.c_void_p(q.data_ptr()), ref.shape[0],
-                                      C.c_void_p(ref.data_ptr()), int(K), int(bool(take_sqrt)), C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)),
-                "sr_knn_mean_dist2")
+    n_query = 0 if q is None else q.shape[0]
+    ws = workspace("sr_knn_workspace_bytes", ref.device, n_query, ref.shape[0])
+    # (query: not ptr(q) -- a NULL query asks for the self search, so an EMPTY query cloud keeps whatever address it has)
+    call("sr_knn_mean_dist2", ref.device, n_query, None if q is None else C.c_void_p(q.data_ptr()), ref.shape[0], ptr(ref), int(K),
+         int(bool(take_sqrt)), ptr(out), *buf(ws))
     return out
 
 

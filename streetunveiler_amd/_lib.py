@@ -105,16 +105,73 @@ SR_DENSIFY_KIND_ORIGINAL, SR_DENSIFY_KIND_CLONE, SR_DENSIFY_KIND_CHILD0, SR_DENS
 SR_DENSIFY_ROLE_COPY, SR_DENSIFY_ROLE_MOMENT, SR_DENSIFY_ROLE_XYZ, SR_DENSIFY_ROLE_SCALING = 0, 1, 2, 3
 
 
-# every symbol include/surfel_raster.h declares (checked by tests/test_abi.py)
-EXPORTS = ["sr_abi_version", "sr_build_switches", "sr_source_digest", "sr_last_error", "sr_geom_bytes", "sr_binning_bytes", "sr_image_bytes",
-           "sr_backward_workspace_bytes", "sr_geom_view", "sr_binning_view", "sr_image_view", "sr_forward_plan", "sr_sh_gradient_expand", "sr_knn_workspace_bytes", "sr_knn_mean_dist2",
-           "sr_forward_render", "sr_backward", "sr_backward_blend", "sr_backward_colors", "sr_backward_geometry", "sr_debug_pair_decisions", "sr_class_image_bytes", "sr_class_forward_render", "sr_class_backward", "sr_class_shared_bytes", "sr_class_forward_shared", "sr_class_backward_shared", "sr_mark_visible", "sr_set_stage_timing", "sr_stage_stats", "sr_debug_radix_sort", "sr_debug_radix_sort_temp_bytes", "sr_debug_lds_atomic_ranks", "sr_rank_mode", "sr_postprocess_forward",
-           "sr_postprocess_backward", "sr_image_loss_workspace_bytes", "sr_image_loss_forward", "sr_image_loss_backward",
-           "sr_adam_step", "sr_densification_stats", "sr_cluster_workspace_bytes", "sr_cluster_radius",
-           "sr_densify_workspace_bytes", "sr_densify_plan", "sr_densify_apply", "sr_tsdf_fuse", "sr_tsdf_fuse_grid",
-           "sr_adam_step_rows", "sr_mask_compose", "sr_mask_compose_backward",
-           "sr_aux_loss_workspace_bytes", "sr_semantic_ce_forward", "sr_semantic_ce_backward", "sr_surface_reg_forward",
-           "sr_surface_reg_backward", "sr_opacity_shrink_forward", "sr_opacity_shrink_backward"]
+# include/surfel_raster.h, once: every function it declares -> (return type, argument types), in the header's order (tests/test_abi.py holds
+# this table, the structures and the constants above to the header's text).  A `void* stream` comes last wherever a call launches.
+_i32, _i64, _u32, _sz, _f32, _f64, _int, _vp, _str = C.c_int32, C.c_int64, C.c_uint32, C.c_size_t, C.c_float, C.c_double, C.c_int, C.c_void_p, C.c_char_p
+_P = C.POINTER
+_FG = [_P(SrFrame), _P(SrGaussians)]
+_GEOM = _BINNING = _IMAGE = _WS = [_vp, _sz]      # a state buffer or a workspace: its address and its size in bytes
+PROTOTYPES = {
+    "sr_abi_version": (_int, []),
+    "sr_build_switches": (_u32, []),
+    "sr_source_digest": (_str, []),
+    "sr_last_error": (_str, []),
+    "sr_geom_bytes": (_sz, [_i32]),
+    "sr_binning_bytes": (_sz, [_i32, _u32, _i32, _i32]),
+    "sr_image_bytes": (_sz, [_i32, _i32]),
+    "sr_backward_workspace_bytes": (_sz, [_i32, _u32, _i32]),
+    "sr_geom_view": (_int, _GEOM + [_i32, _P(SrGeomView)]),
+    "sr_binning_view": (_int, _BINNING + [_i32, _u32, _i32, _i32, _P(SrBinningView)]),
+    "sr_image_view": (_int, _IMAGE + [_i32, _i32, _P(SrImageView)]),
+    "sr_forward_plan": (_int, _FG + _GEOM + [_vp, _P(_u32), _vp]),
+    "sr_forward_render": (_int, _FG + _GEOM + _BINNING + _IMAGE + [_u32, _vp, _vp, _vp]),
+    "sr_backward": (_int, _FG + [_vp] + _GEOM + _BINNING + _IMAGE + [_u32, _vp, _vp] + _WS + [_P(SrGradients), _vp]),
+    "sr_backward_blend": (_int, _FG + _GEOM + _BINNING + _IMAGE + [_u32, _vp, _vp] + _WS + [_vp]),
+    "sr_backward_colors": (_int, _FG + [_vp] + _GEOM + [_u32] + _WS + [_vp, _vp]),
+    "sr_backward_geometry": (_int, _FG + [_vp] + _GEOM + _BINNING + _IMAGE + [_u32] + _WS + [_P(SrGradients), _vp]),
+    "sr_class_image_bytes": (_sz, [_i32, _i32, _i32]),
+    "sr_class_forward_render": (_int, _FG + [_i32] + _GEOM + _BINNING + _IMAGE + [_u32, _vp, _vp]),
+    "sr_class_backward": (_int, _FG + [_i32, _vp] + _GEOM + _BINNING + _IMAGE + [_u32, _vp] + _WS + [_P(SrGradients), _vp]),
+    "sr_class_shared_bytes": (_sz, [_i32, _i32, _i32, _i32, _u32]),
+    "sr_class_forward_shared": (_int, _FG + [_i32, _vp] + _GEOM + _BINNING + _IMAGE + [_u32, _vp, _vp]),
+    "sr_class_backward_shared": (_int, _FG + [_i32] + _GEOM + _BINNING + _IMAGE + [_u32, _vp] + _WS + [_vp]),
+    "sr_sh_gradient_expand": (_int, [_i32] * 4 + [_vp] * 5),
+    "sr_knn_workspace_bytes": (_sz, [_i32, _i32]),
+    "sr_knn_mean_dist2": (_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp] + _WS + [_vp]),
+    "sr_cluster_workspace_bytes": (_sz, [_i32]),
+    "sr_cluster_radius": (_int, [_i32, _vp, _vp, _f32, _vp] + _WS + [_vp]),
+    "sr_mark_visible": (_int, [_i32] + [_vp] * 5),
+    "sr_postprocess_forward": (_int, [_i32, _i32, _f32, _f32, _f32] + [_vp] * 7),
+    "sr_postprocess_backward": (_int, [_i32, _i32, _f32, _f32, _f32] + [_vp] * 9),
+    "sr_image_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "sr_image_loss_forward": (_int, [_i32, _i32, _i32, _f32] + [_vp] * 4 + _WS + [_vp, _vp]),
+    "sr_image_loss_backward": (_int, [_i32, _i32, _i32, _f32] + [_vp] * 4 + _WS + [_vp] * 5),
+    "sr_aux_loss_workspace_bytes": (_sz, [_i64]),
+    "sr_semantic_ce_forward": (_int, [_i32] * 3 + [_vp, _vp, _i32, _P(_f32)] + _WS + [_vp, _vp]),
+    "sr_semantic_ce_backward": (_int, [_i32] * 3 + [_vp, _vp, _i32, _P(_f32)] + [_vp] * 3),
+    "sr_surface_reg_forward": (_int, [_i32, _i32] + [_vp] * 3 + [_f64, _f64] + _WS + [_vp, _vp]),
+    "sr_surface_reg_backward": (_int, [_i32, _i32, _vp, _vp, _f64, _f64] + [_vp] * 5),
+    "sr_opacity_shrink_forward": (_int, [_i64, _vp, _i32] + _WS + [_vp, _vp]),
+    "sr_opacity_shrink_backward": (_int, [_i64, _vp, _i32, _vp, _vp, _vp]),
+    "sr_adam_step": (_int, [_P(SrAdamSegment), _i32, _f64, _f64, _f64, _vp]),
+    "sr_adam_step_rows": (_int, [_P(SrAdamRowSegment), _i32, _i32, _vp, _f64, _f64, _f64, _vp]),
+    "sr_mask_compose": (_int, [_i32, _i32, _P(SrMaskTensors), _P(SrMaskTensors), _vp, _u32, _P(SrMaskEffective), _vp]),
+    "sr_mask_compose_backward": (_int, [_i32, _i32, _P(SrMaskEffective), _vp, _u32, _P(SrMaskTensors), _vp]),
+    "sr_densification_stats": (_int, [_i32] + [_vp] * 6),
+    "sr_densify_workspace_bytes": (_sz, [_i32]),
+    "sr_densify_plan": (_int, [_i32] + [_vp] * 4 + [_f32] * 4 + [_vp] + _WS + [_P(_u32), _vp]),
+    "sr_densify_apply": (_int, [_i32, _P(_u32), _vp, _vp, _vp, _P(SrDensifySegment), _i32] + _WS + [_vp]),
+    "sr_tsdf_fuse": (_int, [_P(SrTsdfViews), _P(SrTsdfSpace), _i32] + [_vp] * 5),
+    "sr_tsdf_fuse_grid": (_int, [_P(SrTsdfViews), _P(SrTsdfSpace), _P(_i32), _P(_f32), _P(_f32), _i32, _i32] + [_vp] * 4),
+    "sr_debug_pair_decisions": (_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
+    "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
+    "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),
+    "sr_rank_mode": (_int, [_vp]),
+    "sr_debug_lds_atomic_ranks": (_int, [_vp, _vp, _u32, _int, _vp]),
+    "sr_set_stage_timing": (None, [_int]),
+    "sr_stage_stats": (_int, [_int, _P(_f32), _P(_int)]),
+}
+EXPORTS = list(PROTOTYPES)
 
 _lib = None
 
@@ -133,103 +190,23 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m streetunveiler_amd.build` "
             "(or __graft_entry__.build()). There is no CPU fallback for the rasterizer.")
     lib = C.CDLL(LIB_PATH)
+    missing = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            missing.append(name)     # (reported after the digest comparison, whose message says what to do about it)
+        else:
+            fn.restype, fn.argtypes = restype, argtypes
     # the in-tree library must be the one built from the sources next to it (it travels prebuilt to the GPU box); SURFEL_RASTER_LIB -- a
     # variant or A/B build chosen on purpose -- is taken as it is
     if not os.environ.get("SURFEL_RASTER_LIB"):
         from .build import source_digest
-        lib.sr_source_digest.restype = C.c_char_p
         have, want = lib.sr_source_digest().decode(), source_digest()
         if have != want:
             raise SurfelRasterError(f"{LIB_PATH} was built from other sources (digest {have}, the tree's is {want}): rebuild it with "
                                     "`python -m streetunveiler_amd.build`")
-    lib.sr_abi_version.restype = C.c_int
-    lib.sr_build_switches.restype = C.c_uint32
-    lib.sr_last_error.restype = C.c_char_p
-    for name in ("sr_geom_bytes", "sr_binning_bytes", "sr_image_bytes", "sr_backward_workspace_bytes"):
-        getattr(lib, name).restype = C.c_size_t
-    lib.sr_geom_bytes.argtypes = [C.c_int32]
-    lib.sr_binning_bytes.argtypes = [C.c_int32, C.c_uint32, C.c_int32, C.c_int32]
-    lib.sr_image_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.sr_backward_workspace_bytes.argtypes = [C.c_int32, C.c_uint32, C.c_int32]
-    lib.sr_geom_view.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(SrGeomView)]
-    lib.sr_binning_view.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(SrBinningView)]
-    lib.sr_image_view.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(SrImageView)]
-    lib.sr_forward_plan.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_size_t, C.c_void_p,
-                                    C.POINTER(C.c_uint32), C.c_void_p]
-    lib.sr_forward_render.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.sr_backward.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_size_t, C.POINTER(SrGradients), C.c_void_p]
-    lib.sr_backward_blend.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sr_backward_colors.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
-                                       C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sr_backward_geometry.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(SrGradients), C.c_void_p]
-    lib.sr_debug_pair_decisions.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.sr_class_shared_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
-    lib.sr_class_shared_bytes.restype = C.c_size_t
-    lib.sr_class_forward_shared.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.sr_class_backward_shared.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                             C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sr_class_image_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.sr_class_image_bytes.restype = C.c_size_t
-    lib.sr_class_forward_render.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.sr_class_backward.argtypes = [C.POINTER(SrFrame), C.POINTER(SrGaussians), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
-                                      C.POINTER(SrGradients), C.c_void_p]
-    lib.sr_sh_gradient_expand.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5
-    lib.sr_knn_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.sr_knn_workspace_bytes.restype = C.c_size_t
-    lib.sr_knn_mean_dist2.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                      C.c_size_t, C.c_void_p]
-    lib.sr_cluster_workspace_bytes.argtypes = [C.c_int32]
-    lib.sr_cluster_workspace_bytes.restype = C.c_size_t
-    lib.sr_cluster_radius.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.sr_set_stage_timing.argtypes = [C.c_int]
-    lib.sr_postprocess_forward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 7
-    lib.sr_postprocess_backward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 9
-    lib.sr_image_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.sr_image_loss_workspace_bytes.restype = C.c_size_t
-    lib.sr_image_loss_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sr_image_loss_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5
-    lib.sr_aux_loss_workspace_bytes.argtypes = [C.c_int64]
-    lib.sr_aux_loss_workspace_bytes.restype = C.c_size_t
-    lib.sr_semantic_ce_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t,
-                                                             C.c_void_p, C.c_void_p]
-    lib.sr_semantic_ce_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float)] + [C.c_void_p] * 3
-    lib.sr_surface_reg_forward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_size_t,
-                                                                                      C.c_void_p, C.c_void_p]
-    lib.sr_surface_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 5
-    lib.sr_opacity_shrink_forward.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sr_opacity_shrink_backward.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.sr_adam_step.argtypes = [C.POINTER(SrAdamSegment), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
-    lib.sr_adam_step_rows.argtypes = [C.POINTER(SrAdamRowSegment), C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
-    lib.sr_mask_compose.argtypes = [C.c_int32, C.c_int32, C.POINTER(SrMaskTensors), C.POINTER(SrMaskTensors), C.c_void_p, C.c_uint32,
-                                    C.POINTER(SrMaskEffective), C.c_void_p]
-    lib.sr_mask_compose_backward.argtypes = [C.c_int32, C.c_int32, C.POINTER(SrMaskEffective), C.c_void_p, C.c_uint32, C.POINTER(SrMaskTensors),
-                                             C.c_void_p]
-    lib.sr_densification_stats.argtypes = [C.c_int32] + [C.c_void_p] * 6
-    lib.sr_densify_workspace_bytes.argtypes = [C.c_int32]
-    lib.sr_densify_workspace_bytes.restype = C.c_size_t
-    lib.sr_densify_plan.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t,
-                                                                                      C.POINTER(C.c_uint32), C.c_void_p]
-    lib.sr_densify_apply.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrDensifySegment),
-                                     C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sr_tsdf_fuse.argtypes = [C.POINTER(SrTsdfViews), C.POINTER(SrTsdfSpace), C.c_int32] + [C.c_void_p] * 5
-    lib.sr_tsdf_fuse_grid.argtypes = [C.POINTER(SrTsdfViews), C.POINTER(SrTsdfSpace), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                      C.c_int32, C.c_int32] + [C.c_void_p] * 4
-    lib.sr_debug_radix_sort_temp_bytes.argtypes = [C.c_uint32]
-    lib.sr_debug_radix_sort_temp_bytes.restype = C.c_size_t
-    lib.sr_debug_radix_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
-    lib.sr_rank_mode.argtypes = [C.c_void_p]
-    lib.sr_debug_lds_atomic_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
-    lib.sr_stage_stats.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    if missing:
+        raise SurfelRasterError(f"{LIB_PATH} does not export {missing}")
     if lib.sr_abi_version() != SR_ABI_VERSION:
         raise SurfelRasterError(f"ABI version mismatch: library reports {lib.sr_abi_version()}, binding expects {SR_ABI_VERSION}")
     _lib = lib

@@ -12,7 +12,6 @@ HIP graph) and its `*_torch` twin: the reference's own lines on plain tensors --
 timing baseline."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import functools
 
@@ -20,28 +19,16 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from ._call import buf, call, ptr, workspace as _workspace
 
 MAX_CLASSES = 8
 REFERENCE_CLASS_WEIGHT = (1.0, 1.0, 1.0, 1.0, 0.2, 1.0)   # [REF train.py:88]
 _LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _need_cuda(t, what):
     if not t.is_cuda:
         raise L.SurfelRasterError(f"{what} needs CUDA (ROCm) tensors; there is no CPU path ({what}_torch is the checker)")
-
-
-def _on(dev):
-    """The device of the call as the current one: a context only where it is not already."""
-    return contextlib.nullcontext() if dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
 
 
 def _upstream(g_loss, dev):
@@ -53,7 +40,7 @@ def _upstream(g_loss, dev):
 
 def aux_loss_workspace(n, device):
     """The uint8 workspace of a forward over n pixels / Gaussians."""
-    return torch.empty(L.load().sr_aux_loss_workspace_bytes(int(n)), dtype=torch.uint8, device=device)
+    return _workspace("sr_aux_loss_workspace_bytes", device, int(n))
 
 
 # ---- semantic cross-entropy ------------------------------------------------------------------------------------------------------------
@@ -114,9 +101,7 @@ def _launch_ce_forward(logits, target, label_bytes, dims, weights, workspace=Non
         workspace = aux_loss_workspace(W * H, dev)
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=dev)
-    with _on(dev):
-        L.check(L.load().sr_semantic_ce_forward(W, H, Cn, _ptr(logits), _ptr(target), label_bytes, _weight_array(weights), _ptr(workspace),
-                                                workspace.numel(), _ptr(out), _stream(dev)), "sr_semantic_ce_forward")
+    call("sr_semantic_ce_forward", dev, W, H, Cn, ptr(logits), ptr(target), label_bytes, _weight_array(weights), *buf(workspace), ptr(out))
     return out
 
 
@@ -126,9 +111,7 @@ def _launch_ce_backward(logits, target, label_bytes, dims, weights, g_loss, out=
     g_loss = _upstream(g_loss, dev)
     if out is None:
         out = torch.empty_like(logits)
-    with _on(dev):
-        L.check(L.load().sr_semantic_ce_backward(W, H, Cn, _ptr(logits), _ptr(target), label_bytes, _weight_array(weights), _ptr(g_loss),
-                                                 _ptr(out), _stream(dev)), "sr_semantic_ce_backward")
+    call("sr_semantic_ce_backward", dev, W, H, Cn, ptr(logits), ptr(target), label_bytes, _weight_array(weights), ptr(g_loss), ptr(out))
     return out
 
 
@@ -218,9 +201,7 @@ def _launch_reg_forward(rn, sn, rd, dims, lambda_normal, lambda_dist, workspace=
         workspace = aux_loss_workspace(W * H, dev)
     if out is None:
         out = torch.empty(3, dtype=torch.float32, device=dev)
-    with _on(dev):
-        L.check(L.load().sr_surface_reg_forward(W, H, _ptr(rn), _ptr(sn), _ptr(rd), float(lambda_normal), float(lambda_dist), _ptr(workspace),
-                                                workspace.numel(), _ptr(out), _stream(dev)), "sr_surface_reg_forward")
+    call("sr_surface_reg_forward", dev, W, H, ptr(rn), ptr(sn), ptr(rd), float(lambda_normal), float(lambda_dist), *buf(workspace), ptr(out))
     return out
 
 
@@ -230,9 +211,8 @@ def _launch_reg_backward(rn, sn, rd, dims, lambda_normal, lambda_dist, g_loss, w
     g_loss = _upstream(g_loss, dev)
     if out is None:
         out = tuple(torch.empty_like(t) if w else None for t, w in zip((rn, sn, rd), want))
-    with _on(dev):
-        L.check(L.load().sr_surface_reg_backward(W, H, _ptr(rn), _ptr(sn), float(lambda_normal), float(lambda_dist), _ptr(g_loss), _ptr(out[0]),
-                                                 _ptr(out[1]), _ptr(out[2]), _stream(dev)), "sr_surface_reg_backward")
+    call("sr_surface_reg_backward", dev, W, H, ptr(rn), ptr(sn), float(lambda_normal), float(lambda_dist), ptr(g_loss), ptr(out[0]), ptr(out[1]),
+         ptr(out[2]))
     return out
 
 
@@ -298,9 +278,7 @@ def _launch_shrink_forward(opacity, activated, workspace=None, out=None):
         workspace = aux_loss_workspace(P, dev)
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=dev)
-    with _on(dev):
-        L.check(L.load().sr_opacity_shrink_forward(P, _ptr(opacity), int(bool(activated)), _ptr(workspace), workspace.numel(), _ptr(out),
-                                                   _stream(dev)), "sr_opacity_shrink_forward")
+    call("sr_opacity_shrink_forward", dev, P, ptr(opacity), int(bool(activated)), *buf(workspace), ptr(out))
     return out
 
 
@@ -309,9 +287,7 @@ def _launch_shrink_backward(opacity, g_loss, activated, out=None):
     g_loss = _upstream(g_loss, dev)
     if out is None:
         out = torch.empty_like(opacity)
-    with _on(dev):
-        L.check(L.load().sr_opacity_shrink_backward(opacity.numel(), _ptr(opacity), int(bool(activated)), _ptr(g_loss), _ptr(out), _stream(dev)),
-                "sr_opacity_shrink_backward")
+    call("sr_opacity_shrink_backward", dev, opacity.numel(), ptr(opacity), int(bool(activated)), ptr(g_loss), ptr(out))
     return out
 
 

@@ -8,18 +8,16 @@ exact variant (`parallel=False`) computes and what this op returns.  The referen
 strictly equivalent": it may split a component that this op keeps whole, and its result depends on the order of the points.
 There is no CPU path.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from ._call import buf, call, ptr, workspace
 
 
 def radius_components(xyz: torch.Tensor, threshold: float, mask: torch.Tensor = None) -> torch.Tensor:
     """int64 [P]: for a point that takes part (mask None or mask[i] true), the smallest index of the points it is connected to through steps
     shorter than `threshold`; -1 for a masked-out point; i for an active point with a NaN / inf coordinate (it is in range of nobody).
     Works on the current stream of xyz's device and reads nothing back to the host."""
-    lib = L.load()
     if not xyz.is_cuda or (mask is not None and not mask.is_cuda):
         raise L.SurfelRasterError("xyz and mask must be CUDA (ROCm) tensors; the clustering has no CPU path")
     if xyz.ndim != 2 or xyz.shape[1] != 3:
@@ -28,13 +26,10 @@ def radius_components(xyz: torch.Tensor, threshold: float, mask: torch.Tensor = 
         raise L.SurfelRasterError("mask must have dimensions (num_points,)")
     pts = xyz.detach().float().contiguous()
     n = pts.shape[0]
-    with torch.cuda.device(pts.device):
-        active = None if mask is None else (mask if mask.dtype == torch.bool else mask != 0).to(pts.device).contiguous()
-        labels = torch.empty((n,), dtype=torch.int64, device=pts.device)
-        ws = torch.empty((lib.sr_cluster_workspace_bytes(n),), dtype=torch.uint8, device=pts.device)
-        L.check(lib.sr_cluster_radius(n, C.c_void_p(pts.data_ptr()), None if active is None else C.c_void_p(active.data_ptr()), float(threshold),
-                                      C.c_void_p(labels.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                      C.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream)), "sr_cluster_radius")
+    active = None if mask is None else (mask if mask.dtype == torch.bool else mask != 0).to(pts.device).contiguous()
+    labels = torch.empty((n,), dtype=torch.int64, device=pts.device)
+    ws = workspace("sr_cluster_workspace_bytes", pts.device, n)
+    call("sr_cluster_radius", pts.device, n, ptr(pts), ptr(active), float(threshold), ptr(labels), *buf(ws))
     return labels
 
 

@@ -26,6 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from ._call import buf, call, ptr, workspace
 
 GROUP_NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")      # the reference's training_setup
 _ATTRIBUTE = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling",
@@ -168,14 +169,6 @@ def densify_and_prune_torch(params, moments, semantics, xyz_gradient_accum, deno
 
 
 # ---- the op --------------------------------------------------------------------------------------------------------------------------
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _check_rows(name, t, P, float32=False, tail=None):
     """dtype, shape and contiguity of one per-Gaussian tensor (a ValueError names it); the device is checked after all of these."""
     if not torch.is_tensor(t):
@@ -209,16 +202,13 @@ class _Plan:
     position reads (the SOURCE rotation and scaling, the noise) -- and the gather of any [P, ...] tensor through it."""
 
     def __init__(self, opacity, scaling, rotation, accum, denom, max_grad, min_opacity, percent_dense_extent, ws_limit, prune_mask, noise, generator):
-        self.lib = L.load()
         dev = self.dev = opacity.device
         P = self.P = opacity.shape[0]
         self.scaling, self.rotation = scaling, rotation
-        with torch.cuda.device(dev):
-            self.ws = torch.empty((self.lib.sr_densify_workspace_bytes(P),), dtype=torch.uint8, device=dev)
-            counts = (C.c_uint32 * 4)()
-            L.check(self.lib.sr_densify_plan(P, _ptr(accum), _ptr(denom), _ptr(opacity), _ptr(scaling), max_grad, min_opacity, percent_dense_extent,
-                                             ws_limit, _ptr(prune_mask), _ptr(self.ws), self.ws.numel(), counts, _stream(dev)), "sr_densify_plan")
-        self.c_counts = counts
+        self.ws = workspace("sr_densify_workspace_bytes", dev, P)
+        self.c_counts = counts = (C.c_uint32 * 4)()
+        call("sr_densify_plan", dev, P, ptr(accum), ptr(denom), ptr(opacity), ptr(scaling), max_grad, min_opacity, percent_dense_extent, ws_limit,
+             ptr(prune_mask), *buf(self.ws), counts)
         self.counts = K, Cl, S, H = tuple(int(c) for c in counts)
         self.P_out = K + Cl + 2 * H
         if noise is None:
@@ -236,12 +226,10 @@ class _Plan:
             words = (t.numel() // self.P if self.P else math.prod(t.shape[1:])) * t.element_size() // 4
             segs.append(L.SrDensifySegment(t.data_ptr(), out.data_ptr(), words, role))
             outs.append(out)
-        with torch.cuda.device(self.dev):
-            for at in range(0, len(segs), L.SR_DENSIFY_MAX_SEGMENTS):
-                part = segs[at:at + L.SR_DENSIFY_MAX_SEGMENTS]
-                L.check(self.lib.sr_densify_apply(self.P, self.c_counts, _ptr(self.noise), _ptr(self.rotation), _ptr(self.scaling),
-                                                  (L.SrDensifySegment * len(part))(*part), len(part), _ptr(self.ws), self.ws.numel(),
-                                                  _stream(self.dev)), "sr_densify_apply")
+        for at in range(0, len(segs), L.SR_DENSIFY_MAX_SEGMENTS):
+            part = segs[at:at + L.SR_DENSIFY_MAX_SEGMENTS]
+            call("sr_densify_apply", self.dev, self.P, self.c_counts, ptr(self.noise), ptr(self.rotation), ptr(self.scaling),
+                 (L.SrDensifySegment * len(part))(*part), len(part), *buf(self.ws))
         return outs
 
     def views(self):

@@ -9,24 +9,16 @@
 plain torch: the CPU checker (in float64: the truth) and the timing baseline on the GPU."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from ._call import buf, call, ptr, workspace as _workspace
 
 WINDOW_SIZE, WINDOW_SIGMA = 11, 1.5
 SSIM_C1, SSIM_C2 = 0.01 ** 2, 0.03 ** 2
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _checked(image, gt, sky, alpha):
@@ -47,21 +39,18 @@ def _checked(image, gt, sky, alpha):
 def image_loss_workspace(image):
     """The uint8 workspace a forward / backward pair on a [C,H,W] image shares."""
     Cn, H, W = image.shape
-    return torch.empty(L.load().sr_image_loss_workspace_bytes(int(W), int(H), int(Cn)), dtype=torch.uint8, device=image.device)
+    return _workspace("sr_image_loss_workspace_bytes", image.device, int(W), int(H), int(Cn))
 
 
 def image_loss_forward(image, gt, lambda_dssim=0.2, sky=None, alpha=None, workspace=None, out=None):
     """Raw forward on the current stream -> (out[3] = {loss, l1, ssim} on the device, workspace for image_loss_backward)."""
     image, gt, sky, alpha, (W, H, Cn) = _checked(image, gt, sky, alpha)
-    lib = L.load()
     dev = image.device
     if workspace is None:
         workspace = image_loss_workspace(image)
     if out is None:
         out = torch.empty(3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.sr_image_loss_forward(W, H, Cn, float(lambda_dssim), _ptr(image), _ptr(gt), _ptr(sky), _ptr(alpha), _ptr(workspace),
-                                          workspace.numel(), _ptr(out), _stream(dev)), "sr_image_loss_forward")
+    call("sr_image_loss_forward", dev, W, H, Cn, float(lambda_dssim), ptr(image), ptr(gt), ptr(sky), ptr(alpha), *buf(workspace), ptr(out))
     return out, workspace
 
 
@@ -69,16 +58,13 @@ def image_loss_backward(image, gt, workspace, g_loss, lambda_dssim=0.2, sky=None
     """Raw backward on the current stream: g_loss is the upstream scalar as a device tensor, workspace what image_loss_forward filled
     for the same inputs -> (g_image, g_sky, g_alpha), the last two None without the composite.  out = the tensors to write into."""
     image, gt, sky, alpha, (W, H, Cn) = _checked(image, gt, sky, alpha)
-    lib = L.load()
     dev = image.device
     g_loss = g_loss.to(dev).contiguous().float()
     if out is None:
         out = (torch.empty_like(image), None if sky is None else torch.empty_like(sky), None if sky is None else torch.empty_like(alpha))
     g_image, g_sky, g_alpha = out
-    with torch.cuda.device(dev):
-        L.check(lib.sr_image_loss_backward(W, H, Cn, float(lambda_dssim), _ptr(image), _ptr(gt), _ptr(sky), _ptr(alpha), _ptr(workspace),
-                                           workspace.numel(), _ptr(g_loss), _ptr(g_image), _ptr(g_sky), _ptr(g_alpha), _stream(dev)),
-                "sr_image_loss_backward")
+    call("sr_image_loss_backward", dev, W, H, Cn, float(lambda_dssim), ptr(image), ptr(gt), ptr(sky), ptr(alpha), *buf(workspace), ptr(g_loss),
+         ptr(g_image), ptr(g_sky), ptr(g_alpha))
     return g_image, g_sky, g_alpha
 
 

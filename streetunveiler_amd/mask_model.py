@@ -13,7 +13,6 @@ reference's `NaN * 0` yields NaN there), and a zero may differ in sign (`-0.0 + 
 `-0.0` for a negative delta).  Everything else is the same single float32 add, bit for bit."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from collections import namedtuple
 
@@ -21,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from ._call import call, ptr
 from .optim import SurfelAdam, row_mask_bytes
 
 # the six tensors, in the order of the reference's training_setup (the order of `base` / `delta` everywhere in this module)
@@ -102,14 +102,6 @@ def compose_masked_torch(base, delta, mask, fixed=()):
 
 
 # ---- the two kernel calls --------------------------------------------------------------------------------------------------------------
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _need_gpu(t, what):
     if t.dtype != torch.float32:
         raise ValueError(f"{what} needs float32 tensors; got {t.dtype} (compose_masked_torch takes any float dtype)")
@@ -125,10 +117,8 @@ def _compose_forward(base, delta, mask_u8, bits):
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=base[0].device)
     out = [None if bits & MASK_PROPERTY_BIT["xyz"] else new(P, 3), new(P, M, 3), None if bits & MASK_PROPERTY_BIT["opacity"] else new(P, 1),
            None if bits & MASK_PROPERTY_BIT["scaling"] else new(P, 2), None if bits & MASK_PROPERTY_BIT["rotation"] else new(P, 4)]
-    with torch.cuda.device(base[0].device):
-        L.check(L.load().sr_mask_compose(P, M, L.SrMaskTensors(*[_ptr(t) for t in base]), L.SrMaskTensors(*[_ptr(t) for t in delta]),
-                                         C.c_void_p(mask_u8.data_ptr()), bits, L.SrMaskEffective(*[_ptr(t) for t in out]),
-                                         _stream(base[0].device)), "sr_mask_compose")
+    call("sr_mask_compose", base[0].device, P, M, L.SrMaskTensors(*map(ptr, base)), L.SrMaskTensors(*map(ptr, delta)), ptr(mask_u8), bits,
+         L.SrMaskEffective(*map(ptr, out)))
     return out
 
 
@@ -139,9 +129,7 @@ def _compose_backward(upstream, mask_u8, bits, P, M, wanted):
     d = [torch.empty(shape, dtype=torch.float32, device=dev) if want else None for shape, want in zip(_row_shapes(P, M), wanted)]
     if any(wanted):
         _need_gpu(next(g for g in upstream if g is not None), "compose_masked")
-        with torch.cuda.device(dev):
-            L.check(L.load().sr_mask_compose_backward(P, M, L.SrMaskEffective(*[_ptr(g) for g in upstream]), C.c_void_p(mask_u8.data_ptr()), bits,
-                                                      L.SrMaskTensors(*[_ptr(t) for t in d]), _stream(dev)), "sr_mask_compose_backward")
+        call("sr_mask_compose_backward", dev, P, M, L.SrMaskEffective(*map(ptr, upstream)), ptr(mask_u8), bits, L.SrMaskTensors(*map(ptr, d)))
     return d
 
 

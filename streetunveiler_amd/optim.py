@@ -14,18 +14,13 @@ are zero for as long as the optimizer lives -- the masked-out rows of the refere
 (include/surfel_raster.h, sr_adam_step_rows, states the contract)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from ._call import call, ptr
 
 ADAM_CHUNK = L.SR_ADAM_CHUNK                    # elements a workgroup of adam_step_kernel handles per iteration
 ADAM_MAX_SEGMENTS = L.SR_ADAM_MAX_SEGMENTS      # tensors per launch
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _bias_terms(lr, step, beta1, beta2):
@@ -94,21 +89,18 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, ep
             seg = L.SrAdamRowSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step_size, bc2_sqrt,
                                      p.numel() // max(1, p.shape[0]))
         by_device.setdefault(p.device, []).append((seg, g, (p, m, v)))      # (g: a contiguous copy stays alive until the launch is enqueued)
-    lib = L.load()
     for dev, entries in by_device.items():
-        with torch.cuda.device(dev):
-            for at in range(0, len(entries), ADAM_MAX_SEGMENTS):
-                part = entries[at:at + ADAM_MAX_SEGMENTS]
-                if row_mask is None:
-                    table = (L.SrAdamSegment * len(part))(*[e[0] for e in part])
-                    L.check(lib.sr_adam_step(table, len(part), float(beta1), float(beta2), float(eps), _stream(dev)), "sr_adam_step")
-                else:
-                    table = (L.SrAdamRowSegment * len(part))(*[e[0] for e in part])
-                    L.check(lib.sr_adam_step_rows(table, len(part), row_mask.numel(), C.c_void_p(row_mask.data_ptr()), float(beta1), float(beta2),
-                                                  float(eps), _stream(dev)), "sr_adam_step_rows")
-                for e in part:
-                    for t in e[2]:
-                        torch.autograd.graph.increment_version(t)
+        for at in range(0, len(entries), ADAM_MAX_SEGMENTS):
+            part = entries[at:at + ADAM_MAX_SEGMENTS]
+            if row_mask is None:
+                table = (L.SrAdamSegment * len(part))(*[e[0] for e in part])
+                call("sr_adam_step", dev, table, len(part), float(beta1), float(beta2), float(eps))
+            else:
+                table = (L.SrAdamRowSegment * len(part))(*[e[0] for e in part])
+                call("sr_adam_step_rows", dev, table, len(part), row_mask.numel(), ptr(row_mask), float(beta1), float(beta2), float(eps))
+            for e in part:
+                for t in e[2]:
+                    torch.autograd.graph.increment_version(t)
 
 
 def adam_step_float64(params, grads, exp_avgs, exp_avg_sqs, lrs, steps, beta1, beta2, eps):
@@ -253,10 +245,7 @@ def densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_ra
         if not t.is_contiguous():
             raise ValueError(f"{name} is not contiguous: it is updated in place")
     viewspace_grad, radii = viewspace_grad.contiguous(), radii.contiguous()
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        L.check(L.load().sr_densification_stats(P, ptr(viewspace_grad), ptr(radii), ptr(xyz_gradient_accum), ptr(denom), ptr(max_radii2D),
-                                                _stream(dev)), "sr_densification_stats")
+    call("sr_densification_stats", dev, P, ptr(viewspace_grad), ptr(radii), ptr(xyz_gradient_accum), ptr(denom), ptr(max_radii2D))
 
 
 def densification_stats_torch(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D):

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._call import call, ptr
 
 _MAX_CALL = 1 << 30      # samples per launch (the C-ABI takes fewer than 2^31)
 
@@ -172,10 +173,6 @@ def _space(voxel_size, center, radius):
     return L.SrTsdfSpace(voxel_size, 1, (C.c_float * 3)(*c), float(radius))
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _pick(tsdf, rgb, weight, return_rgb, return_weight):
     out = (tsdf,) + ((rgb,) if return_rgb else ()) + ((weight,) if return_weight else ())
     return out if len(out) > 1 else tsdf
@@ -192,16 +189,13 @@ def unbounded_tsdf(samples, views, voxel_size, center=None, radius=None, return_
         raise ValueError(f"samples is on {samples.device}, the views on {views.device}")
     space, cv = _space(voxel_size, center, radius), views._c(return_rgb)
     pts = samples.detach().to(torch.float32).contiguous()
-    N, dev, lib = pts.shape[0], views.device, L.load()
-    with torch.cuda.device(dev):
-        tsdf = torch.empty((N,), dtype=torch.float32, device=dev)
-        rgb = torch.empty((N, 3), dtype=torch.float32, device=dev) if return_rgb else None
-        weight = torch.empty((N,), dtype=torch.float32, device=dev) if return_weight else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for at in range(0, N, _MAX_CALL):
-            n = min(_MAX_CALL, N - at)
-            L.check(lib.sr_tsdf_fuse(C.byref(cv), C.byref(space), n, _ptr(pts[at:]), _ptr(tsdf[at:]), None if rgb is None else _ptr(rgb[at:]),
-                                     None if weight is None else _ptr(weight[at:]), stream), "sr_tsdf_fuse")
+    N, dev = pts.shape[0], views.device
+    tsdf = torch.empty((N,), dtype=torch.float32, device=dev)
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev) if return_rgb else None
+    weight = torch.empty((N,), dtype=torch.float32, device=dev) if return_weight else None
+    tail = lambda t, at: None if t is None else ptr(t[at:])
+    for at in range(0, N, _MAX_CALL):
+        call("sr_tsdf_fuse", dev, C.byref(cv), C.byref(space), min(_MAX_CALL, N - at), ptr(pts[at:]), ptr(tsdf[at:]), tail(rgb, at), tail(weight, at))
     return _pick(tsdf, rgb, weight, return_rgb, return_weight)
 
 
@@ -234,17 +228,15 @@ def unbounded_tsdf_grid(views, lo, hi, dims, voxel_size, center=None, radius=Non
     if plane > _MAX_CALL:
         raise ValueError(f"one plane of {ny} x {nz} samples is more than one launch takes ({_MAX_CALL})")
     slab = max(1, min(int(slab) if slab else nx, _MAX_CALL // plane))
-    space, cv, dev, lib = _space(voxel_size, center, radius), views._c(return_rgb), views.device, L.load()
+    space, cv, dev = _space(voxel_size, center, radius), views._c(return_rgb), views.device
     c_dims, c_lo, c_step = (C.c_int32 * 3)(*dims), (C.c_float * 3)(*lo.tolist()), (C.c_float * 3)(*step.tolist())
-    with torch.cuda.device(dev):
-        tsdf = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
-        rgb = torch.empty((nx, ny, nz, 3), dtype=torch.float32, device=dev) if return_rgb else None
-        weight = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev) if return_weight else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for x0 in range(0, nx, slab):
-            L.check(lib.sr_tsdf_fuse_grid(C.byref(cv), C.byref(space), c_dims, c_lo, c_step, x0, min(nx, x0 + slab), _ptr(tsdf[x0:]),
-                                          None if rgb is None else _ptr(rgb[x0:]), None if weight is None else _ptr(weight[x0:]), stream),
-                    "sr_tsdf_fuse_grid")
+    tsdf = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev)
+    rgb = torch.empty((nx, ny, nz, 3), dtype=torch.float32, device=dev) if return_rgb else None
+    weight = torch.empty((nx, ny, nz), dtype=torch.float32, device=dev) if return_weight else None
+    tail = lambda t, x0: None if t is None else ptr(t[x0:])
+    for x0 in range(0, nx, slab):
+        call("sr_tsdf_fuse_grid", dev, C.byref(cv), C.byref(space), c_dims, c_lo, c_step, x0, min(nx, x0 + slab), ptr(tsdf[x0:]), tail(rgb, x0),
+             tail(weight, x0))
     return _pick(tsdf, rgb, weight, return_rgb, return_weight)
 
 

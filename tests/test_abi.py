@@ -155,7 +155,6 @@ def test_workspace_sizes_are_the_recorded_ones(lib):
     import json
     with open(os.path.join(ROOT, "tests", "golden", "workspace_sizes.json")) as f:
         recorded = json.load(f)
-    lib.sr_source_digest.restype = ctypes.c_char_p
     assert recorded["recorded_from_source_digest"] != lib.sr_source_digest().decode()      # not recorded from the library under test
     assert {0, 1} <= set(recorded["counts"])
     for b in (256, 2048, 65536, 262144, 524288):
@@ -341,6 +340,145 @@ def test_library_carries_the_digest_of_the_tree(lib):
     from streetunveiler_amd import build as sb
     want = sb.source_digest()
     assert sb.embedded_digest(sb.LIB) == want
-    lib.sr_source_digest.restype = ctypes.c_char_p
     assert lib.sr_source_digest().decode() == want
     assert sb.embedded_digest(__file__) is None   # (a file without the tag)
+
+
+# ---- the binding against the header's text ---------------------------------------------------------------------------------------------
+# _lib.PROTOTYPES, the Sr* structures and the mirrored SR_* constants are a second, hand-kept statement of include/surfel_raster.h: a wrong
+# width or a missing size_t in an argument list corrupts the call frame silently, and only on the GPU machine.  Held here to the header
+# itself, parsed with regular expressions (it is regular: one declarator per parameter, no function pointers, no nested structures).
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+            "uint8_t": ctypes.c_uint8, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double, "int": ctypes.c_int}
+_DECLARATOR = re.compile(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w+(?:\s*,\s*\w+)*)\s*(?:\[(\d+)\])?")
+
+
+def _header_code():
+    with open(os.path.join(ROOT, "include", "surfel_raster.h")) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+def _header_prototypes():
+    """{name: (return type text, [(base type, is pointer)])} of every function the header declares."""
+    found = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w ]*?\*?)\s*\b(sr_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _header_code(), flags=re.M):
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = _DECLARATOR.fullmatch(" ".join(p.split()))
+            assert m and m.group(4) is None and "," not in m.group(3), (name, p)
+            args.append((m.group(1), m.group(2) == "*"))
+        assert name not in found, name
+        found[name] = (" ".join(ret.split()), args)
+    return found
+
+
+def _header_structs():
+    """{name: [(field, ctypes type)]}: a pointer field is a c_void_p, an array field the array type, a scalar itself."""
+    found = {}
+    for name, body in re.findall(r"typedef struct (Sr\w+) \{(.*?)\}\s*\1;", _header_code(), flags=re.S):
+        fields = []
+        for decl in body.split(";"):
+            if not decl.strip():
+                continue
+            m = _DECLARATOR.fullmatch(" ".join(decl.split()))
+            assert m, (name, decl)
+            base, pointer, names, count = m.groups()
+            ctype = ctypes.c_void_p if pointer else _SCALARS[base]
+            for field in names.replace(" ", "").split(","):
+                fields.append((field, ctype * int(count) if count else ctype))
+        found[name] = fields
+    return found
+
+
+def test_prototype_table_matches_header():
+    declared = _header_prototypes()
+    assert sorted(declared) == _declared_functions() and list(declared) == list(_lib.PROTOTYPES)      # every function once, in the header's order
+    returns = dict(_SCALARS, **{"void": None, "const char*": ctypes.c_char_p})
+    for name, (ret, params) in declared.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert restype is returns[ret], (name, ret, restype)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for k, ((base, pointer), got) in enumerate(zip(params, argtypes)):
+            if not pointer:
+                allowed = [_SCALARS[base]]
+            elif base.startswith("Sr"):
+                allowed = [ctypes.POINTER(getattr(_lib, base))]
+            elif base == "void":
+                allowed = [ctypes.c_void_p]
+            else:      # a device or host array of scalars: untyped, or typed by its pointee
+                allowed = [ctypes.c_void_p, ctypes.POINTER(_SCALARS[base])]
+            assert any(got is a for a in allowed), (name, k, base, pointer, got)
+        if params and params[-1] == ("void", True) and not name.endswith(("_bytes", "_view")):
+            assert argtypes[-1] is ctypes.c_void_p      # (the `void* stream` _call.call appends)
+
+
+def test_prototypes_are_applied_to_the_library(lib):
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def _c_layout(fields):
+    """(offsets, size) the C layout rules give: every member aligned to its own (element) size, the whole to the largest of them."""
+    offsets, at, widest = [], 0, 1
+    for _, ctype in fields:
+        align = ctypes.sizeof(getattr(ctype, "_type_", ctype)) if hasattr(ctype, "_length_") else ctypes.sizeof(ctype)
+        at = (at + align - 1) // align * align
+        offsets.append(at)
+        at += ctypes.sizeof(ctype)
+        widest = max(widest, align)
+    return offsets, (at + widest - 1) // widest * widest
+
+
+def test_every_struct_matches_header():
+    declared = _header_structs()
+    bound = {name: t for name, t in vars(_lib).items() if isinstance(t, type) and issubclass(t, ctypes.Structure)}
+    assert sorted(declared) == sorted(bound) and len(declared) == 13
+    for name, fields in declared.items():
+        got = bound[name]._fields_
+        assert [f[0] for f in got] == [f[0] for f in fields], name
+        for (field, want), (_, have) in zip(fields, got):
+            same = (have._type_ is want._type_ and have._length_ == want._length_) if hasattr(want, "_length_") else have is want
+            assert same, (name, field, want, have)
+        offsets, size = _c_layout(fields)
+        assert [getattr(bound[name], f).offset for f, _ in fields] == offsets and ctypes.sizeof(bound[name]) == size, name
+
+
+def test_mirrored_constants_match_header():
+    code = _header_code()
+    defines = {name: int(value.rstrip("u"), 0) for name, value in re.findall(r"^#define (SR_\w+) (\w+)\b", code, flags=re.M)}
+    mirrored = {name: v for name, v in vars(_lib).items() if name.startswith("SR_") and isinstance(v, int)}
+    for family, count in (("SR_FLAG_", 11), ("SR_ACT_", 3), ("SR_MASK_FIXED_", 6), ("SR_DENSIFY_", 13), ("SR_ADAM_", 2), ("SR_ABI_VERSION", 1)):
+        assert sum(name.startswith(family) for name in mirrored) == sum(name.startswith(family) for name in defines) == count, family
+    for name, value in mirrored.items():
+        assert defines.get(name) == value, (name, value, defines.get(name))
+    stages = re.search(r"typedef enum SrStage \{(.*?)\} SrStage;", code, flags=re.S).group(1)
+    stages = sorted((int(v), name) for name, v in re.findall(r"(SR_STAGE_\w+) = (\d+)", stages))
+    assert [v for v, _ in stages] == list(range(len(stages))) and stages[-1] == (len(_lib.SR_STAGE_NAMES), "SR_STAGE_COUNT")
+    assert _lib.SR_STAGE_NAMES == [name[len("SR_STAGE_"):].lower() for _, name in stages[:-1]]
+
+
+def test_ptr_maps_nothing_to_null():
+    import torch
+    from streetunveiler_amd._call import buf, ptr
+    assert ptr(None) is None and ptr(torch.empty(0)) is None and ptr(torch.empty((0, 3))) is None
+    one = torch.zeros(1)
+    assert isinstance(ptr(one), ctypes.c_void_p) and ptr(one).value == one.data_ptr()
+    address, size = buf(torch.zeros(5, dtype=torch.uint8))
+    assert isinstance(address, ctypes.c_void_p) and size == 5
+
+
+@pytest.mark.gpu
+def test_refusal_through_call_carries_name_and_message(lib):
+    """An ARGUMENT refusal, taken before any launch (sr_opacity_shrink_forward checks P < 1 first): _call.call raises SurfelRasterError
+    with the function's name and the text of sr_last_error()."""
+    import torch
+    from streetunveiler_amd._call import buf, call, ptr
+    dev = torch.device("cuda:0")
+    opacity, ws, out = torch.zeros(4, device=dev), torch.empty(256, dtype=torch.uint8, device=dev), torch.empty(1, device=dev)
+    with pytest.raises(_lib.SurfelRasterError) as err:
+        call("sr_opacity_shrink_forward", dev, 0, ptr(opacity), 0, *buf(ws), ptr(out))
+    last = lib.sr_last_error().decode()
+    assert last == "P 0 < 1" and "sr_opacity_shrink_forward" in str(err.value) and last in str(err.value)
+    with pytest.raises(_lib.SurfelRasterError, match=r"sr_adam_step failed \(-1\): n_segments 0 not in 1\.\.8"):
+        call("sr_adam_step", dev, (_lib.SrAdamSegment * 1)(), 0, 0.9, 0.999, 1e-8)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from streetunveiler_amd._call import stream
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians, synthetic_upstream_grads
 
 pytestmark = pytest.mark.gpu
@@ -289,7 +290,7 @@ def test_lds_atomic_returns_in_lane_order():
         g = torch.Generator().manual_seed(bins)
         digits = torch.randint(0, 2 ** 31 - 1, (n,), generator=g, dtype=torch.int64).to(torch.int32).to(dev)
         ranks = torch.empty(n, dtype=torch.int32, device=dev)
-        assert lib.sr_debug_lds_atomic_ranks(digits.data_ptr(), ranks.data_ptr(), n, bins, torch.cuda.current_stream().cuda_stream) == 0
+        assert lib.sr_debug_lds_atomic_ranks(digits.data_ptr(), ranks.data_ptr(), n, bins, stream()) == 0
         torch.cuda.synchronize()
         d = (digits.cpu().numpy().view(np.uint32) % np.uint32(bins)).reshape(-1, 8, 4, 64)      # block, step, wave, lane
         r = ranks.cpu().numpy().reshape(-1, 8, 4, 64)
@@ -308,7 +309,6 @@ def test_lds_atomic_returns_in_lane_order():
 
 def test_radix_sort_stability_and_edges():
     """The hand-written LSD radix sort behind K2/K4: stable, correct at ragged sizes and for every bit count."""
-    import ctypes as C
     from streetunveiler_amd import _lib
     lib = _lib.load()
     dev = "cuda:0"
@@ -337,7 +337,7 @@ def test_radix_sort_stability_and_edges():
                 if (flags & _lib.SR_FLAG_ONE_SWEEP_SORT) and not (bits == 32 and n >= (1 << 18)):
                     continue
                 rc = lib.sr_debug_radix_sort(k.data_ptr(), None if v is None else v.data_ptr(), ko.data_ptr(), vo.data_ptr(), n, bits,
-                                             tmp.data_ptr(), tmp.numel(), flags, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                                             tmp.data_ptr(), tmp.numel(), flags, stream())
                 _lib.check(rc, "sr_debug_radix_sort")
                 torch.cuda.synchronize()
                 order = np.argsort(keys, kind="stable")
@@ -355,7 +355,7 @@ def test_rank_self_check_and_forced_ballot_fallback():
     from tests.gpu_util import DEV, run_hip_raw, run_oracle, settings_for
     from diff_surfel_rasterization import _C
     lib = _lib.load()
-    mode = lib.sr_rank_mode(C_void(torch.cuda.current_stream().cuda_stream))
+    mode = lib.sr_rank_mode(stream())
     assert mode in (1, 2), f"sr_rank_mode: {mode} ({lib.sr_last_error()})"
     assert mode == 1, "gfx950 returns LDS atomic results in lane order: the fast ranking should have been selected"
     for (P, W, H, tile) in [(40000, 640, 360, None), (15000, 640, 200, (8, 8))]:
@@ -383,11 +383,6 @@ def test_rank_self_check_and_forced_ballot_fallback():
         order = np.argsort(fwd["depths"].view(np.uint32)[fwd["radii"] > 0], kind="stable")
         np.testing.assert_array_equal(outs[0][1][:V], np.flatnonzero(fwd["radii"] > 0)[order].astype(outs[0][1].dtype))
         np.testing.assert_array_equal(outs[0][4], outs[1][4])
-
-
-def C_void(x):
-    import ctypes
-    return ctypes.c_void_p(x)
 
 
 def test_sh_layout_fallbacks_and_scale_modifier():

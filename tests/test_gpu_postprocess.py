@@ -2,13 +2,11 @@
 the bar of tests/postprocess_cases.py (float64 truth, the float32 restatement's own deviation as the yardstick), at every size x depth ratio
 x camera of that module; and the paths autograd never takes: null upstream gradients at the C-ABI, buffers whose previous content must not
 matter, borrowed / float64 inputs, and the elements around every output at the sizes without an interior."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from streetunveiler_amd import _lib as L
+from streetunveiler_amd._call import call, ptr
 from streetunveiler_amd.gaussian_renderer import PipelineParams, postprocess_allmap
 from tests import postprocess_cases as pc
 
@@ -39,10 +37,6 @@ def test_maps_and_gradient_within_bar(size, ratio, cam_name):
         pc.assert_within_bar(got, c["truth"], c["ref"], "postprocess.hip " + c["name"])
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _guarded(n, fill=float("nan")):
     """-> (whole buffer, the n floats in its middle)"""
     buf = torch.full((n + 2 * GUARD,), fill, dtype=torch.float32, device=DEV)
@@ -59,8 +53,7 @@ def _abi_forward(cam, ratio, allmap, outs=None):
     view = cam.world_view_transform.to(DEV).contiguous().float()
     if outs is None:
         outs = [torch.full((ch * H * W,), float("nan"), device=DEV) for ch in (3, 1, 3, 3)]
-    L.check(L.load().sr_postprocess_forward(W, H, cam.FoVx, cam.FoVy, ratio, _ptr(view), _ptr(allmap), *[_ptr(o) for o in outs],
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "sr_postprocess_forward")
+    call("sr_postprocess_forward", view.device, W, H, cam.FoVx, cam.FoVy, ratio, ptr(view), ptr(allmap), *map(ptr, outs))
     torch.cuda.synchronize()
     return outs
 
@@ -72,8 +65,7 @@ def _abi_backward(cam, ratio, allmap, ups, scratch=None, g_allmap=None, scratch_
     view = cam.world_view_transform.to(DEV).contiguous().float()
     scratch = torch.full((6 * H * W,), scratch_fill, device=DEV) if scratch is None else scratch
     g_allmap = torch.full((7 * H * W,), float("nan"), device=DEV) if g_allmap is None else g_allmap
-    L.check(L.load().sr_postprocess_backward(W, H, cam.FoVx, cam.FoVy, ratio, _ptr(view), _ptr(allmap), *[_ptr(u) for u in ups], _ptr(scratch),
-                                             _ptr(g_allmap), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "sr_postprocess_backward")
+    call("sr_postprocess_backward", view.device, W, H, cam.FoVx, cam.FoVy, ratio, ptr(view), ptr(allmap), *map(ptr, ups), ptr(scratch), ptr(g_allmap))
     torch.cuda.synchronize()
     return g_allmap
 

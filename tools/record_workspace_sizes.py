@@ -51,7 +51,6 @@ if __name__ == "__main__":
     from streetunveiler_amd.build import source_digest
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "workspace_sizes.json")
     lib = _lib.load()
-    lib.sr_source_digest.restype = __import__("ctypes").c_char_p
     digest = lib.sr_source_digest().decode()
     if digest == source_digest():
         sys.exit("this library was built from the sources of this tree: it is the one under test, not a reference (set SURFEL_RASTER_LIB)")
