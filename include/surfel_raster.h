@@ -434,6 +434,32 @@ int sr_opacity_shrink_forward(int64_t P, const float* opacity, int32_t activated
                               void* stream);
 int sr_opacity_shrink_backward(int64_t P, const float* opacity, int32_t activated, const float* g_loss, float* g_opacity, void* stream);
 
+/* The per-pixel part of the sky model == SkyModel.render_with_camera of the reference's scene/env_map.py with its constructor defaults,
+ * csrc/sky.hip.  Every pixel of a frame hands that model the same position, so the caller folds the 95 position channels of the first
+ * layer into one vector c[64] = W0[:, 16:] feat + b0 and these calls do what differs per pixel, in float32:
+ *   dir = R ((i - cx) / fx, -(j - cy) / fy, -1) for pixel column i, row j (NOT normalised);  sh[16] = torch-ngp's degree-4 shencoder of dir;
+ *   out[:, j, i] = sigmoid(W3 relu(W2 relu(W1 relu(W0sh sh + c) + b1) + b2) + b3).
+ * cam: 13 device floats {fx, fy, cx, cy, R[9] row-major (c2w[:3, :3])}; w0sh [64,16] (the SH columns of the first layer), c [64],
+ * w1, w2 [64,64], b1, b2 [64], w3 [3,64], b3 [3], all row-major device float32; out and g_out [3,H,W].
+ * sr_sky_forward keeps nothing for the backward.  sr_sky_backward recomputes the activations and writes the gradients whose pointers
+ * are given (NULL: not wanted; none wanted: no work), shaped like their weights; cam gets no gradient.  No atomics: a grid of at most
+ * max_workgroups workgroups (0: the library's default) sweeps the image 256 pixels at a time, each workgroup keeps ONE float64 set of
+ * the 9603 sums, stores it to the workspace, and a second kernel adds the sets in index order and rounds once.  The workspace,
+ * sr_sky_workspace_bytes(max_workgroups) bytes, therefore depends on the workgroup count and not on W * H; two calls with equal
+ * arguments give equal bits, another max_workgroups another order of the same sum.  relu keeps a NaN; its derivative passes the
+ * gradient unless the activation is <= 0, as torch's does.
+ * SR_ERR_INVALID_ARGUMENT before any launch for W or H < 0, max_workgroups outside 0..65536, a NULL cam or weight, a NULL out / g_out
+ * or workspace with work to do; SR_ERR_BUFFER_TOO_SMALL for a short workspace; SR_ERR_UNSUPPORTED for 2^31 pixels or more.  W * H == 0
+ * is no error and no work.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_sky_workspace_bytes(int32_t max_workgroups);
+int sr_sky_forward(int32_t image_width, int32_t image_height, const float* cam, const float* w0sh, const float* c, const float* w1,
+                   const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int32_t max_workgroups, float* out,
+                   void* stream);
+int sr_sky_backward(int32_t image_width, int32_t image_height, const float* cam, const float* w0sh, const float* c, const float* w1,
+                    const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const float* g_out,
+                    int32_t max_workgroups, void* workspace, size_t workspace_bytes, float* g_w0sh, float* g_c, float* g_w1, float* g_b1,
+                    float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* stream);
+
 /* One Adam step over up to SR_ADAM_MAX_SEGMENTS float32 tensors in ONE launch == torch.optim.Adam (no weight decay, no amsgrad, not
  * maximising) as the reference builds it in scene/gaussian_model.py:171-180 and steps it in train.py:197.  Per element, in float32 and
  * in the order of torch's single-tensor path, with correctly rounded division and square root and no contraction:

@@ -14,7 +14,8 @@ _TSDF = ("TsdfViews", "unbounded_tsdf", "unbounded_tsdf_grid", "unbounded_tsdf_t
 _MASK_MODEL = ("MaskedSurfelModel", "compose_masked", "compose_masked_torch")
 _AUX_LOSS = ("semantic_cross_entropy", "surface_regularisers", "opacity_shrink", "SemanticCrossEntropy", "semantic_cross_entropy_torch",
              "surface_regularisers_torch", "opacity_shrink_torch")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS)
+_SKY = ("SkyModel", "sky_rays_mlp", "sky_forward_torch", "position_features")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -39,4 +40,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _AUX_LOSS:
         from . import aux_loss
         return getattr(aux_loss, name)
+    if name in _SKY:
+        from . import sky
+        return getattr(sky, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -153,6 +153,9 @@ PROTOTYPES = {
     "sr_surface_reg_backward": (_int, [_i32, _i32, _vp, _vp, _f64, _f64] + [_vp] * 5),
     "sr_opacity_shrink_forward": (_int, [_i64, _vp, _i32] + _WS + [_vp, _vp]),
     "sr_opacity_shrink_backward": (_int, [_i64, _vp, _i32, _vp, _vp, _vp]),
+    "sr_sky_workspace_bytes": (_sz, [_i32]),
+    "sr_sky_forward": (_int, [_i32, _i32] + [_vp] * 9 + [_i32, _vp, _vp]),
+    "sr_sky_backward": (_int, [_i32, _i32] + [_vp] * 10 + [_i32] + _WS + [_vp] * 9),
     "sr_adam_step": (_int, [_P(SrAdamSegment), _i32, _f64, _f64, _f64, _vp]),
     "sr_adam_step_rows": (_int, [_P(SrAdamRowSegment), _i32, _i32, _vp, _f64, _f64, _f64, _vp]),
     "sr_mask_compose": (_int, [_i32, _i32, _P(SrMaskTensors), _P(SrMaskTensors), _vp, _u32, _P(SrMaskEffective), _vp]),

@@ -34,6 +34,7 @@ SOURCES = [
     ("render_class.hip", []),
     ("postprocess.hip", []),
     ("image_loss.hip", []),
+    ("sky.hip", []),                            # the fmaf()s are written out; contraction of the few other expressions is within its float32 bar
     ("aux_loss.hip", ["-ffp-contract=off"]),    # every element is ONE float64 expression rounded once: written as it is evaluated
     ("optimizer.hip", ["-ffp-contract=off"]),   # the Adam step's operation order is the one torch's single-tensor path states
     ("mask_model.hip", ["-ffp-contract=off"]),  # the effective value is ONE float32 add: base + delta, never part of a fused operation

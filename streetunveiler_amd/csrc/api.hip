@@ -1076,6 +1076,54 @@ int sr_opacity_shrink_backward(int64_t P, const float* opacity, int32_t activate
     return SR_OK;
 }
 
+size_t sr_sky_workspace_bytes(int32_t max_workgroups) { return max_workgroups >= 0 ? sky_workspace_bytes(max_workgroups) : 0; }
+
+namespace {
+
+constexpr int kSkyMaxGroups = 1 << 16;
+
+int sky_args(const char* what, int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1,
+             const float* w2, const float* b2, const float* w3, const float* b3, int32_t max_workgroups, SkyWeights* p) {
+    if (W < 0 || H < 0) return fail(SR_ERR_INVALID_ARGUMENT, "%s: bad image size %dx%d", what, W, H);
+    if (max_workgroups < 0 || max_workgroups > kSkyMaxGroups)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%s: max_workgroups %d not in 0..%d", what, max_workgroups, kSkyMaxGroups);
+    if ((int64_t)W * (int64_t)H > 0x7fffffffll) return fail(SR_ERR_UNSUPPORTED, "%s: %dx%d is 2^31 pixels or more", what, W, H);
+    if (!cam || !w0sh || !c || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return fail(SR_ERR_INVALID_ARGUMENT, "%s: cam or a weight pointer is NULL", what);
+    *p = SkyWeights{w0sh, c, w1, b1, w2, b2, w3, b3};
+    return SR_OK;
+}
+
+}  // namespace
+
+int sr_sky_forward(int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1, const float* w2,
+                   const float* b2, const float* w3, const float* b3, int32_t max_workgroups, float* out, void* stream) {
+    SkyWeights p;
+    if (int rc = sky_args("sr_sky_forward", W, H, cam, w0sh, c, w1, b1, w2, b2, w3, b3, max_workgroups, &p)) return rc;
+    if (W == 0 || H == 0) return SR_OK;
+    if (!out) return fail(SR_ERR_INVALID_ARGUMENT, "sr_sky_forward: out is NULL");
+    SR_HIP(launch_sky_forward(W, H, cam, p, max_workgroups, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_sky_backward(int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* w3, const float* b3, const float* g_out, int32_t max_workgroups, void* workspace,
+                    size_t workspace_bytes, float* g_w0sh, float* g_c, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3,
+                    void* stream) {
+    SkyWeights p;
+    if (int rc = sky_args("sr_sky_backward", W, H, cam, w0sh, c, w1, b1, w2, b2, w3, b3, max_workgroups, &p)) return rc;
+    if (W == 0 || H == 0) return SR_OK;
+    if (!g_out) return fail(SR_ERR_INVALID_ARGUMENT, "sr_sky_backward: g_out is NULL");
+    float* const grads[8] = {g_w0sh, g_c, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+    bool any = false;
+    for (float* g : grads) any = any || g != nullptr;
+    if (!any) return SR_OK;
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "sr_sky_backward: workspace is NULL");
+    if (workspace_bytes < sky_workspace_bytes(max_workgroups))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "sr_sky_backward: workspace %zu < %zu", workspace_bytes, sky_workspace_bytes(max_workgroups));
+    SR_HIP(launch_sky_backward(W, H, cam, p, g_out, max_workgroups, workspace, grads, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream) {
     if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
     if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)

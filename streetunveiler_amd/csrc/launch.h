@@ -1,7 +1,7 @@
 // launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
-// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, DensifyRule and the three Tsdf
+// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, SkyWeights, DensifyRule and the three Tsdf
 // structs, which their kernels take by value.
 #pragma once
 #include "common.h"
@@ -190,6 +190,21 @@ hipError_t launch_surface_reg_backward(const SurfaceRegArgs& a, const float* g_l
                                        hipStream_t s);
 hipError_t launch_opacity_shrink_forward(size_t P, const float* opacity, bool activated, void* workspace, float* out1, hipStream_t s);
 hipError_t launch_opacity_shrink_backward(size_t P, const float* opacity, bool activated, const float* g_loss, float* g_opacity, hipStream_t s);
+
+// ---- sky.hip -------------------------------------------------------------------------------------------------------------------------
+constexpr int kSkyParams = 64 * 16 + 64 + 2 * (64 * 64 + 64) + 3 * 64 + 3;   // 9603: {W0sh c W1 b1 W2 b2 W3 b3}
+constexpr int kSkyParamsPadded = kSkyParams + 1;
+constexpr int kSkyDefaultForwardGroups = 1024;    // workgroups of 256 pixels where max_workgroups == 0: a few per CU
+constexpr int kSkyDefaultBackwardGroups = 256;    // one per CU: its sums, weights and panels take most of a CU's LDS
+struct SkyWeights {        // a kernel parameter, by value: device pointers
+    const float *w0sh, *c, *w1, *b1, *w2, *b2, *w3, *b3;
+};
+int sky_backward_groups(int max_workgroups);
+size_t sky_workspace_bytes(int max_workgroups);   // the float64 parameter-gradient set of every workgroup of the backward
+hipError_t launch_sky_forward(int W, int H, const float* cam, const SkyWeights& p, int max_workgroups, float* out, hipStream_t s);
+// grads: g_w0sh, g_c, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3; a NULL pointer is skipped
+hipError_t launch_sky_backward(int W, int H, const float* cam, const SkyWeights& p, const float* g_out, int max_workgroups, void* workspace,
+                               float* const (&grads)[8], hipStream_t s);
 
 // ---- optimizer.hip -------------------------------------------------------------------------------------------------------------------
 bool adam_supported(const SrAdamSegment* segments, int n_segments);
