@@ -665,6 +665,35 @@ int sr_tsdf_fuse(const SrTsdfViews* views, const SrTsdfSpace* space, int32_t n, 
 int sr_tsdf_fuse_grid(const SrTsdfViews* views, const SrTsdfSpace* space, const int32_t* dims, const float* lo, const float* step,
                       int32_t ix_begin, int32_t ix_end, float* tsdf, float* rgb, float* weight, void* stream);
 
+/* Marching cubes on a resident float32 volume (csrc/mesh.hip; the case table and its conventions: csrc/mc_table.h, derived by
+ * tools/make_mc_table.py): volume [dims[0], dims[1], dims[2]] with the last axis fastest -- what sr_tsdf_fuse_grid fills -- -> an indexed,
+ * welded triangle mesh, vertices [Nv,3] float32 and faces [Nf,3] int32.  Two calls with one host read-back between them, which is the
+ * caller's: sr_mesh_count leaves counts[2] = {Nv, Nf} in DEVICE memory; the caller reads them, allocates and calls sr_mesh_emit with the
+ * same volume, dims, level and workspace (sr_mesh_workspace_bytes(dims) bytes of device memory, 16-B aligned: 5 bytes a grid point + 16
+ * per 4096 grid points; 0 for dims no call accepts).
+ *     inside means value < level, strictly; grid point (ix, iy, iz) has the linear index (ix dims[1] + iy) dims[2] + iz;
+ *     a grid point OWNS the vertex of each of its three forward edges (axis x, y, z) whose two ends are finite and differ in `inside`;
+ *     the cell whose lowest corner a grid point is yields the triangles of its case (bit c = corner c inside) iff its eight corners are
+ *     finite; an edge with a NaN or inf end owns no vertex, a cell with such a corner emits no triangle;
+ *     vertices ascend by (linear index of the owning point, axis x < y < z), faces by (linear index of the cell's lowest corner, order
+ *     in the table); a face holds vertex indices; its normal (right-hand rule) points towards the larger values;
+ *     the vertex on the edge from grid point i to i + 1 along an axis: t = (level - a) / (b - a) in float32 (IEEE division), a the value
+ *     at i; its coordinate along that axis is fmaf(i + t, step[axis], lo[axis]), the other two are fmaf(index, step, lo) -- the grid
+ *     points of sr_tsdf_fuse_grid.  A vertex at t == 0 or t == 1 is kept: zero-area triangles are legal, the topology stays closed.
+ *     With space != NULL and space->contract != 0 each vertex y is then replaced by uncontract(y) radius + center as sr_tsdf_fuse states
+ *     it (voxel_size is not read); else the vertices stay in grid coordinates.
+ * A grid with an axis of length 1 has no cells: an empty mesh (counts = {0, 0}), no error.  Exclusive prefix sums, no atomics: equal
+ * inputs give equal bits.  A count reads 0xFFFFFFFF where Nv or 3 Nf does not fit in int32: no mesh this ABI can index.
+ * Both calls check every argument before their first HIP call (SR_ERR_INVALID_ARGUMENT: a NULL pointer, a non-positive dim, a NaN level,
+ * a workspace too small or not 16-B aligned, a negative count, faces without vertices; SR_ERR_UNSUPPORTED: 2^31 grid points or more,
+ * 3 n_faces beyond int32), run on the caller's stream, allocate nothing and read nothing back.  All offsets into the volume are 64-bit.
+ * Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_mesh_workspace_bytes(const int32_t* dims);
+int sr_mesh_count(const float* volume, const int32_t* dims, float level, void* workspace, size_t workspace_bytes, uint32_t* counts,
+                  void* stream);
+int sr_mesh_emit(const float* volume, const int32_t* dims, float level, const float* lo, const float* step, const SrTsdfSpace* space,
+                 void* workspace, size_t workspace_bytes, int32_t n_vertices, int32_t n_faces, float* vertices, int32_t* faces, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

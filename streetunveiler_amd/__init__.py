@@ -15,7 +15,9 @@ _MASK_MODEL = ("MaskedSurfelModel", "compose_masked", "compose_masked_torch")
 _AUX_LOSS = ("semantic_cross_entropy", "surface_regularisers", "opacity_shrink", "SemanticCrossEntropy", "semantic_cross_entropy_torch",
              "surface_regularisers_torch", "opacity_shrink_torch")
 _SKY = ("SkyModel", "sky_rays_mlp", "sky_forward_torch", "position_features")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY)
+_MESH = ("marching_cubes", "marching_cubes_numpy", "extract_mesh_unbounded", "contracted_bound", "SurfelMesh")
+_MESH_PLY = ("write_mesh_ply", "read_mesh_ply")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -43,4 +45,10 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _SKY:
         from . import sky
         return getattr(sky, name)
+    if name in _MESH:
+        from . import mesh
+        return getattr(mesh, name)
+    if name in _MESH_PLY:
+        from . import ply
+        return getattr(ply, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

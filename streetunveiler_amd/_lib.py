@@ -166,6 +166,9 @@ PROTOTYPES = {
     "sr_densify_apply": (_int, [_i32, _P(_u32), _vp, _vp, _vp, _P(SrDensifySegment), _i32] + _WS + [_vp]),
     "sr_tsdf_fuse": (_int, [_P(SrTsdfViews), _P(SrTsdfSpace), _i32] + [_vp] * 5),
     "sr_tsdf_fuse_grid": (_int, [_P(SrTsdfViews), _P(SrTsdfSpace), _P(_i32), _P(_f32), _P(_f32), _i32, _i32] + [_vp] * 4),
+    "sr_mesh_workspace_bytes": (_sz, [_P(_i32)]),
+    "sr_mesh_count": (_int, [_vp, _P(_i32), _f32] + _WS + [_vp, _vp]),
+    "sr_mesh_emit": (_int, [_vp, _P(_i32), _f32, _P(_f32), _P(_f32), _P(SrTsdfSpace)] + _WS + [_i32, _i32, _vp, _vp, _vp]),
     "sr_debug_pair_decisions": (_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
     "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
     "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),

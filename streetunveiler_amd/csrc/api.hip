@@ -1369,6 +1369,62 @@ int sr_tsdf_fuse_grid(const SrTsdfViews* views, const SrTsdfSpace* space, const 
     return SR_OK;
 }
 
+// the checks sr_mesh_count and sr_mesh_emit share -> the kernels' view of the grid; *cells = 0 for a grid with an axis of length 1
+static int mesh_arguments(const float* volume, const int32_t* dims, float level, const void* workspace, size_t workspace_bytes, MeshGrid* g, bool* cells) {
+    if (!volume) return fail(SR_ERR_INVALID_ARGUMENT, "volume is NULL");
+    if (!dims) return fail(SR_ERR_INVALID_ARGUMENT, "dims is NULL");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return fail(SR_ERR_INVALID_ARGUMENT, "dims %d x %d x %d: every axis holds at least one sample", dims[0], dims[1], dims[2]);
+    if (level != level) return fail(SR_ERR_INVALID_ARGUMENT, "level is NaN");
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];   // < 2^62: the product below cannot wrap
+    const unsigned long long n = plane < (1ull << 31) ? plane * (unsigned long long)dims[2] : plane;
+    if (n >= (1ull << 31))
+        return fail(SR_ERR_UNSUPPORTED, "a grid of %d x %d x %d points: fewer than 2^31", dims[0], dims[1], dims[2]);
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < mesh_workspace_bytes((uint32_t)n)) return fail(SR_ERR_INVALID_ARGUMENT, "workspace %zu < %zu", workspace_bytes, mesh_workspace_bytes((uint32_t)n));
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    if ((uintptr_t)volume & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "volume is not 4-B aligned");
+    *g = MeshGrid{dims[0], dims[1], dims[2], (uint32_t)n, level};
+    *cells = dims[0] > 1 && dims[1] > 1 && dims[2] > 1;
+    return SR_OK;
+}
+
+size_t sr_mesh_workspace_bytes(const int32_t* dims) {
+    if (!dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return 0;
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane >= (1ull << 31) || plane * (unsigned long long)dims[2] >= (1ull << 31)) return 0;
+    return mesh_workspace_bytes((uint32_t)(plane * (unsigned long long)dims[2]));
+}
+
+int sr_mesh_count(const float* volume, const int32_t* dims, float level, void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    MeshGrid g; bool cells;
+    if (int rc = mesh_arguments(volume, dims, level, workspace, workspace_bytes, &g, &cells)) return rc;
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!cells) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s)); return SR_OK; }
+    SR_HIP(mesh_count(volume, g, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_mesh_emit(const float* volume, const int32_t* dims, float level, const float* lo, const float* step, const SrTsdfSpace* space,
+                 void* workspace, size_t workspace_bytes, int32_t n_vertices, int32_t n_faces, float* vertices, int32_t* faces, void* stream) {
+    MeshGrid g; bool cells;
+    if (int rc = mesh_arguments(volume, dims, level, workspace, workspace_bytes, &g, &cells)) return rc;
+    if (!lo || !step) return fail(SR_ERR_INVALID_ARGUMENT, "lo / step is NULL");
+    if (n_vertices < 0 || n_faces < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n_vertices %d / n_faces %d is negative", n_vertices, n_faces);
+    if (n_faces > 0x7FFFFFFF / 3) return fail(SR_ERR_UNSUPPORTED, "%d faces: 3 n_faces does not fit in int32", n_faces);
+    if (n_faces > 0 && n_vertices == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices", n_faces);
+    if (n_vertices > 0 && !vertices) return fail(SR_ERR_INVALID_ARGUMENT, "vertices is NULL");
+    if (n_faces > 0 && !faces) return fail(SR_ERR_INVALID_ARGUMENT, "faces is NULL");
+    if (((uintptr_t)vertices | (uintptr_t)faces) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "vertices / faces is not 4-B aligned");
+    if (!cells || n_vertices == 0) return SR_OK;
+    const MeshFrame frame{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}};
+    TsdfSpace sp{0.f, 0, {0.f, 0.f, 0.f}, 1.f};
+    if (space && space->contract) sp = TsdfSpace{0.f, 1, {space->center[0], space->center[1], space->center[2]}, space->radius};
+    SR_HIP(mesh_emit(volume, g, frame, sp, workspace, (uint32_t)n_vertices, (uint32_t)n_faces, vertices, faces, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, void* stream) {
     if (n > 0 && (!digits || !ranks)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bins < 1 || bins > 1024 || (n % 256u) != 0u) return fail(SR_ERR_INVALID_ARGUMENT, "bins %d not in 1..1024 or n %u not a multiple of 256", bins, n);

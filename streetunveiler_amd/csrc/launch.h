@@ -1,8 +1,8 @@
 // launch.h -- everything that crosses translation units on the host side: the launchers, their scratch sizes and the host-only types
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
-// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, SkyWeights, DensifyRule and the three Tsdf
-// structs, which their kernels take by value.
+// Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, SkyWeights, DensifyRule, the three Tsdf
+// structs and the two Mesh structs, which their kernels take by value.
 #pragma once
 #include "common.h"
 
@@ -254,5 +254,21 @@ struct TsdfGrid {          // sample (ix, iy, iz) = fmaf(index, step, lo) per ax
 // grid == nullptr: the n samples are read from `samples` [n,3]; rgb (with channels 4) and weight may be nullptr
 hipError_t launch_tsdf_fuse(const TsdfViewsDev& views, const TsdfSpace& space, const TsdfGrid* grid, int n, const float* samples, float* tsdf,
                             float* rgb, float* weight, hipStream_t s);
+
+// ---- mesh.hip ------------------------------------------------------------------------------------------------------------------------
+struct MeshGrid {          // kernel parameters, by value
+    int nx, ny, nz;        // every axis at least 2 (a grid without cells never reaches a launch)
+    uint32_t n;            // nx ny nz < 2^31
+    float level;
+};
+struct MeshFrame {         // grid point (ix, iy, iz) sits at fmaf(index, step, lo) per axis
+    float lo[3], step[3];
+};
+size_t mesh_workspace_bytes(uint32_t n);
+// counts: device {Nv, Nf}; a count is 0xFFFFFFFF where Nv or 3 Nf is beyond int32
+hipError_t mesh_count(const float* volume, const MeshGrid& g, void* workspace, uint32_t* counts, hipStream_t s);
+// after mesh_count on the same volume, level and workspace; space.contract: the vertices are un-contracted and un-normalised
+hipError_t mesh_emit(const float* volume, const MeshGrid& g, const MeshFrame& frame, const TsdfSpace& space, void* workspace, uint32_t n_vertices,
+                     uint32_t n_faces, float* vertices, int32_t* faces, hipStream_t s);
 
 }  // namespace sr

@@ -9,6 +9,7 @@
 // grid coordinate), so all four instantiations evaluate one and the same expression per sample; every division is the IEEE one.
 #include <cmath>
 
+#include "contraction.h"
 #include "launch.h"
 
 namespace sr {
@@ -19,12 +20,7 @@ constexpr int kTsdfThreads = 256;
 // and the truncation of the sample.  The "> 1" test is taken on the norm of the WORLD point, as the reference's line 201 does after
 // line 200 has overwritten `samples`.
 __device__ __forceinline__ float adaptive_trunc(float& x, float& y, float& z, const TsdfSpace& sp) {
-    const float mag = __fsqrt_rn(x * x + y * y + z * z);
-    if (!(mag < 1.f)) {
-        const float k = __fdiv_rn(1.f, 2.f - mag);
-        x = k * __fdiv_rn(x, mag); y = k * __fdiv_rn(y, mag); z = k * __fdiv_rn(z, mag);
-    }
-    x = x * sp.radius + sp.center[0]; y = y * sp.radius + sp.center[1]; z = z * sp.radius + sp.center[2];
+    uncontract_to_world(x, y, z, sp);   // contraction.h
     const float norm = __fsqrt_rn(x * x + y * y + z * z);
     float trunc = sp.trunc;
     if (norm > 1.f) trunc *= __fdiv_rn(1.f, 2.f - fminf(norm, 1.9f));

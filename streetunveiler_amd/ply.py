@@ -5,6 +5,9 @@ binary little-endian, float32 properties x y z nx ny nz f_dc_0..2 f_rest_0..44 o
 int32 `semantics`.  f_dc / f_rest are stored CHANNEL-major (the [P,K,3] feature tensors transposed to [P,3,K] and
 flattened), all values are the raw (pre-activation) parameters.  The reader takes the properties by name, so files
 with a different property order or extra properties load too; ASCII PLY is accepted as well.
+
+`write_mesh_ply` / `read_mesh_ply`: the triangle mesh of streetunveiler_amd.mesh.extract_mesh_unbounded, binary little-endian -- a
+`vertex` element (float x y z, uchar red green blue) and a `face` element (`list uchar int vertex_indices`, three int32 per face).
 """
 from __future__ import annotations
 
@@ -106,3 +109,61 @@ def load_ply(path, max_sh_degree: int = 3):
         "semantics": np.asarray(col["semantics"], np.int32) if "semantics" in col else np.zeros(P, np.int32),
     }
     return out
+
+
+def mesh_colors_u8(colors):
+    """Vertex colours in [0, 1] -> the uchar values `write_mesh_ply` stores: round(255 c), clipped; a NaN is 0."""
+    c = np.nan_to_num(np.asarray(colors, dtype=np.float64), nan=0.0)
+    return np.clip(np.rint(c * 255.0), 0, 255).astype(np.uint8)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def write_mesh_ply(path, mesh) -> None:
+    """`mesh`: (vertices [Nv,3] float, faces [Nf,3] integer, colors [Nv,3] in [0, 1] or None) -- a SurfelMesh, tensors or arrays."""
+    vertices, faces, colors = mesh
+    vertices, faces = np.asarray(_host(vertices), dtype=np.float32).reshape(-1, 3), np.asarray(_host(faces), dtype=np.int32).reshape(-1, 3)
+    rgb = mesh_colors_u8(_host(colors)).reshape(-1, 3) if colors is not None else np.full((vertices.shape[0], 3), 255, dtype=np.uint8)
+    if rgb.shape[0] != vertices.shape[0]:
+        raise ValueError(f"{rgb.shape[0]} colours for {vertices.shape[0]} vertices")
+    rows = np.empty(vertices.shape[0], dtype=np.dtype([("xyz", "<f4", (3,)), ("rgb", "u1", (3,))]))
+    rows["xyz"], rows["rgb"] = vertices, rgb
+    tris = np.empty(faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    tris["n"], tris["v"] = 3, faces
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {vertices.shape[0]}", "property float x", "property float y",
+              "property float z", "property uchar red", "property uchar green", "property uchar blue", f"element face {faces.shape[0]}",
+              "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rows.tobytes())
+        fh.write(tris.tobytes())
+
+
+def read_mesh_ply(path):
+    """-> (vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] uint8) of a file `write_mesh_ply` wrote."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        header = []
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError(f"{path}: unterminated PLY header")
+            header.append(" ".join(line.decode("ascii", "replace").split()))
+            if header[-1] == "end_header":
+                break
+        counts = {tok[1]: int(tok[2]) for tok in (h.split() for h in header) if tok and tok[0] == "element"}
+        properties = [h for h in header if h.startswith("property")]
+        if header[0] != "format binary_little_endian 1.0" or list(counts) != ["vertex", "face"] or properties != [
+                "property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+                "property uchar blue", "property list uchar int vertex_indices"]:
+            raise ValueError(f"{path}: not the layout write_mesh_ply writes")
+        vertex = np.dtype([("xyz", "<f4", (3,)), ("rgb", "u1", (3,))])
+        face = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+        rows = np.frombuffer(fh.read(vertex.itemsize * counts["vertex"]), dtype=vertex, count=counts["vertex"])
+        tris = np.frombuffer(fh.read(face.itemsize * counts["face"]), dtype=face, count=counts["face"])
+        if fh.read(1) or (len(tris) and not (tris["n"] == 3).all()):
+            raise ValueError(f"{path}: trailing bytes or a face that is no triangle")
+    return rows["xyz"].copy(), tris["v"].copy(), rows["rgb"].copy()

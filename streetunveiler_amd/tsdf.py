@@ -14,8 +14,8 @@ with the un-normalised WORLD points (line 200) before it tests `norm(samples) > 
 is defined on.  The running averages start from tsdf = 1 with weight = 1 (a phantom observation of +1) and rgb = 0, and the normal map
 the reference samples per view is never used.
 
-Out of scope: the bounded path (`extract_mesh_bounded` is open3d's ScalableTSDFVolume) and marching cubes itself (the reference imports
-it from a `utils.mcube_utils` its tree does not hold).  There is no CPU path for the HIP entry points."""
+Out of scope: the bounded path (`extract_mesh_bounded` is open3d's ScalableTSDFVolume).  Marching cubes on the grid this module fuses
+is streetunveiler_amd.mesh.  There is no CPU path for the HIP entry points."""
 from __future__ import annotations
 
 import ctypes as C
