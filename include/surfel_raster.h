@@ -694,6 +694,48 @@ int sr_mesh_count(const float* volume, const int32_t* dims, float level, void* w
 int sr_mesh_emit(const float* volume, const int32_t* dims, float level, const float* lo, const float* step, const SrTsdfSpace* space,
                  void* workspace, size_t workspace_bytes, int32_t n_vertices, int32_t n_faces, float* vertices, int32_t* faces, void* stream);
 
+/* Mesh post-processing (csrc/mesh_post.hip): what the reference's post_process_mesh does with every mesh it writes
+ * (utils/mesh_utils.py:23-44, through open3d: cluster_connected_triangles, remove_triangles_by_mask, remove_unreferenced_vertices,
+ * remove_degenerate_triangles) on an indexed mesh resident on the GPU: faces [nf,3] int32 over nv vertices [nv,3] float32, with optional
+ * colours [nv,3] float32.  All pointers are device pointers; workspace: sr_mesh_post_workspace_bytes(nv, nf) bytes, 16-B aligned (28 bytes a
+ * face + 4 a vertex; 0 for counts no call accepts).
+ *   Edges and components.  An edge of face (a, b, c) is the unordered index pair of (a, b), (b, c) or (c, a) -- a pair of equal indices is
+ *     an edge like any other.  Two faces are adjacent when they have an equal edge: in either winding, for any number of faces on one edge
+ *     and for duplicate faces; sharing only a vertex joins nothing.  A component is named by its smallest face index: labels[f];
+ *     sizes[r] = the face count of the component at its root r, 0 at every other face.  The dense cluster id of a component is the rank
+ *     of its root among the roots -- the order in which a sweep over the faces from 0 upwards meets the components.  That should also be
+ *     open3d's numbering; this has not been verified against open3d.
+ *   Threshold (the caller's: a device word, so that no host synchronisation is needed for it).  With n = the k-th largest value of sizes
+ *     over all nf entries, zeros included, k = min(cluster_to_keep, nf): threshold = max(n, min_triangles), min_triangles = 50 in the
+ *     reference.  A face goes when its component's size is < threshold, strictly, so ties at the k-th place all stay.  With fewer
+ *     components than cluster_to_keep, n is 0 and the floor decides: every component of at least min_triangles faces stays (the
+ *     reference's np.sort(...)[-cluster_to_keep] raises IndexError there: a deliberate difference).
+ *   Order of the removals, as open3d runs them: (1) the faces of the small components; (2) the vertices no remaining face references,
+ *     their colours with them; (3) the faces with two equal indices.  A vertex that only a degenerate face of a kept component references
+ *     therefore stays.  Surviving vertices and faces keep their relative order; vertex and colour rows are copied word for word; the only
+ *     atomics are integer additions and the union-find's compare-and-swap under the smaller root: equal inputs give equal bits.
+ *   A face with an index outside [0, nv) is never used to address memory: it is counted, is a component of its own and is never kept.
+ *   cluster_area, open3d's third result, is not computed (the reference does not read it).
+ * sr_mesh_components: labels [nf], sizes [nf], n_out_of_range [1].  sr_mesh_filter_count: from labels and sizes (in [0, nf) or the face is
+ * not kept) and *threshold, counts[3] = {nv_out, nf_out, n_out_of_range} in DEVICE memory -- the one read-back, which is the caller's;
+ * sr_mesh_filter_emit, with the same faces, nv, nf and workspace and the two counts read: vertices_out [nv_out,3], colors_out [nv_out,3]
+ * where colors is not NULL, faces_out [nf_out,3] renumbered.
+ * Cost: a half-edge walks the bucket of its lower vertex, so a vertex of valence d costs about 2 d^2 reads: small on a marching-cubes
+ * mesh (d about 6), slow and still right at a hub vertex.
+ * nf == 0 or nv == 0 is no error and no work: counts = {0, 0, 0}, nothing is emitted (sr_mesh_components writes nothing for nf == 0 and
+ * refuses nf > 0 with nv == 0, where no face has a label to give).  All three check every argument before their first HIP call
+ * (SR_ERR_INVALID_ARGUMENT: a negative count, a NULL or misaligned pointer, nv_out > nv, nf_out > nf, faces without vertices;
+ * SR_ERR_BUFFER_TOO_SMALL: a short workspace; SR_ERR_UNSUPPORTED: 3 nf beyond int32), run on the caller's stream and allocate nothing.
+ * Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_mesh_post_workspace_bytes(int32_t nv, int32_t nf);
+int sr_mesh_components(const int32_t* faces, int32_t nv, int32_t nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int sr_mesh_filter_count(const int32_t* faces, int32_t nv, int32_t nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold,
+                         void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream);
+int sr_mesh_filter_emit(const int32_t* faces, int32_t nv, int32_t nf, const float* vertices, const float* colors, void* workspace,
+                        size_t workspace_bytes, int32_t nv_out, int32_t nf_out, float* vertices_out, float* colors_out, int32_t* faces_out,
+                        void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

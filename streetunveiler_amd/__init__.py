@@ -17,7 +17,8 @@ _AUX_LOSS = ("semantic_cross_entropy", "surface_regularisers", "opacity_shrink",
 _SKY = ("SkyModel", "sky_rays_mlp", "sky_forward_torch", "position_features")
 _MESH = ("marching_cubes", "marching_cubes_numpy", "extract_mesh_unbounded", "contracted_bound", "SurfelMesh")
 _MESH_PLY = ("write_mesh_ply", "read_mesh_ply")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY)
+_MESH_POST = ("connected_triangles", "post_process_mesh", "connected_triangles_numpy", "post_process_mesh_numpy")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -51,4 +52,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _MESH_PLY:
         from . import ply
         return getattr(ply, name)
+    if name in _MESH_POST:
+        from . import mesh_post
+        return getattr(mesh_post, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

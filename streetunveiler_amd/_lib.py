@@ -169,7 +169,11 @@ PROTOTYPES = {
     "sr_mesh_workspace_bytes": (_sz, [_P(_i32)]),
     "sr_mesh_count": (_int, [_vp, _P(_i32), _f32] + _WS + [_vp, _vp]),
     "sr_mesh_emit": (_int, [_vp, _P(_i32), _f32, _P(_f32), _P(_f32), _P(SrTsdfSpace)] + _WS + [_i32, _i32, _vp, _vp, _vp]),
-    "sr_debug_pair_decisions": (_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
+    "sr_mesh_post_workspace_bytes": (_sz, [_i32, _i32]),
+    "sr_mesh_components": (_int, [_vp, _i32, _i32, _vp, _vp, _vp] + _WS + [_vp]),
+    "sr_mesh_filter_count": (_int, [_vp, _i32, _i32, _vp, _vp, _vp] + _WS + [_vp, _vp]),
+    "sr_mesh_filter_emit": (_int, [_vp, _i32, _i32, _vp, _vp] + _WS + [_i32, _i32, _vp, _vp, _vp, _vp]),
+    "sr_debug_pair_decisions":(_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
     "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
     "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),
     "sr_rank_mode": (_int, [_vp]),

@@ -43,6 +43,7 @@ SOURCES = [
     ("densify.hip", ["-ffp-contract=off"]),     # the order of the child position and the child scale is what the tests hold
     ("tsdf.hip", ["-ffp-contract=off"]),        # the fmaf()s written out in it are the only fused operations: one expression in every instantiation
     ("mesh.hip", ["-ffp-contract=off"]),        # as tsdf.hip: the coordinates' fmaf()s are the only fused operations, t is one IEEE division
+    ("mesh_post.hip", []),                      # integers only
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -1425,6 +1425,72 @@ int sr_mesh_emit(const float* volume, const int32_t* dims, float level, const fl
     return SR_OK;
 }
 
+// the checks the three sr_mesh_* post-processing calls share; *work = 0 for a mesh without faces or without vertices
+static int mesh_post_arguments(const int32_t* faces, int32_t nv, int32_t nf, const void* workspace, size_t workspace_bytes, bool* work) {
+    if (nv < 0 || nf < 0) return fail(SR_ERR_INVALID_ARGUMENT, "nv %d / nf %d is negative", nv, nf);
+    if (nf > 0x7FFFFFFF / 3) return fail(SR_ERR_UNSUPPORTED, "%d faces: 3 nf does not fit in int32 (process the mesh in parts)", nf);
+    *work = nv > 0 && nf > 0;
+    if (!*work) return SR_OK;
+    if (!faces) return fail(SR_ERR_INVALID_ARGUMENT, "faces is NULL");
+    if ((uintptr_t)faces & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "faces is not 4-B aligned");
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < mesh_post_workspace_bytes(nv, nf))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, mesh_post_workspace_bytes(nv, nf));
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    return SR_OK;
+}
+
+size_t sr_mesh_post_workspace_bytes(int32_t nv, int32_t nf) {
+    if (nv < 0 || nf < 0 || nf > 0x7FFFFFFF / 3) return 0;
+    return mesh_post_workspace_bytes(nv, nf);
+}
+
+int sr_mesh_components(const int32_t* faces, int32_t nv, int32_t nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (!n_out_of_range) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is NULL");
+    if (nf > 0 && nv > 0 && (!labels || !sizes)) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes is NULL");
+    if (((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)n_out_of_range) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes / n_out_of_range is not 4-B aligned");
+    if (nf == 0) return SR_OK;      // no face: nothing to label, nothing out of range, no work
+    if (nv == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices: every index is out of range", nf);
+    SR_HIP(mesh_components(faces, nv, nf, labels, sizes, n_out_of_range, workspace, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_mesh_filter_count(const int32_t* faces, int32_t nv, int32_t nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold,
+                         void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) { SR_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s)); return SR_OK; }
+    if (!labels || !sizes) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes is NULL");
+    if (!threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NULL");
+    if (((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)threshold) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes / threshold is not 4-B aligned");
+    SR_HIP(mesh_filter_count(faces, nv, nf, labels, sizes, threshold, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_mesh_filter_emit(const int32_t* faces, int32_t nv, int32_t nf, const float* vertices, const float* colors, void* workspace,
+                        size_t workspace_bytes, int32_t nv_out, int32_t nf_out, float* vertices_out, float* colors_out, int32_t* faces_out, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (nv_out < 0 || nf_out < 0) return fail(SR_ERR_INVALID_ARGUMENT, "nv_out %d / nf_out %d is negative", nv_out, nf_out);
+    if (nv_out > nv || nf_out > nf) return fail(SR_ERR_INVALID_ARGUMENT, "nv_out %d / nf_out %d: more than the %d vertices / %d faces that came in", nv_out, nf_out, nv, nf);
+    if (nf_out > 0 && nv_out == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices", nf_out);
+    if (nv_out > 0 && (!vertices || !vertices_out)) return fail(SR_ERR_INVALID_ARGUMENT, "vertices / vertices_out is NULL");
+    if (nv_out > 0 && colors && !colors_out) return fail(SR_ERR_INVALID_ARGUMENT, "colors_out is NULL (colors is given)");
+    if (nf_out > 0 && !faces_out) return fail(SR_ERR_INVALID_ARGUMENT, "faces_out is NULL");
+    if (((uintptr_t)vertices | (uintptr_t)colors | (uintptr_t)vertices_out | (uintptr_t)colors_out | (uintptr_t)faces_out) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "vertices / colors / vertices_out / colors_out / faces_out is not 4-B aligned");
+    if (!work || nv_out == 0) return SR_OK;
+    SR_HIP(mesh_filter_emit(faces, nv, nf, vertices, colors, workspace, (uint32_t)nv_out, (uint32_t)nf_out, vertices_out, colors_out, faces_out,
+                            static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, void* stream) {
     if (n > 0 && (!digits || !ranks)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bins < 1 || bins > 1024 || (n % 256u) != 0u) return fail(SR_ERR_INVALID_ARGUMENT, "bins %d not in 1..1024 or n %u not a multiple of 256", bins, n);

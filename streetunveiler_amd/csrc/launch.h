@@ -271,4 +271,15 @@ hipError_t mesh_count(const float* volume, const MeshGrid& g, void* workspace, u
 hipError_t mesh_emit(const float* volume, const MeshGrid& g, const MeshFrame& frame, const TsdfSpace& space, void* workspace, uint32_t n_vertices,
                      uint32_t n_faces, float* vertices, int32_t* faces, hipStream_t s);
 
+// ---- mesh_post.hip -------------------------------------------------------------------------------------------------------------------
+size_t mesh_post_workspace_bytes(int nv, int nf);
+// nv, nf >= 1 and 3 nf <= INT32_MAX in all three.  labels, sizes: device [nf]; n_out_of_range: device [1]
+hipError_t mesh_components(const int32_t* faces, int nv, int nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* ws, hipStream_t s);
+// threshold: device [1]; counts: device {nv_out, nf_out, n_out_of_range}
+hipError_t mesh_filter_count(const int32_t* faces, int nv, int nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold, void* ws,
+                             uint32_t* counts, hipStream_t s);
+// after mesh_filter_count on the same faces and workspace, with the counts it left; nv_out >= 1; colors / colors_out may be nullptr
+hipError_t mesh_filter_emit(const int32_t* faces, int nv, int nf, const float* vertices, const float* colors, void* ws, uint32_t nv_out, uint32_t nf_out,
+                            float* vertices_out, float* colors_out, int32_t* faces_out, hipStream_t s);
+
 }  // namespace sr
