@@ -736,6 +736,62 @@ int sr_mesh_filter_emit(const int32_t* faces, int32_t nv, int32_t nf, const floa
                         size_t workspace_bytes, int32_t nv_out, int32_t nf_out, float* vertices_out, float* colors_out, int32_t* faces_out,
                         void* stream);
 
+/* The frame masks of the unveiling stage (csrc/unveil.hip): what connects the instance selection, the masked model and its losses in the
+ * reference's inpainting_pipeline/ -- the point-in-frame tests of scene/__init__.py:217-312 and the pixel masks and condition images of
+ * inpainting_pipeline/utils.py:17-30, 2_condition_preparation/2_generate_inpainted_mask.py:111-159 and
+ * 3_reoptimization/1_optimization.py:115-187.  All pointers are device pointers; nothing is read back, nothing allocated.
+ *   Cameras.  cams [F,24] float32, a row = {w2c rows 0..2 (12 values, row-major [R | t]), K (9, row-major), max_z (+inf: none),
+ *     reso_scale (0: none), one unused}; hw [F,2] int32 = (h, w).  sr_points_in_frame* read one row (F = 1).
+ *   The predicate, in float32, strict: cam = R x + t; p = K cam; pix = p.xy / p.z (IEEE division); a point is in the frame iff
+ *     pix.x < w, pix.x > 0, pix.y < h, pix.y > 0, cam.z > 0 and cam.z < max_z.  A NaN decides nothing true; a point with a NaN or infinite
+ *     coordinate is in no frame.  Pixel coordinates: trunc(pix), then trunc(trunc(pix) / reso_scale) in float32 true division where a
+ *     scale is given; int64.  depth = cam.z.
+ *   sr_points_in_frame: mask [P] bytes (0 / 1).  With count != NULL it also scans the flags into the workspace and leaves the number of
+ *     admitted points in count[0] (DEVICE memory: the one read-back is the caller's); sr_points_in_frame_emit, with the same points,
+ *     camera and workspace and that number n, writes pix [n,2] int64 = (x, y) and depth [n] in ascending point index.
+ *   sr_frame_visibility: count [F] int64 and depth_sum [F] float64 (the float32 depths of the admitted points, added as doubles) over
+ *     points x frames in one launch plus one fold of per-block partials; every addition's order depends on P alone.
+ *   sr_semantic_mask_of_points: maps [F,Hm,Wm] uint8 labels; mask[i] = 1 iff in some frame that admits point i,
+ *     (1 << label) & remain_bit != 0 at maps[f, pix.y, pix.x].  One thread per point walks the frames in order and stops once its point
+ *     is set.  A label of 31 or more matches nothing (the reference shifts an int32 by it); bit 31 of remain_bit is ignored.  A pixel
+ *     index outside [0,Hm) x [0,Wm) -- reso_scale and the map size disagree -- is not read, matches nothing and is counted in
+ *     n_out_of_range[0] (uint64, device) for every frame the thread tested before it stopped (the reference would raise).
+ *   The dilation.  out(y, x) = OR of the predicate at (y + dy, x + dx), dy and dx in [-(k / 2), k - 1 - k / 2], pixels outside the image
+ *     contributing nothing: cv2.dilate with a k x k kernel of ones, the default anchor (k / 2, k / 2) and the default border as OpenCV
+ *     documents them (not verified against cv2, which is not a dependency).  1 <= k <= 31.  Outputs are bytes (0 / 1) [H,W].
+ *     sr_dilate_mask: the predicate is mask[y, x] != 0.  sr_instance_pixel_mask: |alpha_a - alpha_b| > threshold ([H,W] float32 each; a
+ *     NaN difference is not set).  sr_refill_mask: not (sum over the C channels of |render_a - render_b| < eps) and mask != 0
+ *     ([C,H,W] float32, the channels added in order; a NaN sum is set).  The undilated mask exists only as bits in the LDS.
+ *   sr_inpaint_conditions: the images are [3,H,W] (renders, normal, sky) or [H,W] (alphas, depth) float32; with
+ *     q(x) = trunc(clamp(255 x + 0.5, 0, 255)) in float32, a product then a sum (torchvision's save_image; a NaN gives 0):
+ *     original_rgb = q(full_render + sky (1 - full_alpha)), inpainted_rgb = q(background_render + sky (1 - full_alpha)) -- the FULL alpha,
+ *     as the reference --, empty_opacity = q(full_alpha - background_alpha), inpainted_depth = q(clamp(d, 0, 1)) with
+ *     d = 1 / background_depth and an infinite d set to 0, inpainted_normal = q(clamp(0.5 n + 0.5, 0, 1)); uint8 in [H,W,C] layout; mask =
+ *     sr_instance_pixel_mask(full_alpha, background_alpha, threshold, k).  Two launches.
+ * P == 0 or F == 0 is no error: count and depth_sum are zeroed, nothing else is written.  Every call checks its arguments before its first
+ * HIP call (SR_ERR_INVALID_ARGUMENT: a negative count, a NULL or misaligned pointer, H or W < 1, k outside 1..31, a NaN threshold;
+ * SR_ERR_BUFFER_TOO_SMALL: a short workspace -- sr_unveil_workspace_bytes(P, F) bytes, 16-B aligned: 4 bytes a point + 16 per (frame, 2048
+ * points); SR_ERR_UNSUPPORTED: H W beyond int32, H > 2 097 120 rows, W > 2^31 - 129 columns, C outside 1..16) and runs on the caller's stream.  Integer atomics only: equal inputs
+ * give equal bits.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_unveil_workspace_bytes(int32_t P, int32_t F);
+int sr_points_in_frame(int32_t P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* workspace,
+                       size_t workspace_bytes, uint32_t* count, void* stream);
+int sr_points_in_frame_emit(int32_t P, const float* xyz, const float* cam, const int32_t* hw, void* workspace, size_t workspace_bytes,
+                            int32_t n, int64_t* pix, float* depth, void* stream);
+int sr_frame_visibility(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, void* workspace,
+                        size_t workspace_bytes, int64_t* count, double* depth_sum, void* stream);
+int sr_semantic_mask_of_points(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, const uint8_t* maps,
+                               int32_t Hm, int32_t Wm, uint32_t remain_bit, uint8_t* mask, uint64_t* n_out_of_range, void* stream);
+int sr_dilate_mask(int32_t H, int32_t W, int32_t k, const uint8_t* mask, uint8_t* out, void* stream);
+int sr_instance_pixel_mask(int32_t H, int32_t W, const float* alpha_a, const float* alpha_b, float threshold, int32_t k, uint8_t* out,
+                           void* stream);
+int sr_refill_mask(int32_t H, int32_t W, int32_t C, const float* render_a, const float* render_b, const uint8_t* mask, float eps,
+                   int32_t k, uint8_t* out, void* stream);
+int sr_inpaint_conditions(int32_t H, int32_t W, const float* full_render, const float* full_alpha, const float* background_render,
+                          const float* background_alpha, const float* background_depth, const float* background_normal, const float* sky,
+                          float threshold, int32_t k, uint8_t* mask, uint8_t* original_rgb, uint8_t* inpainted_rgb, uint8_t* empty_opacity,
+                          uint8_t* inpainted_depth, uint8_t* inpainted_normal, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

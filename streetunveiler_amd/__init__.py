@@ -18,7 +18,11 @@ _SKY = ("SkyModel", "sky_rays_mlp", "sky_forward_torch", "position_features")
 _MESH = ("marching_cubes", "marching_cubes_numpy", "extract_mesh_unbounded", "contracted_bound", "SurfelMesh")
 _MESH_PLY = ("write_mesh_ply", "read_mesh_ply")
 _MESH_POST = ("connected_triangles", "post_process_mesh", "connected_triangles_numpy", "post_process_mesh_numpy")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST)
+_UNVEIL = ("FrameCamera", "FrameCameras", "pack_cameras", "points_in_frame", "frame_visibility", "pick_view", "semantic_mask_of_points",
+           "dilate_mask", "instance_pixel_mask", "refill_mask", "inpaint_conditions", "points_in_frame_torch", "frame_visibility_torch",
+           "pick_view_torch", "semantic_mask_of_points_torch", "dilate_mask_numpy", "dilate_mask_torch", "instance_pixel_mask_torch",
+           "refill_mask_torch", "inpaint_conditions_torch")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -55,4 +59,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _MESH_POST:
         from . import mesh_post
         return getattr(mesh_post, name)
+    if name in _UNVEIL:
+        from . import unveil
+        return getattr(unveil, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -173,6 +173,15 @@ PROTOTYPES = {
     "sr_mesh_components": (_int, [_vp, _i32, _i32, _vp, _vp, _vp] + _WS + [_vp]),
     "sr_mesh_filter_count": (_int, [_vp, _i32, _i32, _vp, _vp, _vp] + _WS + [_vp, _vp]),
     "sr_mesh_filter_emit": (_int, [_vp, _i32, _i32, _vp, _vp] + _WS + [_i32, _i32, _vp, _vp, _vp, _vp]),
+    "sr_unveil_workspace_bytes": (_sz, [_i32, _i32]),
+    "sr_points_in_frame": (_int, [_i32] + [_vp] * 4 + _WS + [_vp, _vp]),
+    "sr_points_in_frame_emit": (_int, [_i32] + [_vp] * 3 + _WS + [_i32, _vp, _vp, _vp]),
+    "sr_frame_visibility": (_int, [_i32, _i32] + [_vp] * 3 + _WS + [_vp] * 3),
+    "sr_semantic_mask_of_points": (_int, [_i32, _i32] + [_vp] * 4 + [_i32, _i32, _u32] + [_vp] * 3),
+    "sr_dilate_mask": (_int, [_i32] * 3 + [_vp] * 3),
+    "sr_instance_pixel_mask": (_int, [_i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp]),
+    "sr_refill_mask": (_int, [_i32] * 3 + [_vp] * 3 + [_f32, _i32, _vp, _vp]),
+    "sr_inpaint_conditions": (_int, [_i32, _i32] + [_vp] * 7 + [_f32, _i32] + [_vp] * 7),
     "sr_debug_pair_decisions":(_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
     "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
     "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),

@@ -44,6 +44,7 @@ SOURCES = [
     ("tsdf.hip", ["-ffp-contract=off"]),        # the fmaf()s written out in it are the only fused operations: one expression in every instantiation
     ("mesh.hip", ["-ffp-contract=off"]),        # as tsdf.hip: the coordinates' fmaf()s are the only fused operations, t is one IEEE division
     ("mesh_post.hip", []),                      # integers only
+    ("unveil.hip", ["-ffp-contract=off"]),      # 255 x + 0.5 and the composites are a product THEN a sum, as the stock-torch lines they restate
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -1491,6 +1491,154 @@ int sr_mesh_filter_emit(const int32_t* faces, int32_t nv, int32_t nf, const floa
     return SR_OK;
 }
 
+// the checks the per-point sr_* calls of unveil.hip share; *work = 0 where there is no point or no frame
+static int unveil_point_arguments(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, bool* work) {
+    if (P < 0 || F < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P %d / F %d is negative", P, F);
+    *work = P > 0 && F > 0;
+    if (!*work) return SR_OK;
+    if (!xyz || !cams || !hw) return fail(SR_ERR_INVALID_ARGUMENT, "xyz / cams / hw is NULL");
+    if (((uintptr_t)xyz | (uintptr_t)cams | (uintptr_t)hw) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "xyz / cams / hw is not 4-B aligned");
+    return SR_OK;
+}
+
+static int unveil_workspace(int32_t P, int32_t F, const void* workspace, size_t workspace_bytes) {
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < unveil_workspace_bytes(P, F)) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, unveil_workspace_bytes(P, F));
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    return SR_OK;
+}
+
+// the checks the per-pixel sr_* calls of unveil.hip share
+static int unveil_image_arguments(int32_t H, int32_t W, int32_t k) {
+    if (H < 1 || W < 1) return fail(SR_ERR_INVALID_ARGUMENT, "an image of %d x %d: H and W must be at least 1", H, W);
+    if ((long long)H * W > 0x7FFFFFFFll) return fail(SR_ERR_UNSUPPORTED, "an image of %d x %d: H W must fit in int32", H, W);
+    // a tile is 64 x kDilateRows pixels: the tile rows are the launch's grid.y, and a tile's halo reaches 64 columns past its own
+    if (H > kDilateRows * 65535) return fail(SR_ERR_UNSUPPORTED, "an image of %d rows: at most %d", H, kDilateRows * 65535);
+    if (W > 0x7FFFFFFF - 128) return fail(SR_ERR_UNSUPPORTED, "an image of %d columns: at most %d", W, 0x7FFFFFFF - 128);
+    if (k < 1 || k > 31) return fail(SR_ERR_INVALID_ARGUMENT, "k = %d not in 1..31", k);
+    return SR_OK;
+}
+
+size_t sr_unveil_workspace_bytes(int32_t P, int32_t F) {
+    if (P < 0 || F < 0) return 0;
+    return unveil_workspace_bytes(P, F);
+}
+
+int sr_points_in_frame(int32_t P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                       uint32_t* count, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, 1, xyz, cam, hw, &work)) return rc;
+    if ((uintptr_t)count & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "count is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {
+        if (count) SR_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
+        return SR_OK;
+    }
+    if (!mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (count) if (int rc = unveil_workspace(P, 1, workspace, workspace_bytes)) return rc;
+    SR_HIP(points_in_frame(P, xyz, cam, hw, mask, workspace, count, s));
+    return SR_OK;
+}
+
+int sr_points_in_frame_emit(int32_t P, const float* xyz, const float* cam, const int32_t* hw, void* workspace, size_t workspace_bytes, int32_t n,
+                            int64_t* pix, float* depth, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, 1, xyz, cam, hw, &work)) return rc;
+    if (n < 0 || n > P) return fail(SR_ERR_INVALID_ARGUMENT, "n = %d: not in 0..P = %d", n, P);
+    if (n == 0) return SR_OK;
+    if (int rc = unveil_workspace(P, 1, workspace, workspace_bytes)) return rc;
+    if (!pix || !depth) return fail(SR_ERR_INVALID_ARGUMENT, "pix / depth is NULL");
+    if (((uintptr_t)pix & 7u) || ((uintptr_t)depth & 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "pix is not 8-B or depth not 4-B aligned");
+    SR_HIP(points_in_frame_emit(P, xyz, cam, hw, workspace, (uint32_t)n, pix, depth, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_frame_visibility(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, void* workspace, size_t workspace_bytes,
+                        int64_t* count, double* depth_sum, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, F, xyz, cams, hw, &work)) return rc;
+    if (F == 0) return SR_OK;
+    if (!count || !depth_sum) return fail(SR_ERR_INVALID_ARGUMENT, "count / depth_sum is NULL");
+    if (((uintptr_t)count | (uintptr_t)depth_sum) & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "count / depth_sum is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {   // no point: every count and sum is 0 (all bits zero)
+        SR_HIP(hipMemsetAsync(count, 0, sizeof(int64_t) * (size_t)F, s));
+        SR_HIP(hipMemsetAsync(depth_sum, 0, sizeof(double) * (size_t)F, s));
+        return SR_OK;
+    }
+    if (int rc = unveil_workspace(P, F, workspace, workspace_bytes)) return rc;
+    SR_HIP(frame_visibility(P, F, xyz, cams, hw, workspace, count, depth_sum, s));
+    return SR_OK;
+}
+
+int sr_semantic_mask_of_points(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, const uint8_t* maps, int32_t Hm,
+                               int32_t Wm, uint32_t remain_bit, uint8_t* mask, uint64_t* n_out_of_range, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, F, xyz, cams, hw, &work)) return rc;
+    if (Hm < 1 || Wm < 1) return fail(SR_ERR_INVALID_ARGUMENT, "maps of %d x %d: Hm and Wm must be at least 1", Hm, Wm);
+    if (!n_out_of_range) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is NULL");
+    if ((uintptr_t)n_out_of_range & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is not 8-B aligned");
+    if (P > 0 && !mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {   // no frame sets anything
+        SR_HIP(hipMemsetAsync(n_out_of_range, 0, sizeof(uint64_t), s));
+        if (P > 0) SR_HIP(hipMemsetAsync(mask, 0, (size_t)P, s));
+        return SR_OK;
+    }
+    if (!maps) return fail(SR_ERR_INVALID_ARGUMENT, "maps is NULL");
+    const UnveilSemantic a{P, F, Hm, Wm, remain_bit & 0x7FFFFFFFu, xyz, cams, hw, maps};
+    SR_HIP(semantic_mask_of_points(a, mask, n_out_of_range, s));
+    return SR_OK;
+}
+
+int sr_dilate_mask(int32_t H, int32_t W, int32_t k, const uint8_t* mask, uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!mask || !out) return fail(SR_ERR_INVALID_ARGUMENT, "mask / out is NULL");
+    if (mask == out) return fail(SR_ERR_INVALID_ARGUMENT, "out must not be the mask: a tile reads its neighbours' pixels");
+    SR_HIP(dilate_mask(H, W, k, mask, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_instance_pixel_mask(int32_t H, int32_t W, const float* alpha_a, const float* alpha_b, float threshold, int32_t k, uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!alpha_a || !alpha_b || !out) return fail(SR_ERR_INVALID_ARGUMENT, "alpha_a / alpha_b / out is NULL");
+    if (((uintptr_t)alpha_a | (uintptr_t)alpha_b) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "alpha_a / alpha_b is not 4-B aligned");
+    if (threshold != threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NaN");
+    SR_HIP(instance_pixel_mask(H, W, k, alpha_a, alpha_b, threshold, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_refill_mask(int32_t H, int32_t W, int32_t C, const float* render_a, const float* render_b, const uint8_t* mask, float eps, int32_t k,
+                   uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (C < 1 || C > 16) return fail(SR_ERR_UNSUPPORTED, "C = %d channels: 1..16", C);
+    if (!render_a || !render_b || !mask || !out) return fail(SR_ERR_INVALID_ARGUMENT, "render_a / render_b / mask / out is NULL");
+    if (mask == out) return fail(SR_ERR_INVALID_ARGUMENT, "out must not be the mask: a tile reads its neighbours' pixels");
+    if (((uintptr_t)render_a | (uintptr_t)render_b) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "render_a / render_b is not 4-B aligned");
+    if (eps != eps) return fail(SR_ERR_INVALID_ARGUMENT, "eps is NaN");
+    SR_HIP(refill_mask(H, W, C, k, render_a, render_b, mask, eps, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_inpaint_conditions(int32_t H, int32_t W, const float* full_render, const float* full_alpha, const float* background_render,
+                          const float* background_alpha, const float* background_depth, const float* background_normal, const float* sky,
+                          float threshold, int32_t k, uint8_t* mask, uint8_t* original_rgb, uint8_t* inpainted_rgb, uint8_t* empty_opacity,
+                          uint8_t* inpainted_depth, uint8_t* inpainted_normal, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!full_render || !full_alpha || !background_render || !background_alpha || !background_depth || !background_normal || !sky)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an input image is NULL");
+    if (((uintptr_t)full_render | (uintptr_t)full_alpha | (uintptr_t)background_render | (uintptr_t)background_alpha | (uintptr_t)background_depth |
+         (uintptr_t)background_normal | (uintptr_t)sky) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an input image is not 4-B aligned");
+    if (!mask || !original_rgb || !inpainted_rgb || !empty_opacity || !inpainted_depth || !inpainted_normal)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an output is NULL");
+    if (threshold != threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NaN");
+    const UnveilConditions a{H, W, full_render, full_alpha, background_render, background_alpha, background_depth, background_normal, sky,
+                             original_rgb, inpainted_rgb, empty_opacity, inpainted_depth, inpainted_normal};
+    SR_HIP(inpaint_conditions(a, threshold, k, mask, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, void* stream) {
     if (n > 0 && (!digits || !ranks)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bins < 1 || bins > 1024 || (n % 256u) != 0u) return fail(SR_ERR_INVALID_ARGUMENT, "bins %d not in 1..1024 or n %u not a multiple of 256", bins, n);

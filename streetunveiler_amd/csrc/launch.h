@@ -2,7 +2,7 @@
 // they take.  Each is declared here exactly once; api.hip and every file that defines or calls one of them includes this header, so a
 // changed parameter list is a compile error where it is defined, not an unresolved symbol when the library is loaded.
 // Host-only: nothing in here is a kernel parameter except PostCam, LossImages, CeArgs, SurfaceRegArgs, SkyWeights, DensifyRule, the three Tsdf
-// structs and the two Mesh structs, which their kernels take by value.
+// structs, the two Mesh structs and the two Unveil structs, which their kernels take by value.
 #pragma once
 #include "common.h"
 
@@ -281,5 +281,41 @@ hipError_t mesh_filter_count(const int32_t* faces, int nv, int nf, const int32_t
 // after mesh_filter_count on the same faces and workspace, with the counts it left; nv_out >= 1; colors / colors_out may be nullptr
 hipError_t mesh_filter_emit(const int32_t* faces, int nv, int nf, const float* vertices, const float* colors, void* ws, uint32_t nv_out, uint32_t nf_out,
                             float* vertices_out, float* colors_out, int32_t* faces_out, hipStream_t s);
+// The exclusive scan of n >= 1 words in place (n < 2^31, the sum fits in 32 bits), also unveil.hip's compaction: chunks of
+// kScanInPlaceChunk items, `chunks` = scan_in_place_chunk_words(n) words of device scratch; total_out (device, may be nullptr) gets the sum
+constexpr int kScanInPlaceChunk = 4096;
+inline size_t scan_in_place_chunk_words(uint32_t n) { return ((size_t)n + kScanInPlaceChunk - 1) / kScanInPlaceChunk + 1; }
+hipError_t exclusive_scan_in_place(uint32_t* data, uint32_t n, uint32_t* chunks, uint32_t* total_out, hipStream_t s);
+
+// ---- unveil.hip ----------------------------------------------------------------------------------------------------------------------
+constexpr int kUnveilCamFloats = 24;   // a camera row: w2c rows 0..2 (12), K (9), max_z (+inf: none), reso_scale (0: none), one unused
+constexpr int kDilateRows = 32;        // output rows of a dilation tile (64 columns wide); the tile rows are grid.y: H <= 32 * 65535 (api.hip)
+struct UnveilSemantic {    // a kernel parameter, by value: device pointers
+    int P, F, Hm, Wm;
+    uint32_t remain_bit;   // bits 0..30
+    const float* xyz;      // [P,3]
+    const float* cams;     // [F,kUnveilCamFloats]
+    const int32_t* hw;     // [F,2] = (h, w)
+    const uint8_t* maps;   // [F,Hm,Wm] labels
+};
+struct UnveilConditions {  // a kernel parameter, by value: device pointers; the images are [C,H,W] float32, the outputs [H,W,C] uint8
+    int H, W;
+    const float *full_render, *full_alpha, *background_render, *background_alpha, *background_depth, *background_normal, *sky;
+    uint8_t *original_rgb, *inpainted_rgb, *empty_opacity, *inpainted_depth, *inpainted_normal;
+};
+size_t unveil_workspace_bytes(int P, int F);
+// P >= 1 in all four.  count == nullptr: the mask alone; else the admitted points' offsets stay in the workspace and *count (device) = n
+hipError_t points_in_frame(int P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* ws, uint32_t* count, hipStream_t s);
+hipError_t points_in_frame_emit(int P, const float* xyz, const float* cam, const int32_t* hw, const void* ws, uint32_t n, int64_t* pix, float* depth,
+                                hipStream_t s);
+hipError_t frame_visibility(int P, int F, const float* xyz, const float* cams, const int32_t* hw, void* ws, int64_t* count, double* depth_sum,
+                            hipStream_t s);
+hipError_t semantic_mask_of_points(const UnveilSemantic& a, uint8_t* mask, uint64_t* n_out_of_range, hipStream_t s);
+// H, W >= 1, H W < 2^31, H <= kDilateRows * 65535, W <= INT32_MAX - 128, 1 <= k <= 31 in all four; masks and outputs are bytes [H,W]
+hipError_t dilate_mask(int H, int W, int k, const uint8_t* mask, uint8_t* out, hipStream_t s);
+hipError_t instance_pixel_mask(int H, int W, int k, const float* alpha_a, const float* alpha_b, float threshold, uint8_t* out, hipStream_t s);
+hipError_t refill_mask(int H, int W, int C, int k, const float* render_a, const float* render_b, const uint8_t* mask, float eps, uint8_t* out,
+                       hipStream_t s);
+hipError_t inpaint_conditions(const UnveilConditions& a, float threshold, int k, uint8_t* mask_out, hipStream_t s);
 
 }  // namespace sr

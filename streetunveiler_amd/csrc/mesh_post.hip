@@ -42,7 +42,7 @@ static MeshPostLayout mesh_post_layout(int nv, int nf) {
     L.vert = c.take(4 * v);
     L.edge = c.take(8 * 3 * f);
     L.parent = c.take(4 * f);
-    L.chunks = c.take(4 * (((v > f ? v : f) + kPostChunk - 1) / kPostChunk + 1));
+    L.chunks = c.take(4 * scan_in_place_chunk_words((uint32_t)(v > f ? v : f)));
     L.total = c.off;
     return L;
 }
@@ -83,8 +83,10 @@ __global__ __launch_bounds__(kPostThreads) void post_chunk_apply_kernel(uint32_t
     }
 }
 
-// n >= 1; the sum must fit in 32 bits (here: at most 3 nf, nv or nf); total_out (device, may be nullptr) gets it
-static hipError_t exclusive_scan_in_place(uint32_t* data, uint32_t n, uint32_t* chunks, uint32_t* total_out, hipStream_t s) {
+// n >= 1; the sum must fit in 32 bits (here: at most 3 nf, nv or nf); total_out (device, may be nullptr) gets it.  Declared in launch.h:
+// unveil.hip compacts with it too.
+static_assert(kPostChunk == kScanInPlaceChunk, "launch.h sizes the callers' chunk scratch");
+hipError_t exclusive_scan_in_place(uint32_t* data, uint32_t n, uint32_t* chunks, uint32_t* total_out, hipStream_t s) {
     const uint32_t nchunks = (n + kPostChunk - 1) / kPostChunk;
     hipLaunchKernelGGL(post_chunk_sums_kernel, dim3(nchunks), dim3(kPostThreads), 0, s, data, n, chunks);
     hipLaunchKernelGGL(post_chunk_bases_kernel, dim3(1), dim3(kPostScanThreads), 0, s, chunks, (int)nchunks, total_out);
