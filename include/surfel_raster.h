@@ -792,6 +792,39 @@ int sr_inpaint_conditions(int32_t H, int32_t W, const float* full_render, const 
                           float threshold, int32_t k, uint8_t* mask, uint8_t* original_rgb, uint8_t* inpainted_rgb, uint8_t* empty_opacity,
                           uint8_t* inpainted_depth, uint8_t* inpainted_normal, void* stream);
 
+/* LiDAR scene initialisation (csrc/voxel.hip): the semantic voxel downsample of the reference's SemanticPointCloud.voxel_down_sample
+ * [REF utils/pcd_utils.py:73-142] -- one output point per occupied voxel.  All arrays are device arrays except lo (three HOST doubles);
+ * points, colors, normals are [n,3] float32 or float64 (the *_f64 flags: 0 / 1), semantics [n] int32 or int64 (semantics_bytes 4 / 8) or
+ * NULL.  n < 2^31.
+ *   The voxel of a point, in the points' own dtype T: with v = (T)voxel_size and lo = min(points, 0) - (T)(voxel_size * 0.5) per axis (formed
+ *     by the caller in T, handed over exactly in doubles), c = trunc((p - lo) / v) -- ONE IEEE subtraction and ONE IEEE division, never a
+ *     product with the reciprocal -- and index = c.x + offset c.y + offset^2 c.z in int64, where the caller computes, in host float64,
+ *     hi = max(points, 0) + (T)(voxel_size * 0.5) and offset = (int)((max(hi) - min(lo) + 2 voxel_size) / voxel_size).  1 <= offset < 2^21.
+ *   sr_voxel_bounds: bounds [7] doubles = the minimum xyz and the maximum xyz over the rows whose three coordinates are finite, and the number
+ *     of the other rows (the caller refuses a cloud that has one: the reference silently produces garbage there).
+ *   sr_voxel_group: keys, stable sorts (label, then index: the library's radix sort in chained 32-bit passes, as many as offset asks
+ *     for), segment heads, per-voxel member count and label statistics; counts [3] (DEVICE memory: the one read-back is the caller's) =
+ *     {occupied voxels, kept voxels, labels outside 0..255}.  The label of a voxel is its most frequent label (the lowest of equally frequent
+ *     ones); a voxel is KEPT iff 5 max_count >= 4 members in integers -- the reference's `1.0 * max / len < 0.8` in float32 drops the same
+ *     voxels for every voxel of fewer than 2^23 members.  Without semantics every voxel is kept.  A label outside 0..255 is counted and
+ *     otherwise taken modulo 256: the caller raises (the reference takes any int32, while the model shifts 1 << label).
+ *   sr_voxel_emit, with the same cloud and workspace and the two counts read back: out_points / out_colors / out_normals [n_kept,3] float32 =
+ *     the arithmetic means of the members (float64 sums in an order that depends on the inputs alone, sum / count in float64, rounded once
+ *     to float32), out_semantics [n_kept] int32, and where not NULL out_counts [n_kept] int32 = the members and out_index [n_kept] int64 = the
+ *     voxel index; rows in ascending voxel index.  A NULL attribute and its output are skipped.
+ * Equal inputs give equal bits; integer atomics only.  A voxel of more than 128 members is given a wave, not a lane.  n == 0 is no error
+ * (counts are zeroed, nothing else is written; sr_voxel_bounds refuses it).  Every call checks its arguments before its first HIP call
+ * (SR_ERR_INVALID_ARGUMENT: a negative count, a NULL or misaligned pointer, a voxel_size that is not positive and finite, a non-finite lo,
+ * counts that contradict each other; SR_ERR_BUFFER_TOO_SMALL: a short workspace -- sr_voxel_workspace_bytes(n) bytes, 16-B aligned;
+ * SR_ERR_UNSUPPORTED: offset >= 2^21) and runs on the caller's stream.  Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_voxel_workspace_bytes(int32_t n);
+int sr_voxel_bounds(int32_t n, const void* points, int32_t points_f64, void* workspace, size_t workspace_bytes, double* bounds, void* stream);
+int sr_voxel_group(int32_t n, const void* points, int32_t points_f64, const void* semantics, int32_t semantics_bytes, const double* lo,
+                   double voxel_size, int64_t offset, void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream);
+int sr_voxel_emit(int32_t n, const void* points, int32_t points_f64, const void* colors, int32_t colors_f64, const void* normals,
+                  int32_t normals_f64, void* workspace, size_t workspace_bytes, int32_t n_voxels, int32_t n_kept, float* out_points,
+                  float* out_colors, float* out_normals, int32_t* out_semantics, int32_t* out_counts, int64_t* out_index, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

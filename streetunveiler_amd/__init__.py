@@ -22,7 +22,8 @@ _UNVEIL = ("FrameCamera", "FrameCameras", "pack_cameras", "points_in_frame", "fr
            "dilate_mask", "instance_pixel_mask", "refill_mask", "inpaint_conditions", "points_in_frame_torch", "frame_visibility_torch",
            "pick_view_torch", "semantic_mask_of_points_torch", "dilate_mask_numpy", "dilate_mask_torch", "instance_pixel_mask_torch",
            "refill_mask_torch", "inpaint_conditions_torch")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL)
+_VOXEL = ("SemanticCloud", "voxel_down_sample", "voxel_down_sample_torch", "create_from_pcd")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL + _VOXEL)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -62,4 +63,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _UNVEIL:
         from . import unveil
         return getattr(unveil, name)
+    if name in _VOXEL:
+        from . import voxel
+        return getattr(voxel, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -45,6 +45,7 @@ SOURCES = [
     ("mesh.hip", ["-ffp-contract=off"]),        # as tsdf.hip: the coordinates' fmaf()s are the only fused operations, t is one IEEE division
     ("mesh_post.hip", []),                      # integers only
     ("unveil.hip", ["-ffp-contract=off"]),      # 255 x + 0.5 and the composites are a product THEN a sum, as the stock-torch lines they restate
+    ("voxel.hip", ["-ffp-contract=off"]),       # the voxel coordinate is ONE subtraction and ONE division in the points' dtype: a bit-exact contract
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

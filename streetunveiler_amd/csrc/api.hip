@@ -1639,6 +1639,79 @@ int sr_inpaint_conditions(int32_t H, int32_t W, const float* full_render, const 
     return SR_OK;
 }
 
+// the checks the three launching sr_voxel_* calls share: the cloud and the workspace
+static int voxel_arguments(int32_t n, const void* points, int32_t points_f64, const void* workspace, size_t workspace_bytes) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n %d is negative", n);
+    if (points_f64 != 0 && points_f64 != 1) return fail(SR_ERR_INVALID_ARGUMENT, "points_f64 = %d: 0 (float32) or 1 (float64)", points_f64);
+    if (n == 0) return SR_OK;
+    if (!points) return fail(SR_ERR_INVALID_ARGUMENT, "points is NULL");
+    if ((uintptr_t)points & (points_f64 ? 7u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "points is not aligned to its element size");
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    if (workspace_bytes < voxel_workspace_bytes((uint32_t)n))
+        return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, voxel_workspace_bytes((uint32_t)n));
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    return SR_OK;
+}
+
+static int voxel_attribute(const char* name, const void* p, int32_t is_f64) {
+    if (is_f64 != 0 && is_f64 != 1) return fail(SR_ERR_INVALID_ARGUMENT, "%s_f64 = %d: 0 (float32) or 1 (float64)", name, is_f64);
+    if ((uintptr_t)p & (is_f64 ? 7u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "%s is not aligned to its element size", name);
+    return SR_OK;
+}
+
+size_t sr_voxel_workspace_bytes(int32_t n) { return n < 0 ? 0 : voxel_workspace_bytes((uint32_t)n); }
+
+int sr_voxel_bounds(int32_t n, const void* points, int32_t points_f64, void* workspace, size_t workspace_bytes, double* bounds, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (!bounds) return fail(SR_ERR_INVALID_ARGUMENT, "bounds is NULL");
+    if ((uintptr_t)bounds & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "bounds is not 8-B aligned");
+    if (n == 0) return fail(SR_ERR_INVALID_ARGUMENT, "an empty cloud has no bounds");
+    SR_HIP(voxel_bounds((uint32_t)n, points, points_f64, workspace, bounds, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_voxel_group(int32_t n, const void* points, int32_t points_f64, const void* semantics, int32_t semantics_bytes, const double* lo,
+                   double voxel_size, int64_t offset, void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (!(voxel_size > 0.0 && voxel_size <= DBL_MAX)) return fail(SR_ERR_INVALID_ARGUMENT, "voxel_size %g is not a positive finite number", voxel_size);
+    if (!lo) return fail(SR_ERR_INVALID_ARGUMENT, "lo is NULL");
+    if (!(std::isfinite(lo[0]) && std::isfinite(lo[1]) && std::isfinite(lo[2])))
+        return fail(SR_ERR_INVALID_ARGUMENT, "lo = (%g, %g, %g) is not finite: the cloud has a NaN or infinite coordinate", lo[0], lo[1], lo[2]);
+    if (offset < 1) return fail(SR_ERR_INVALID_ARGUMENT, "offset %lld < 1", (long long)offset);
+    if (offset >= kVoxelMaxOffset)
+        return fail(SR_ERR_UNSUPPORTED, "offset %lld >= 2^21: offset^3 would leave int64 (a larger voxel_size, or the cloud in parts)", (long long)offset);
+    if (semantics && semantics_bytes != 4 && semantics_bytes != 8) return fail(SR_ERR_INVALID_ARGUMENT, "semantics_bytes = %d: 4 (int32) or 8 (int64)", semantics_bytes);
+    if (semantics && ((uintptr_t)semantics & (uintptr_t)(semantics_bytes - 1))) return fail(SR_ERR_INVALID_ARGUMENT, "semantics is not aligned to its element size");
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s)); return SR_OK; }
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(s, false, &sort_mode)) return rc;
+    SR_HIP(voxel_group((uint32_t)n, points, points_f64, semantics, semantics_bytes, lo, voxel_size, (long long)offset, workspace, counts, sort_mode, s));
+    return SR_OK;
+}
+
+int sr_voxel_emit(int32_t n, const void* points, int32_t points_f64, const void* colors, int32_t colors_f64, const void* normals,
+                  int32_t normals_f64, void* workspace, size_t workspace_bytes, int32_t n_voxels, int32_t n_kept, float* out_points,
+                  float* out_colors, float* out_normals, int32_t* out_semantics, int32_t* out_counts, int64_t* out_index, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (int rc = voxel_attribute("colors", colors, colors_f64)) return rc;
+    if (int rc = voxel_attribute("normals", normals, normals_f64)) return rc;
+    if (n_voxels < 0 || n_voxels > n) return fail(SR_ERR_INVALID_ARGUMENT, "n_voxels = %d: not in 0..n = %d", n_voxels, n);
+    if (n_kept < 0 || n_kept > n_voxels) return fail(SR_ERR_INVALID_ARGUMENT, "n_kept = %d: not in 0..n_voxels = %d", n_kept, n_voxels);
+    if (n_kept == 0) return SR_OK;
+    if (!out_points) return fail(SR_ERR_INVALID_ARGUMENT, "out_points is NULL");
+    if (colors && !out_colors) return fail(SR_ERR_INVALID_ARGUMENT, "out_colors is NULL (colors is given)");
+    if (normals && !out_normals) return fail(SR_ERR_INVALID_ARGUMENT, "out_normals is NULL (normals is given)");
+    if (((uintptr_t)out_points | (uintptr_t)out_colors | (uintptr_t)out_normals | (uintptr_t)out_semantics | (uintptr_t)out_counts) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an output is not 4-B aligned");
+    if ((uintptr_t)out_index & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "out_index is not 8-B aligned");
+    SR_HIP(voxel_emit((uint32_t)n, points, points_f64, colors, colors_f64, normals, normals_f64, workspace, (uint32_t)n_voxels, (uint32_t)n_kept, out_points,
+                      out_colors, out_normals, out_semantics, out_counts, out_index, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
 int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, void* stream) {
     if (n > 0 && (!digits || !ranks)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bins < 1 || bins > 1024 || (n % 256u) != 0u) return fail(SR_ERR_INVALID_ARGUMENT, "bins %d not in 1..1024 or n %u not a multiple of 256", bins, n);

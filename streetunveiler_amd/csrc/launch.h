@@ -318,4 +318,20 @@ hipError_t refill_mask(int H, int W, int C, int k, const float* render_a, const 
                        hipStream_t s);
 hipError_t inpaint_conditions(const UnveilConditions& a, float threshold, int k, uint8_t* mask_out, hipStream_t s);
 
+// ---- voxel.hip -----------------------------------------------------------------------------------------------------------------------
+constexpr int kVoxelHeavy = 128;       // a voxel of more members than this gets a wave instead of a lane
+constexpr long long kVoxelMaxOffset = 1ll << 21;   // offset^3 must stay inside int64
+size_t voxel_workspace_bytes(uint32_t n);
+// n >= 1 in all three; points / colors / normals are [n,3] float32 or float64 (the *_f64 flags).  bounds: device [7] doubles = min xyz, max
+// xyz over the finite rows, the number of non-finite rows
+hipError_t voxel_bounds(uint32_t n, const void* points, int points_f64, void* ws, double* bounds, hipStream_t s);
+// labels: nullptr or [n] int32 / int64 (label_bytes 4 / 8); lo: three host doubles; 1 <= offset < kVoxelMaxOffset; counts (device, may be
+// nullptr): {voxels, kept, bad labels}
+hipError_t voxel_group(uint32_t n, const void* points, int points_f64, const void* labels, int label_bytes, const double* lo, double voxel_size,
+                       long long offset, void* ws, uint32_t* counts, RankMode rank_mode, hipStream_t s);
+// after voxel_group on the same points and workspace; rows >= 1: the kept count read back.  A nullptr attribute or output is skipped
+hipError_t voxel_emit(uint32_t n, const void* points, int points_f64, const void* colors, int colors_f64, const void* normals, int normals_f64,
+                      const void* ws, uint32_t n_voxels, uint32_t rows, float* out_points, float* out_colors, float* out_normals, int32_t* out_labels,
+                      int32_t* out_counts, int64_t* out_index, hipStream_t s);
+
 }  // namespace sr
