@@ -825,6 +825,56 @@ int sr_voxel_emit(int32_t n, const void* points, int32_t points_f64, const void*
                   int32_t normals_f64, void* workspace, size_t workspace_bytes, int32_t n_voxels, int32_t n_kept, float* out_points,
                   float* out_colors, float* out_normals, int32_t* out_semantics, int32_t* out_counts, int64_t* out_index, void* stream);
 
+/* LiDAR colouring and labelling from the camera frames (csrc/lidar_label.hip): what every dataset reader of the reference does to a sweep
+ * before the voxel downsample [REF scene/dataset_readers/projection_utils.py:17-104, waymo.py:79-192, kitti.py:117-163,
+ * pandaset.py:53-106].  One record of the DEVICE table a call reads (`views`: n_views records, 8-B aligned); it never crosses the call
+ * boundary by value, so it is a plain struct tag, and streetunveiler_amd/lidar_label.py states the same 192 bytes as a numpy dtype:
+ * rows 0..2 of the world-to-camera matrix (its last row must be (0, 0, 0, 1): the caller checks), the intrinsics row-major, the picture's
+ * size, the picture (uint8 [h,w,3], NULL where only labels are asked for: the colour sums are then zero) and the label map (uint8 [h,w]).
+ * Both pictures are dense and have EXACTLY h x w pixels: the library cannot check device memory and reads pixel (v, u) at v * w + u. */
+struct SrLabelView {
+    double w2c[12];
+    double K[9];
+    int32_t h, w;
+    const uint8_t* image;
+    const uint8_t* map;
+};
+/*   The predicate, in float64 in this order whatever the points' dtype (float32 is widened on load), no fused operation:
+ *     cam_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i,  p_i = (K_i0 cam_0 + K_i1 cam_1) + K_i2 cam_2,  pix = (p_0 / p_2, p_1 / p_2) by IEEE division;
+ *     inside iff pix.x < w && pix.x > 0 && pix.y < h && pix.y > 0 && cam_2 > 0 -- all strict, false for a NaN -- and x, y, z are finite;
+ *     (u, v) = trunc(pix).
+ *   The certainty test with r = check_range >= 0 and l0 = lut[map[v,u]] (label_lut: 256 device bytes applied to every map byte as it is
+ *     read, NULL = identity): the corners (v-r, u-r), (v-r, u+r), (v+r, u-r) and the fourth are compared with l0 where they are valid --
+ *     v-r > 0 resp. v+r < h with u-r > 0 resp. u+r < w, so row 0 and column 0 never are -- and the point is certain when no valid corner
+ *     differs.  fourth_corner = 0 (the reference): the fourth corner, valid when v+r < h && u+r < w, reads COLUMN u-r, which wraps to
+ *     w + u - r where it is negative (the reference's own line 94 under numpy's indexing); 1 (mirrored): it reads (v+r, u+r).
+ *   sr_lidar_label_decide: sweep s = the points sweep_offsets[s] .. sweep_offsets[s+1] (DEVICE int32 [n_sweeps + 1], ascending from 0 to n;
+ *     values outside are clamped, max_sweep_points >= the longest sweep) goes through the views s C .. s C + C - 1, C = cameras_per_sweep in
+ *     1..32, n_views >= n_sweeps C, n_views <= 65535.  per_view = 0: one row a point -- over its sweep's cameras in order, where the point is
+ *     inside and certain, the pixel's three bytes are added to integer sums, 1 to its count and label = lut[map[v,u]] (the last camera wins);
+ *     rows with count > 0 are kept.  per_view = 1: one row per (point, camera) that is inside and certain, in the order (sweep, camera,
+ *     point); n C < 2^31.  Rows and their scanned output offsets stay in the workspace; counts [2] (DEVICE uint64; the one read-back is
+ *     the caller's) = {kept rows, 0}.
+ *   sr_lidar_vote: every point through every view, no certainty test: per point the hits per class lut[map[v,u]] < n_classes (1..8) and
+ *     whether any view saw it -> valid_mask [n] bytes; a point's row carries tag = the FIRST largest class (argmax), count 1 where valid.
+ *     counts = {valid points, (point, view) hits whose label >= n_classes -- counted, not added to a class: the caller raises}.
+ *   sr_lidar_label_emit, after either on the same points, offsets and workspace, rows_per_point = 1 (per_view = 0, the vote) or C, n_rows =
+ *     counts[0]: out_xyz [n_rows,3] in the points' dtype, bit for bit; out_rgb [n_rows,3] doubles = sums / count, one IEEE division of
+ *     exact integers, on the 0..255 scale; out_semantics int32, out_index int64 = the point's index; rows_per_sweep int32 [n_sweeps].
+ *     NULL outputs are skipped; sweep_offsets NULL = one sweep of all points.
+ * Equal inputs give equal bits: the order comes from a prefix sum, the only atomic is the integer counter of the vote.  Every call checks its
+ * host arguments before its first HIP call and runs on the caller's stream; n == 0 is no error (counts are zeroed).  n < 2^31.
+ * Added without a new SR_ABI_VERSION: nothing that existed changed. */
+size_t sr_lidar_label_workspace_bytes(int32_t n, int32_t rows_per_point);
+int sr_lidar_label_decide(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                          const void* views, int32_t n_views, int32_t cameras_per_sweep, int32_t check_range, int32_t fourth_corner,
+                          const uint8_t* label_lut, int32_t per_view, void* workspace, size_t workspace_bytes, uint64_t* counts, void* stream);
+int sr_lidar_label_emit(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                        int32_t rows_per_point, void* workspace, size_t workspace_bytes, int32_t n_rows, void* out_xyz, double* out_rgb,
+                        int32_t* out_semantics, int64_t* out_index, int32_t* rows_per_sweep, void* stream);
+int sr_lidar_vote(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, int32_t n_classes, const uint8_t* label_lut,
+                  void* workspace, size_t workspace_bytes, uint8_t* valid_mask, uint64_t* counts, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

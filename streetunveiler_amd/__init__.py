@@ -23,7 +23,10 @@ _UNVEIL = ("FrameCamera", "FrameCameras", "pack_cameras", "points_in_frame", "fr
            "pick_view_torch", "semantic_mask_of_points_torch", "dilate_mask_numpy", "dilate_mask_torch", "instance_pixel_mask_torch",
            "refill_mask_torch", "inpaint_conditions_torch")
 _VOXEL = ("SemanticCloud", "voxel_down_sample", "voxel_down_sample_torch", "create_from_pcd")
-__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL + _VOXEL)
+_LIDAR_LABEL = ("LabelViews", "LabelledSweeps", "label_sweeps", "vote_semantics", "label_sweeps_numpy", "vote_semantics_numpy", "label_sweeps_torch",
+                "vote_semantics_torch", "in_frame_numpy", "certain_mask_numpy")
+__all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL + _VOXEL +
+               _LIDAR_LABEL)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -66,4 +69,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _VOXEL:
         from . import voxel
         return getattr(voxel, name)
+    if name in _LIDAR_LABEL:
+        from . import lidar_label
+        return getattr(lidar_label, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -186,6 +186,10 @@ PROTOTYPES = {
     "sr_voxel_bounds": (_int, [_i32, _vp, _i32] + _WS + [_vp, _vp]),
     "sr_voxel_group": (_int, [_i32, _vp, _i32, _vp, _i32, _P(_f64), _f64, _i64] + _WS + [_vp, _vp]),
     "sr_voxel_emit": (_int, [_i32, _vp, _i32, _vp, _i32, _vp, _i32] + _WS + [_i32, _i32] + [_vp] * 7),
+    "sr_lidar_label_workspace_bytes": (_sz, [_i32, _i32]),
+    "sr_lidar_label_decide": (_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp] + [_i32] * 4 + [_vp, _i32] + _WS + [_vp, _vp]),
+    "sr_lidar_label_emit": (_int, [_i32, _vp, _i32, _vp] + [_i32] * 3 + _WS + [_i32] + [_vp] * 6),
+    "sr_lidar_vote": (_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp] + _WS + [_vp] * 3),
     "sr_debug_pair_decisions":(_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
     "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
     "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),

@@ -46,6 +46,7 @@ SOURCES = [
     ("mesh_post.hip", []),                      # integers only
     ("unveil.hip", ["-ffp-contract=off"]),      # 255 x + 0.5 and the composites are a product THEN a sum, as the stock-torch lines they restate
     ("voxel.hip", ["-ffp-contract=off"]),       # the voxel coordinate is ONE subtraction and ONE division in the points' dtype: a bit-exact contract
+    ("lidar_label.hip", ["-ffp-contract=off"]), # the projection is the float64 operations as written, one rounding each: the decisions' contract
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]

@@ -1712,6 +1712,101 @@ int sr_voxel_emit(int32_t n, const void* points, int32_t points_f64, const void*
     return SR_OK;
 }
 
+// the checks the three launching sr_lidar_* calls share: the cloud, the view table and the workspace of n * rows_per_point rows
+static int lidar_arguments(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, const uint8_t* label_lut,
+                           int32_t rows_per_point, const void* workspace, size_t workspace_bytes, bool needs_views) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n %d is negative", n);
+    if (points_f64 != 0 && points_f64 != 1) return fail(SR_ERR_INVALID_ARGUMENT, "points_f64 = %d: 0 (float32) or 1 (float64)", points_f64);
+    if (rows_per_point < 1 || rows_per_point > kLabelMaxCameras)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%d rows a point: 1..%d", rows_per_point, kLabelMaxCameras);
+    if ((uint64_t)n * (uint64_t)rows_per_point >= (1ull << 31))
+        return fail(SR_ERR_UNSUPPORTED, "%d points x %d rows: fewer than 2^31 rows a call (fewer sweeps a call)", n, rows_per_point);
+    if (needs_views) {
+        if (n_views < 1 || n_views > kLabelMaxViews) return fail(SR_ERR_INVALID_ARGUMENT, "n_views = %d: 1..%d", n_views, kLabelMaxViews);
+        if (!views) return fail(SR_ERR_INVALID_ARGUMENT, "views is NULL");
+        if ((uintptr_t)views & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "views is not 8-B aligned");
+        (void)label_lut;       // 256 device bytes or NULL: nothing to check on the host
+    }
+    if (n == 0) return SR_OK;
+    if (!points) return fail(SR_ERR_INVALID_ARGUMENT, "points is NULL");
+    if ((uintptr_t)points & (points_f64 ? 7u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "points is not aligned to its element size");
+    if (!workspace) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is NULL");
+    const size_t need = lidar_label_workspace_bytes((uint64_t)n * (uint64_t)rows_per_point);
+    if (workspace_bytes < need) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15u) return fail(SR_ERR_INVALID_ARGUMENT, "workspace is not 16-B aligned");
+    return SR_OK;
+}
+
+static int lidar_sweeps(int32_t n, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points) {
+    if (n_sweeps < 1 || n_sweeps > kLabelMaxViews) return fail(SR_ERR_INVALID_ARGUMENT, "n_sweeps = %d: 1..%d", n_sweeps, kLabelMaxViews);
+    if ((uintptr_t)sweep_offsets & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "sweep_offsets is not 4-B aligned");
+    if (!sweep_offsets && n_sweeps != 1) return fail(SR_ERR_INVALID_ARGUMENT, "sweep_offsets is NULL with %d sweeps", n_sweeps);
+    if (max_sweep_points < 0 || max_sweep_points > n) return fail(SR_ERR_INVALID_ARGUMENT, "max_sweep_points = %d: not in 0..n = %d", max_sweep_points, n);
+    if (n > 0 && max_sweep_points < 1) return fail(SR_ERR_INVALID_ARGUMENT, "max_sweep_points = 0 with %d points", n);
+    return SR_OK;
+}
+
+size_t sr_lidar_label_workspace_bytes(int32_t n, int32_t rows_per_point) {
+    if (n < 0 || rows_per_point < 1 || rows_per_point > kLabelMaxCameras || (uint64_t)n * (uint64_t)rows_per_point >= (1ull << 31)) return 0;
+    return lidar_label_workspace_bytes((uint64_t)n * (uint64_t)rows_per_point);
+}
+
+int sr_lidar_label_decide(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                          const void* views, int32_t n_views, int32_t cameras_per_sweep, int32_t check_range, int32_t fourth_corner,
+                          const uint8_t* label_lut, int32_t per_view, void* workspace, size_t workspace_bytes, uint64_t* counts, void* stream) {
+    if (cameras_per_sweep < 1 || cameras_per_sweep > kLabelMaxCameras)
+        return fail(SR_ERR_INVALID_ARGUMENT, "cameras_per_sweep = %d: 1..%d", cameras_per_sweep, kLabelMaxCameras);
+    if (per_view != 0 && per_view != 1) return fail(SR_ERR_INVALID_ARGUMENT, "per_view = %d: 0 or 1", per_view);
+    const int32_t rows_per_point = per_view ? cameras_per_sweep : 1;
+    if (int rc = lidar_arguments(n, points, points_f64, views, n_views, label_lut, rows_per_point, workspace, workspace_bytes, true)) return rc;
+    if (int rc = lidar_sweeps(n, sweep_offsets, n_sweeps, max_sweep_points)) return rc;
+    if ((int64_t)n_sweeps * cameras_per_sweep > n_views)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%d sweeps x %d cameras > %d views", n_sweeps, cameras_per_sweep, n_views);
+    if (check_range < 0) return fail(SR_ERR_INVALID_ARGUMENT, "check_range %d is negative", check_range);
+    if (fourth_corner != 0 && fourth_corner != 1) return fail(SR_ERR_INVALID_ARGUMENT, "fourth_corner = %d: 0 (the reference's column) or 1 (mirrored)", fourth_corner);
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s)); return SR_OK; }
+    const LabelCloud c{(uint32_t)n, points, points_f64, sweep_offsets, n_sweeps, (uint32_t)max_sweep_points, rows_per_point};
+    SR_HIP(lidar_label_decide(c, static_cast<const SrLabelView*>(views), cameras_per_sweep, check_range, fourth_corner == 1, label_lut, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_lidar_label_emit(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                        int32_t rows_per_point, void* workspace, size_t workspace_bytes, int32_t n_rows, void* out_xyz, double* out_rgb,
+                        int32_t* out_semantics, int64_t* out_index, int32_t* rows_per_sweep, void* stream) {
+    if (int rc = lidar_arguments(n, points, points_f64, nullptr, 0, nullptr, rows_per_point, workspace, workspace_bytes, false)) return rc;
+    if (int rc = lidar_sweeps(n, sweep_offsets, n_sweeps, max_sweep_points)) return rc;
+    if (n_rows < 0 || (int64_t)n_rows > (int64_t)n * rows_per_point)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_rows = %d: not in 0..%lld", n_rows, (long long)n * rows_per_point);
+    if ((uintptr_t)out_xyz & (points_f64 ? 7u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "out_xyz is not aligned to the points' element size");
+    if (((uintptr_t)out_rgb | (uintptr_t)out_index) & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "out_rgb or out_index is not 8-B aligned");
+    if (((uintptr_t)out_semantics | (uintptr_t)rows_per_sweep) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "out_semantics or rows_per_sweep is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_rows == 0) {
+        if (rows_per_sweep) SR_HIP(hipMemsetAsync(rows_per_sweep, 0, sizeof(int32_t) * (size_t)n_sweeps, s));
+        return SR_OK;
+    }
+    const LabelCloud c{(uint32_t)n, points, points_f64, sweep_offsets, n_sweeps, (uint32_t)max_sweep_points, rows_per_point};
+    SR_HIP(lidar_label_emit(c, workspace, (uint32_t)n_rows, out_xyz, out_rgb, out_semantics, out_index, rows_per_sweep, s));
+    return SR_OK;
+}
+
+int sr_lidar_vote(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, int32_t n_classes, const uint8_t* label_lut,
+                  void* workspace, size_t workspace_bytes, uint8_t* valid_mask, uint64_t* counts, void* stream) {
+    if (int rc = lidar_arguments(n, points, points_f64, views, n_views, label_lut, 1, workspace, workspace_bytes, true)) return rc;
+    if (n_classes < 1 || n_classes > kLabelMaxClasses) return fail(SR_ERR_INVALID_ARGUMENT, "n_classes = %d: 1..%d", n_classes, kLabelMaxClasses);
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s)); return SR_OK; }
+    if (!valid_mask) return fail(SR_ERR_INVALID_ARGUMENT, "valid_mask is NULL");
+    const LabelCloud c{(uint32_t)n, points, points_f64, nullptr, 1, (uint32_t)n, 1};
+    SR_HIP(lidar_vote(c, static_cast<const SrLabelView*>(views), n_views, n_classes, label_lut, workspace, valid_mask, counts, s));
+    return SR_OK;
+}
+
 int sr_debug_lds_atomic_ranks(const uint32_t* digits, uint32_t* ranks, uint32_t n, int bins, void* stream) {
     if (n > 0 && (!digits || !ranks)) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bins < 1 || bins > 1024 || (n % 256u) != 0u) return fail(SR_ERR_INVALID_ARGUMENT, "bins %d not in 1..1024 or n %u not a multiple of 256", bins, n);

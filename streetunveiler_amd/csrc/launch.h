@@ -334,4 +334,28 @@ hipError_t voxel_emit(uint32_t n, const void* points, int points_f64, const void
                       const void* ws, uint32_t n_voxels, uint32_t rows, float* out_points, float* out_colors, float* out_normals, int32_t* out_labels,
                       int32_t* out_counts, int64_t* out_index, hipStream_t s);
 
+// ---- lidar_label.hip -----------------------------------------------------------------------------------------------------------------
+constexpr int kLabelMaxCameras = 32;   // a row's colour sums (13 bits each) and its count (6 bits) are sized for it
+constexpr int kLabelMaxViews = 65535;  // the vote counts a class in 16 bits; a sweep is a grid row
+constexpr int kLabelMaxClasses = 8;
+// what a decide / vote and the emit after it share: the cloud, its sweeps (offsets: device [n_sweeps + 1] or nullptr = one sweep of all
+// points; max_sweep >= the longest) and how many rows a point has (1, or C in the per-view mode)
+struct LabelCloud {
+    uint32_t n;
+    const void* points;
+    int points_f64;
+    const int32_t* sweep_offsets;
+    int n_sweeps;
+    uint32_t max_sweep;
+    int rows_per_point;
+};
+size_t lidar_label_workspace_bytes(uint64_t rows);
+// n >= 1 in all three; counts: device [2] uint64
+hipError_t lidar_label_decide(const LabelCloud& c, const SrLabelView* views, int cameras, int check_range, bool mirrored, const uint8_t* lut, void* ws,
+                              uint64_t* counts, hipStream_t s);
+hipError_t lidar_vote(const LabelCloud& c, const SrLabelView* views, int n_views, int n_classes, const uint8_t* lut, void* ws, uint8_t* valid_mask,
+                      uint64_t* counts, hipStream_t s);
+hipError_t lidar_label_emit(const LabelCloud& c, const void* ws, uint32_t n_rows, void* out_xyz, double* out_rgb, int32_t* out_semantics, int64_t* out_index,
+                            int32_t* rows_per_sweep, hipStream_t s);
+
 }  // namespace sr

@@ -28,8 +28,8 @@ every device; (2) labels must lie in 0..255 (the model elsewhere shifts 1 << lab
 (3) a NaN or infinite coordinate is refused (the reference silently produces garbage).  Also refused: offset >= 2**21 (offset**3 would
 leave int64), a voxel_size that is not positive and finite, row counts that disagree, CPU tensors -- there is no CPU path.
 
-Out of scope: colouring and labelling the LiDAR returns from the images (getWaymoPointCloudSemanticFromImage*, getCertainSemanticMask) and
-the dataset readers themselves.  voxel_down_sample_with_no_grad is the same routine (nothing here records a graph) and is an alias."""
+Out of scope: the dataset readers themselves (colouring and labelling the LiDAR returns from the images -- getWaymoPointCloudSemanticFromImage*,
+getCertainSemanticMask -- is lidar_label.py).  voxel_down_sample_with_no_grad is the same routine (nothing here records a graph) and is an alias."""
 from __future__ import annotations
 
 import ctypes as C
