@@ -12,17 +12,35 @@
 // and every gradient element is the float64 expression of its float32 inputs, rounded to float32 ONCE, at the store; the sums stay
 // float64 up to the store of the loss.  No atomics, no host read-back; g is read from device memory, so a captured graph replays with
 // whatever the upstream scalar then holds.
-#include "launch.h"
+#include "abi.h"
 #include "reduce.h"
 
 namespace sr {
+
+constexpr int kCeMaxClasses = 8;
+static_assert(SR_CE_MAX_CLASSES == kCeMaxClasses, "the header's class limit is the kernels'");
+enum class CeTarget { kProbabilities = 0, kLabelsU8 = 1, kLabelsI32 = 4, kLabelsI64 = 8 };   // the labels' values are their widths in bytes
+struct CeArgs {            // a kernel parameter, by value: the class weights travel in the launch
+    int C;
+    size_t N;              // H * W
+    float w[kCeMaxClasses];
+    const float* x;        // [C,H,W] logits
+    const void* target;    // [H,W] labels or [C,H,W] float probabilities
+};
+struct SurfaceRegArgs {    // a kernel parameter, by value
+    size_t N;
+    double lambda_normal, lambda_dist;
+    const float* rend_normal;   // [3,H,W]
+    const float* surf_normal;   // [3,H,W]
+    const float* rend_dist;     // [1,H,W]
+};
 
 constexpr int kAuxThreads = kReduceThreads;   // one pixel / Gaussian per thread; one partial (pair) per workgroup
 
 static inline size_t aux_blocks(size_t n) { return (n + kAuxThreads - 1) / kAuxThreads; }
 
-bool aux_loss_supported(size_t n) { return aux_blocks(n) <= 0x7fffffffull; }
-size_t aux_loss_workspace_bytes(size_t n) { return aux_blocks(n) * 2 * sizeof(double); }
+static bool aux_loss_supported(size_t n) { return aux_blocks(n) <= 0x7fffffffull; }              // the element counts the launches can address
+static size_t aux_loss_workspace_bytes(size_t n) { return aux_blocks(n) * 2 * sizeof(double); }   // per-block partial sums of n pixels / Gaussians
 
 // ---- finalize: one workgroup; K == 1: out[0] = w0 * sum0 / n;  K == 2: out = {a + b, a, b},  a = w0 * sum0 / n,  b = w1 * sum1 / n ---------
 template <int K>
@@ -141,7 +159,7 @@ static hipError_t ce_forward(const CeArgs& a, void* workspace, float* out1, hipS
     return hipGetLastError();
 }
 
-hipError_t launch_semantic_ce_forward(const CeArgs& a, CeTarget form, void* workspace, float* out1, hipStream_t s) {
+static hipError_t launch_semantic_ce_forward(const CeArgs& a, CeTarget form, void* workspace, float* out1, hipStream_t s) {
     switch (form) {
         case CeTarget::kProbabilities: return ce_forward<CeTarget::kProbabilities>(a, workspace, out1, s);
         case CeTarget::kLabelsU8: return ce_forward<CeTarget::kLabelsU8>(a, workspace, out1, s);
@@ -151,7 +169,7 @@ hipError_t launch_semantic_ce_forward(const CeArgs& a, CeTarget form, void* work
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_semantic_ce_backward(const CeArgs& a, CeTarget form, const float* g_loss, float* g_x, hipStream_t s) {
+static hipError_t launch_semantic_ce_backward(const CeArgs& a, CeTarget form, const float* g_loss, float* g_x, hipStream_t s) {
     const dim3 grid((unsigned)aux_blocks(a.N)), block(kAuxThreads);
     switch (form) {
         case CeTarget::kProbabilities: hipLaunchKernelGGL(semantic_ce_backward_kernel<CeTarget::kProbabilities>, grid, block, 0, s, a, g_loss, g_x); break;
@@ -195,7 +213,7 @@ __global__ __launch_bounds__(kAuxThreads) void surface_reg_backward_kernel(Surfa
     if (g_dist) g_dist[pix] = (float)(g * a.lambda_dist / (double)a.N);
 }
 
-hipError_t launch_surface_reg_forward(const SurfaceRegArgs& a, void* workspace, float* out3, hipStream_t s) {
+static hipError_t launch_surface_reg_forward(const SurfaceRegArgs& a, void* workspace, float* out3, hipStream_t s) {
     double* partials = static_cast<double*>(workspace);
     const int blocks = (int)aux_blocks(a.N);
     hipLaunchKernelGGL(surface_reg_forward_kernel, dim3(blocks), dim3(kAuxThreads), 0, s, a, partials);
@@ -203,7 +221,7 @@ hipError_t launch_surface_reg_forward(const SurfaceRegArgs& a, void* workspace, 
     return hipGetLastError();
 }
 
-hipError_t launch_surface_reg_backward(const SurfaceRegArgs& a, const float* g_loss, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist,
+static hipError_t launch_surface_reg_backward(const SurfaceRegArgs& a, const float* g_loss, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist,
                                        hipStream_t s) {
     hipLaunchKernelGGL(surface_reg_backward_kernel, dim3((unsigned)aux_blocks(a.N)), dim3(kAuxThreads), 0, s, a, g_loss, g_rend_normal, g_surf_normal,
                        g_rend_dist);
@@ -237,7 +255,7 @@ __global__ __launch_bounds__(kAuxThreads) void opacity_shrink_backward_kernel(si
     }
 }
 
-hipError_t launch_opacity_shrink_forward(size_t P, const float* opacity, bool activated, void* workspace, float* out1, hipStream_t s) {
+static hipError_t launch_opacity_shrink_forward(size_t P, const float* opacity, bool activated, void* workspace, float* out1, hipStream_t s) {
     double* partials = static_cast<double*>(workspace);
     const int blocks = (int)aux_blocks(P);
     if (activated)
@@ -248,7 +266,7 @@ hipError_t launch_opacity_shrink_forward(size_t P, const float* opacity, bool ac
     return hipGetLastError();
 }
 
-hipError_t launch_opacity_shrink_backward(size_t P, const float* opacity, bool activated, const float* g_loss, float* g_opacity, hipStream_t s) {
+static hipError_t launch_opacity_shrink_backward(size_t P, const float* opacity, bool activated, const float* g_loss, float* g_opacity, hipStream_t s) {
     const dim3 grid((unsigned)aux_blocks(P)), block(kAuxThreads);
     if (activated)
         hipLaunchKernelGGL(opacity_shrink_backward_kernel<true>, grid, block, 0, s, P, opacity, g_loss, g_opacity);
@@ -258,3 +276,101 @@ hipError_t launch_opacity_shrink_backward(size_t P, const float* opacity, bool a
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+namespace {
+
+// shared refusals of the auxiliary losses: the element count, then (forwards only: workspace_bytes != nullptr) the workspace
+int aux_count(const char* what, int64_t n, const void* workspace, const size_t* workspace_bytes) {
+    if (!aux_loss_supported((size_t)n)) return fail(SR_ERR_UNSUPPORTED, "%s: %lld elements are beyond the launch limits", what, (long long)n);
+    if (!workspace_bytes) return SR_OK;
+    return check_workspace_size(workspace, *workspace_bytes, aux_loss_workspace_bytes((size_t)n), what);
+}
+
+int semantic_ce_args(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                     CeArgs* a, CeTarget* form) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (C < 1 || C > SR_CE_MAX_CLASSES) return fail(SR_ERR_INVALID_ARGUMENT, "%d classes: not in 1..%d", C, SR_CE_MAX_CLASSES);
+    if (label_bytes != 0 && label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail(SR_ERR_INVALID_ARGUMENT, "label_bytes %d: not 0 (probabilities), 1, 4 or 8", label_bytes);
+    if (!logits || !target) return fail(SR_ERR_INVALID_ARGUMENT, "logits / target is NULL");
+    *form = static_cast<CeTarget>(label_bytes);
+    a->C = C;
+    a->N = (size_t)W * (size_t)H;
+    for (int c = 0; c < kCeMaxClasses; ++c) a->w[c] = c < C ? (weight ? weight[c] : 1.f) : 0.f;
+    a->x = logits;
+    a->target = target;
+    return SR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sr_aux_loss_workspace_bytes(int64_t n) { return n > 0 ? aux_loss_workspace_bytes((size_t)n) : 0; }
+
+int sr_semantic_ce_forward(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                           void* workspace, size_t workspace_bytes, float* out1, void* stream) {
+    CeArgs a;
+    CeTarget form;
+    if (int rc = semantic_ce_args(W, H, C, logits, target, label_bytes, weight, &a, &form)) return rc;
+    if (!out1) return fail(SR_ERR_INVALID_ARGUMENT, "out1 is NULL");
+    if (int rc = aux_count("sr_semantic_ce_forward", (int64_t)a.N, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_semantic_ce_forward(a, form, workspace, out1, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_semantic_ce_backward(int32_t W, int32_t H, int32_t C, const float* logits, const void* target, int32_t label_bytes, const float* weight,
+                            const float* g_loss, float* g_logits, void* stream) {
+    CeArgs a;
+    CeTarget form;
+    if (int rc = semantic_ce_args(W, H, C, logits, target, label_bytes, weight, &a, &form)) return rc;
+    if (!g_loss || !g_logits) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_logits is NULL");
+    if (int rc = aux_count("sr_semantic_ce_backward", (int64_t)a.N, nullptr, nullptr)) return rc;
+    SR_HIP(launch_semantic_ce_backward(a, form, g_loss, g_logits, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_surface_reg_forward(int32_t W, int32_t H, const float* rend_normal, const float* surf_normal, const float* rend_dist, double lambda_normal,
+                           double lambda_dist, void* workspace, size_t workspace_bytes, float* out3, void* stream) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (!rend_normal || !surf_normal || !rend_dist || !out3) return fail(SR_ERR_INVALID_ARGUMENT, "rend_normal / surf_normal / rend_dist / out3 is NULL");
+    const SurfaceRegArgs a{(size_t)W * (size_t)H, lambda_normal, lambda_dist, rend_normal, surf_normal, rend_dist};
+    if (int rc = aux_count("sr_surface_reg_forward", (int64_t)a.N, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_surface_reg_forward(a, workspace, out3, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_surface_reg_backward(int32_t W, int32_t H, const float* rend_normal, const float* surf_normal, double lambda_normal, double lambda_dist,
+                            const float* g_loss, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist, void* stream) {
+    if (W < 1 || H < 1) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d", W, H);
+    if (!g_loss) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss is NULL");
+    if (g_rend_normal && !surf_normal) return fail(SR_ERR_INVALID_ARGUMENT, "g_rend_normal is asked for without surf_normal");
+    if (g_surf_normal && !rend_normal) return fail(SR_ERR_INVALID_ARGUMENT, "g_surf_normal is asked for without rend_normal");
+    const SurfaceRegArgs a{(size_t)W * (size_t)H, lambda_normal, lambda_dist, rend_normal, surf_normal, nullptr};
+    if (int rc = aux_count("sr_surface_reg_backward", (int64_t)a.N, nullptr, nullptr)) return rc;
+    if (!g_rend_normal && !g_surf_normal && !g_rend_dist) return SR_OK;
+    SR_HIP(launch_surface_reg_backward(a, g_loss, g_rend_normal, g_surf_normal, g_rend_dist, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_opacity_shrink_forward(int64_t P, const float* opacity, int32_t activated, void* workspace, size_t workspace_bytes, float* out1, void* stream) {
+    if (P < 1) return fail(SR_ERR_INVALID_ARGUMENT, "P %lld < 1", (long long)P);
+    if (!opacity || !out1) return fail(SR_ERR_INVALID_ARGUMENT, "opacity / out1 is NULL");
+    if (int rc = aux_count("sr_opacity_shrink_forward", P, workspace, &workspace_bytes)) return rc;
+    SR_HIP(launch_opacity_shrink_forward((size_t)P, opacity, activated != 0, workspace, out1, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_opacity_shrink_backward(int64_t P, const float* opacity, int32_t activated, const float* g_loss, float* g_opacity, void* stream) {
+    if (P < 1) return fail(SR_ERR_INVALID_ARGUMENT, "P %lld < 1", (long long)P);
+    if (!g_loss || !g_opacity) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_opacity is NULL");
+    if (!activated && !opacity) return fail(SR_ERR_INVALID_ARGUMENT, "opacity is NULL");
+    if (int rc = aux_count("sr_opacity_shrink_backward", P, nullptr, nullptr)) return rc;
+    SR_HIP(launch_opacity_shrink_backward((size_t)P, opacity, activated != 0, g_loss, g_opacity, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

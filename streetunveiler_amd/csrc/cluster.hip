@@ -15,7 +15,7 @@
 #include <cstdint>
 
 #include "cloud.h"
-#include "launch.h"
+#include "abi.h"
 #include "union_find.h"
 
 namespace sr {
@@ -114,10 +114,10 @@ static float cluster_d2_below(float r) {
     return t;
 }
 
-size_t cluster_workspace_bytes(int n) { return cluster_layout(n).total; }
+static size_t cluster_workspace_bytes(int n) { return cluster_layout(n).total; }
 
-// n >= 1; radius finite and >= 0 (api.hip)
-hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* ws, size_t ws_bytes,
+// n >= 1; radius finite and >= 0
+static hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* ws, size_t ws_bytes,
                           RankMode rank_mode, hipStream_t s) {
     const ClusterLayout L = cluster_layout(n);
     if (ws_bytes < L.total) return hipErrorInvalidValue;
@@ -138,3 +138,25 @@ hipError_t cluster_radius(int n, const float* xyz, const uint8_t* active, float 
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+extern "C" {
+
+size_t sr_cluster_workspace_bytes(int32_t n) { return cluster_workspace_bytes(n > 0 ? n : 0); }
+
+int sr_cluster_radius(int32_t n, const float* xyz, const uint8_t* active, float radius, int64_t* labels, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "negative point count");
+    if (!(radius >= 0.f && radius <= FLT_MAX)) return fail(SR_ERR_INVALID_ARGUMENT, "radius %g is not a finite number >= 0", (double)radius);
+    if (n == 0) return SR_OK;
+    if (!xyz || !labels || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int rc = check_workspace_size(workspace, workspace_bytes, cluster_workspace_bytes(n))) return rc;
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &sort_mode)) return rc;
+    SR_HIP(cluster_radius(n, xyz, active, radius, labels, workspace, workspace_bytes, sort_mode, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

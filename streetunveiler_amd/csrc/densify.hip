@@ -9,7 +9,7 @@
 // below is the one that runs; the quotient accum / denom, 1 / norm and exp(s) / 1.6 are correctly rounded IEEE divisions.
 #include <cmath>
 
-#include "launch.h"
+#include "abi.h"
 #include "scan.h"
 
 namespace sr {
@@ -18,6 +18,11 @@ constexpr int kDfThreads = 256;               // Gaussians per block of the deci
 constexpr int kDfChunkWords = 4096;           // output words of one tensor a workgroup of the gather handles per iteration
 constexpr int kDfMaxBlocks = 4096;            // 256 CUs x 16 workgroups; the rest is grid-strided
 constexpr uint32_t kDfIndexMask = 0x3FFFFFFFu;
+
+struct DensifyRule {   // a kernel parameter, by value
+    float max_grad, min_opacity, percent_dense_extent, ws_limit;   // ws_limit < 0: no world-size test
+    int select;        // 0: nothing is clone- or split-selected and accum / denom are not read (max_grad is +inf or NaN)
+};
 
 struct DensifyLayout {
     size_t flags, map, child_rank, totals, total;
@@ -35,7 +40,7 @@ static DensifyLayout densify_layout(int P) {
     L.total = c.off;
     return L;
 }
-size_t densify_workspace_bytes(int P) { return densify_layout(P).total; }
+static size_t densify_workspace_bytes(int P) { return densify_layout(P).total; }
 
 // ---- decision ------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float max_like_torch(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }   // torch.max keeps a NaN
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(kDfThreads) void densify_map_kernel(int P, const ui
     }
 }
 
-hipError_t densify_plan(int P, const float* accum, const float* denom, const float* opacity, const float* scaling, const DensifyRule& rule,
+static hipError_t densify_plan(int P, const float* accum, const float* denom, const float* opacity, const float* scaling, const DensifyRule& rule,
                         const uint8_t* prune_mask, void* workspace, uint32_t* counts_pinned_dev, hipStream_t s) {
     const DensifyLayout L = densify_layout(P);
     uint8_t* flags = at<uint8_t>(workspace, L.flags);
@@ -136,7 +141,7 @@ hipError_t densify_plan(int P, const float* accum, const float* denom, const flo
     return hipGetLastError();
 }
 
-const uint32_t* densify_counts_device(int P, const void* workspace) {
+static const uint32_t* densify_counts_device(int P, const void* workspace) {
     const DensifyLayout L = densify_layout(P);
     return reinterpret_cast<const uint32_t*>(static_cast<const char*>(workspace) + L.totals + 16 * (size_t)L.nblocks);
 }
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(kDfThreads) void densify_gather_kernel(const Gather
     }
 }
 
-hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+static hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
                          const SrDensifySegment* segments, int n_segments, const void* workspace, hipStream_t stream) {
     const DensifyLayout L = densify_layout(P);
     const char* ws = static_cast<const char*>(workspace);
@@ -246,3 +251,67 @@ hipError_t densify_apply(int P, const uint32_t* counts, const float* noise, cons
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+extern "C" {
+
+size_t sr_densify_workspace_bytes(int32_t P) { return densify_workspace_bytes(P > 0 ? P : 0); }
+
+int sr_densify_plan(int32_t P, const float* accum, const float* denom, const float* opacity, const float* scaling, float max_grad,
+                    float min_opacity, float percent_dense_extent, float ws_limit, const uint8_t* prune_mask, void* workspace,
+                    size_t workspace_bytes, uint32_t* counts_out, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (!counts_out) return fail(SR_ERR_INVALID_ARGUMENT, "counts_out is NULL");
+    counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    if (P == 0) return SR_OK;
+    if (P >= (1 << 30)) return fail(SR_ERR_UNSUPPORTED, "P = %d: the source map holds 30-bit indices", P);
+    DensifyRule rule{max_grad, min_opacity, percent_dense_extent, ws_limit, max_grad < INFINITY ? 1 : 0};   // (NaN: not below +inf)
+    if (rule.select && (!accum || !denom)) return fail(SR_ERR_INVALID_ARGUMENT, "accum / denom is NULL (only a max_grad of +inf goes without them)");
+    if (!opacity || !scaling) return fail(SR_ERR_INVALID_ARGUMENT, "opacity / scaling is NULL");
+    if (int rc = check_workspace(workspace, workspace_bytes, densify_workspace_bytes(P))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // K, C, S and H travel like sr_forward_plan's D: the totals kernel stores them into the calling thread's pinned words when those are
+    // mapped into the device's address space, else a DMA copy fetches them; the host waits for the stream once.
+    uint32_t* pinned = pinned_words();
+    uint32_t* pinned_dev = nullptr;
+    if (pinned && hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0) != hipSuccess) { pinned_dev = nullptr; (void)hipGetLastError(); }
+    SR_HIP(densify_plan(P, accum, denom, opacity, scaling, rule, prune_mask, workspace, pinned_dev ? pinned_dev + 4 : nullptr, s));
+    uint32_t* target = pinned ? pinned + 4 : counts_out;
+    if (!pinned_dev) SR_HIP(hipMemcpyAsync(target, densify_counts_device(P, workspace), 16, hipMemcpyDeviceToHost, s));
+    SR_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < 4; ++k) counts_out[k] = reinterpret_cast<volatile uint32_t*>(target)[k];
+    return SR_OK;
+}
+
+int sr_densify_apply(int32_t P, const uint32_t* counts, const float* noise, const float* rotation, const float* scaling,
+                     const SrDensifySegment* segments, int32_t n_segments, void* workspace, size_t workspace_bytes, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if (n_segments < 0 || n_segments > SR_DENSIFY_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 0..%d", n_segments, SR_DENSIFY_MAX_SEGMENTS);
+    if (n_segments > 0 && !segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    const uint64_t K = counts[0], C = counts[1], S = counts[2], H = counts[3];
+    if (C > K || H > S || K + S > (uint64_t)P)
+        return fail(SR_ERR_INVALID_ARGUMENT, "counts {%u, %u, %u, %u} are not those of a plan over %d Gaussians", counts[0], counts[1], counts[2], counts[3], P);
+    const bool rows = K + C + 2 * H > 0;
+    for (int k = 0; k < n_segments; ++k) {
+        const SrDensifySegment& a = segments[k];
+        if (a.role < SR_DENSIFY_ROLE_COPY || a.role > SR_DENSIFY_ROLE_SCALING) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: unknown role %d", k, a.role);
+        if (a.row_words < 0 || a.row_words > 65535) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: row_words %d not in 0..65535", k, a.row_words);
+        if (a.role == SR_DENSIFY_ROLE_XYZ && a.row_words != 3) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the xyz role takes rows of 3 words, not %d", k, a.row_words);
+        if (a.role == SR_DENSIFY_ROLE_SCALING && a.row_words != 2) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the scaling role takes rows of 2 words, not %d", k, a.row_words);
+        if (a.row_words == 0 || !rows) continue;
+        if (!a.src || !a.dst) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: src / dst is NULL", k);
+        if (((uintptr_t)a.src | (uintptr_t)a.dst) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: src / dst is not 4-B aligned", k);
+        if (a.role == SR_DENSIFY_ROLE_XYZ && H > 0 && (!noise || !rotation || !scaling))
+            return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: the xyz role needs noise, rotation and scaling when children survive", k);
+    }
+    if (P == 0 || !rows || n_segments == 0) return SR_OK;
+    if (int rc = check_workspace_size(workspace, workspace_bytes, densify_workspace_bytes(P))) return rc;   // (no alignment test here, unlike the plan)
+    SR_HIP(densify_apply(P, counts, noise, rotation, scaling, segments, n_segments, workspace, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

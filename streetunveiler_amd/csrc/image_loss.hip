@@ -13,9 +13,18 @@
 //           B = ds/d(s1), Cm = ds/d(s12), A = ds/d(mu1) - 2 mu1 B - mu2 Cm;  the same separable zero-padded window over three fields.
 //           g is read from device memory.  With the composite: dL/dsky = (1 - alpha) dL/dx,  dL/dalpha = -sum_c sky_c dL/dx_c
 //           (one workgroup walks the channels of its tile, so that sum needs no atomics either).
-#include "launch.h"   // LossImages
+#include "abi.h"
 
 namespace sr {
+
+struct LossImages {       // a kernel parameter, by value
+    int W, H, C;
+    float lambda;
+    const float* image;   // [C,H,W]
+    const float* gt;      // [C,H,W]
+    const float* sky;     // [C,H,W] or NULL
+    const float* alpha;   // [1,H,W] or NULL (with sky)
+};
 
 constexpr int kLossTW = 32, kLossTH = 16, kLossR = 5;
 constexpr int kLossSW = kLossTW + 2 * kLossR, kLossSH = kLossTH + 2 * kLossR;   // staged tile with its halo: 42 x 26
@@ -220,15 +229,15 @@ static inline int loss_tiles_x(int W) { return (W + kLossTW - 1) / kLossTW; }
 static inline int loss_tiles_y(int H) { return (H + kLossTH - 1) / kLossTH; }
 
 // the frame sizes the launches below can address: the tile count as an int, grid.y / grid.z within the launch limits
-bool image_loss_supported(int W, int H, int C) {
+static bool image_loss_supported(int W, int H, int C) {
     const long long tiles = (long long)loss_tiles_x(W) * loss_tiles_y(H) * C;
     return tiles <= 0x7fffffffLL && loss_tiles_y(H) <= 65535 && C <= 65535;
 }
 
 // workspace: [kLossMaxBlocks][2] partial sums, then the planes A, B, Cm of [C,H,W] floats each
-size_t image_loss_partial_bytes() { return (size_t)kLossMaxBlocks * 2 * sizeof(float); }
+static size_t image_loss_partial_bytes() { return (size_t)kLossMaxBlocks * 2 * sizeof(float); }
 
-hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s) {
+static hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float* out3, hipStream_t s) {
     const size_t n = (size_t)a.W * a.H * a.C;
     float* partials = static_cast<float*>(workspace);
     float* A = partials + kLossMaxBlocks * 2;
@@ -244,8 +253,8 @@ hipError_t launch_image_loss_forward(const LossImages& a, void* workspace, float
     return hipGetLastError();
 }
 
-hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
-                                      float* g_alpha, hipStream_t s) {
+static hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace, const float* g_loss, float* g_image, float* g_sky,
+                                             float* g_alpha, hipStream_t s) {
     const size_t n = (size_t)a.W * a.H * a.C;
     const float* A = static_cast<const float*>(workspace) + kLossMaxBlocks * 2;
     const float *B = A + n, *Cm = B + n;
@@ -261,3 +270,46 @@ hipError_t launch_image_loss_backward(const LossImages& a, const void* workspace
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+extern "C" size_t sr_image_loss_workspace_bytes(int32_t W, int32_t H, int32_t C) {
+    if (W <= 0 || H <= 0 || C <= 0) return 0;
+    return image_loss_partial_bytes() + 3 * sizeof(float) * (size_t)W * (size_t)H * (size_t)C;
+}
+
+static int image_loss_args(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                           const float* alpha, const void* workspace, size_t workspace_bytes, LossImages* a) {
+    if (W <= 0 || H <= 0 || C <= 0) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size %dx%d with %d channels", W, H, C);
+    if (!image || !gt || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "image / gt / workspace is NULL");
+    if ((sky != nullptr) != (alpha != nullptr)) return fail(SR_ERR_INVALID_ARGUMENT, "sky and alpha go together: give both or neither");
+    if (!image_loss_supported(W, H, C)) return fail(SR_ERR_UNSUPPORTED, "%dx%d with %d channels is beyond the launch limits", W, H, C);
+    if (int rc = check_workspace_size(workspace, workspace_bytes, sr_image_loss_workspace_bytes(W, H, C))) return rc;
+    *a = LossImages{W, H, C, lambda_dssim, image, gt, sky, alpha};
+    return SR_OK;
+}
+
+extern "C" {
+
+int sr_image_loss_forward(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                          const float* alpha, void* workspace, size_t workspace_bytes, float* out3, void* stream) {
+    LossImages a;
+    if (int rc = image_loss_args(W, H, C, lambda_dssim, image, gt, sky, alpha, workspace, workspace_bytes, &a)) return rc;
+    if (!out3) return fail(SR_ERR_INVALID_ARGUMENT, "out3 is NULL");
+    SR_HIP(launch_image_loss_forward(a, workspace, out3, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_image_loss_backward(int32_t W, int32_t H, int32_t C, float lambda_dssim, const float* image, const float* gt, const float* sky,
+                           const float* alpha, const void* workspace, size_t workspace_bytes, const float* g_loss, float* g_image,
+                           float* g_sky, float* g_alpha, void* stream) {
+    LossImages a;
+    if (int rc = image_loss_args(W, H, C, lambda_dssim, image, gt, sky, alpha, workspace, workspace_bytes, &a)) return rc;
+    if (!g_loss || !g_image) return fail(SR_ERR_INVALID_ARGUMENT, "g_loss / g_image is NULL");
+    if (sky && (!g_sky || !g_alpha)) return fail(SR_ERR_INVALID_ARGUMENT, "with sky and alpha, g_sky and g_alpha are required");
+    SR_HIP(launch_image_loss_backward(a, workspace, g_loss, g_image, g_sky, g_alpha, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -15,7 +15,7 @@
 #include <cstdint>
 
 #include "cloud.h"
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
 
@@ -278,10 +278,10 @@ KnnLayout knn_layout(int nq, int nr) {   // nq == 0: self search
     return L;
 }
 
-size_t knn_workspace_bytes(int nq, int nr) { return knn_layout(nq, nr).total; }
+static size_t knn_workspace_bytes(int nq, int nr) { return knn_layout(nq, nr).total; }
 
 // query == nullptr / nq == 0: every reference point against the others
-hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
+static hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* reference, int K, int take_sqrt, float* out, void* ws,
                           size_t ws_bytes, RankMode rank_mode, hipStream_t s) {
     const bool self = query == nullptr;
     if (self) nq = 0;
@@ -321,3 +321,29 @@ hipError_t knn_mean_dist2(int nq, const float* query, int nr, const float* refer
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+extern "C" {
+
+size_t sr_knn_workspace_bytes(int32_t n_query, int32_t n_reference) {
+    return knn_workspace_bytes(n_query > 0 ? n_query : 0, n_reference > 0 ? n_reference : 0);
+}
+
+int sr_knn_mean_dist2(int32_t n_query, const float* query, int32_t n_reference, const float* reference, int32_t K,
+                      int32_t take_sqrt, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (K != 3 && K != 10) return fail(SR_ERR_UNSUPPORTED, "K = %d, supported: 3 and 10", K);
+    if (n_reference < 0 || (query && n_query < 0)) return fail(SR_ERR_INVALID_ARGUMENT, "negative point count");
+    const int nq = query ? n_query : 0;
+    if ((query ? nq : n_reference) == 0) return SR_OK;
+    if (n_reference == 0) return fail(SR_ERR_INVALID_ARGUMENT, "empty reference cloud");
+    if (!reference || !out || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int rc = check_workspace_size(workspace, workspace_bytes, knn_workspace_bytes(nq, n_reference))) return rc;
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(static_cast<hipStream_t>(stream), false, &sort_mode)) return rc;
+    SR_HIP(knn_mean_dist2(nq, query, n_reference, reference, K, take_sqrt, out, workspace, workspace_bytes, sort_mode, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

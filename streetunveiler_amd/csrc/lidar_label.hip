@@ -18,13 +18,27 @@
 // the float64 operations written below, one rounding each, in this order.
 #include <cmath>
 
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
 
 constexpr int kLabelThreads = 256;
 constexpr int kVoteRows = 4;                                 // points a thread of lidar_vote_kernel holds
 constexpr int kVoteChunk = kVoteRows * kLabelThreads;
+constexpr int kLabelMaxCameras = 32;   // a row's colour sums (13 bits each) and its count (6 bits) are sized for it
+constexpr int kLabelMaxViews = 65535;  // the vote counts a class in 16 bits; a sweep is a grid row
+constexpr int kLabelMaxClasses = 8;
+// what a decide / vote and the emit after it share: the cloud, its sweeps (offsets: device [n_sweeps + 1] or nullptr = one sweep of all
+// points; max_sweep >= the longest) and how many rows a point has (1, or C in the per-view mode)
+struct LabelCloud {
+    uint32_t n;
+    const void* points;
+    int points_f64;
+    const int32_t* sweep_offsets;
+    int n_sweeps;
+    uint32_t max_sweep;
+    int rows_per_point;
+};
 
 // ---- a row ----------------------------------------------------------------------------------------------------------------------------
 // sums of at most 32 bytes: 13 bits each; count 0..32: 6 bits; label: 8 bits
@@ -261,14 +275,14 @@ static LabelLayout label_layout(uint64_t rows) {
     L.total = c.off;
     return L;
 }
-size_t lidar_label_workspace_bytes(uint64_t rows) { return label_layout(rows).total; }
+static size_t lidar_label_workspace_bytes(uint64_t rows) { return label_layout(rows).total; }
 
 static dim3 sweep_grid(const LabelCloud& c) {
     return dim3((unsigned)(((uint64_t)c.max_sweep + kLabelThreads - 1) / kLabelThreads), (unsigned)(c.sweep_offsets ? c.n_sweeps : 1));
 }
 
 // c.rows_per_point = 1 (a row a point) or `cameras` (a row per (point, camera)); c.n rows_per_point < 2^31
-hipError_t lidar_label_decide(const LabelCloud& c, const SrLabelView* views, int cameras, int check_range, bool mirrored, const uint8_t* lut, void* ws,
+static hipError_t lidar_label_decide(const LabelCloud& c, const SrLabelView* views, int cameras, int check_range, bool mirrored, const uint8_t* lut, void* ws,
                               uint64_t* counts, hipStream_t s) {
     const uint64_t total = (uint64_t)c.n * (uint64_t)c.rows_per_point;
     const LabelLayout L = label_layout(total);
@@ -290,7 +304,7 @@ hipError_t lidar_label_decide(const LabelCloud& c, const SrLabelView* views, int
     return exclusive_scan_in_place(flags, (uint32_t)total, at<uint32_t>(ws, L.chunks), reinterpret_cast<uint32_t*>(counts), s);   // the low word: little-endian
 }
 
-hipError_t lidar_vote(const LabelCloud& c, const SrLabelView* views, int n_views, int n_classes, const uint8_t* lut, void* ws, uint8_t* valid_mask,
+static hipError_t lidar_vote(const LabelCloud& c, const SrLabelView* views, int n_views, int n_classes, const uint8_t* lut, void* ws, uint8_t* valid_mask,
                       uint64_t* counts, hipStream_t s) {
     const LabelLayout L = label_layout(c.n);
     unsigned long long* rows = at<unsigned long long>(ws, L.rows);
@@ -306,7 +320,7 @@ hipError_t lidar_vote(const LabelCloud& c, const SrLabelView* views, int n_views
 }
 
 // n_rows >= 1
-hipError_t lidar_label_emit(const LabelCloud& c, const void* ws, uint32_t n_rows, void* out_xyz, double* out_rgb, int32_t* out_semantics, int64_t* out_index,
+static hipError_t lidar_label_emit(const LabelCloud& c, const void* ws, uint32_t n_rows, void* out_xyz, double* out_rgb, int32_t* out_semantics, int64_t* out_index,
                             int32_t* rows_per_sweep, hipStream_t s) {
     const uint64_t total = (uint64_t)c.n * (uint64_t)c.rows_per_point;
     const LabelLayout L = label_layout(total);
@@ -322,3 +336,101 @@ hipError_t lidar_label_emit(const LabelCloud& c, const void* ws, uint32_t n_rows
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks the three launching sr_lidar_* calls share: the cloud, the view table and the workspace of n * rows_per_point rows
+static int lidar_arguments(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, const uint8_t* label_lut,
+                           int32_t rows_per_point, const void* workspace, size_t workspace_bytes, bool needs_views) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n %d is negative", n);
+    if (int rc = check_f32_or_f64("points", nullptr, points_f64)) return rc;   // the flag; the address once there are points
+    if (rows_per_point < 1 || rows_per_point > kLabelMaxCameras)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%d rows a point: 1..%d", rows_per_point, kLabelMaxCameras);
+    if ((uint64_t)n * (uint64_t)rows_per_point >= (1ull << 31))
+        return fail(SR_ERR_UNSUPPORTED, "%d points x %d rows: fewer than 2^31 rows a call (fewer sweeps a call)", n, rows_per_point);
+    if (needs_views) {
+        if (n_views < 1 || n_views > kLabelMaxViews) return fail(SR_ERR_INVALID_ARGUMENT, "n_views = %d: 1..%d", n_views, kLabelMaxViews);
+        if (!views) return fail(SR_ERR_INVALID_ARGUMENT, "views is NULL");
+        if ((uintptr_t)views & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "views is not 8-B aligned");
+        (void)label_lut;       // 256 device bytes or NULL: nothing to check on the host
+    }
+    if (n == 0) return SR_OK;
+    if (!points) return fail(SR_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (int rc = check_f32_or_f64("points", points, points_f64)) return rc;
+    return check_workspace(workspace, workspace_bytes, lidar_label_workspace_bytes((uint64_t)n * (uint64_t)rows_per_point));
+}
+
+static int lidar_sweeps(int32_t n, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points) {
+    if (n_sweeps < 1 || n_sweeps > kLabelMaxViews) return fail(SR_ERR_INVALID_ARGUMENT, "n_sweeps = %d: 1..%d", n_sweeps, kLabelMaxViews);
+    if ((uintptr_t)sweep_offsets & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "sweep_offsets is not 4-B aligned");
+    if (!sweep_offsets && n_sweeps != 1) return fail(SR_ERR_INVALID_ARGUMENT, "sweep_offsets is NULL with %d sweeps", n_sweeps);
+    if (max_sweep_points < 0 || max_sweep_points > n) return fail(SR_ERR_INVALID_ARGUMENT, "max_sweep_points = %d: not in 0..n = %d", max_sweep_points, n);
+    if (n > 0 && max_sweep_points < 1) return fail(SR_ERR_INVALID_ARGUMENT, "max_sweep_points = 0 with %d points", n);
+    return SR_OK;
+}
+
+extern "C" {
+
+size_t sr_lidar_label_workspace_bytes(int32_t n, int32_t rows_per_point) {
+    if (n < 0 || rows_per_point < 1 || rows_per_point > kLabelMaxCameras || (uint64_t)n * (uint64_t)rows_per_point >= (1ull << 31)) return 0;
+    return lidar_label_workspace_bytes((uint64_t)n * (uint64_t)rows_per_point);
+}
+
+int sr_lidar_label_decide(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                          const void* views, int32_t n_views, int32_t cameras_per_sweep, int32_t check_range, int32_t fourth_corner,
+                          const uint8_t* label_lut, int32_t per_view, void* workspace, size_t workspace_bytes, uint64_t* counts, void* stream) {
+    if (cameras_per_sweep < 1 || cameras_per_sweep > kLabelMaxCameras)
+        return fail(SR_ERR_INVALID_ARGUMENT, "cameras_per_sweep = %d: 1..%d", cameras_per_sweep, kLabelMaxCameras);
+    if (per_view != 0 && per_view != 1) return fail(SR_ERR_INVALID_ARGUMENT, "per_view = %d: 0 or 1", per_view);
+    const int32_t rows_per_point = per_view ? cameras_per_sweep : 1;
+    if (int rc = lidar_arguments(n, points, points_f64, views, n_views, label_lut, rows_per_point, workspace, workspace_bytes, true)) return rc;
+    if (int rc = lidar_sweeps(n, sweep_offsets, n_sweeps, max_sweep_points)) return rc;
+    if ((int64_t)n_sweeps * cameras_per_sweep > n_views)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%d sweeps x %d cameras > %d views", n_sweeps, cameras_per_sweep, n_views);
+    if (check_range < 0) return fail(SR_ERR_INVALID_ARGUMENT, "check_range %d is negative", check_range);
+    if (fourth_corner != 0 && fourth_corner != 1) return fail(SR_ERR_INVALID_ARGUMENT, "fourth_corner = %d: 0 (the reference's column) or 1 (mirrored)", fourth_corner);
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s)); return SR_OK; }
+    const LabelCloud c{(uint32_t)n, points, points_f64, sweep_offsets, n_sweeps, (uint32_t)max_sweep_points, rows_per_point};
+    SR_HIP(lidar_label_decide(c, static_cast<const SrLabelView*>(views), cameras_per_sweep, check_range, fourth_corner == 1, label_lut, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_lidar_label_emit(int32_t n, const void* points, int32_t points_f64, const int32_t* sweep_offsets, int32_t n_sweeps, int32_t max_sweep_points,
+                        int32_t rows_per_point, void* workspace, size_t workspace_bytes, int32_t n_rows, void* out_xyz, double* out_rgb,
+                        int32_t* out_semantics, int64_t* out_index, int32_t* rows_per_sweep, void* stream) {
+    if (int rc = lidar_arguments(n, points, points_f64, nullptr, 0, nullptr, rows_per_point, workspace, workspace_bytes, false)) return rc;
+    if (int rc = lidar_sweeps(n, sweep_offsets, n_sweeps, max_sweep_points)) return rc;
+    if (n_rows < 0 || (int64_t)n_rows > (int64_t)n * rows_per_point)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_rows = %d: not in 0..%lld", n_rows, (long long)n * rows_per_point);
+    if ((uintptr_t)out_xyz & (points_f64 ? 7u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "out_xyz is not aligned to the points' element size");
+    if (((uintptr_t)out_rgb | (uintptr_t)out_index) & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "out_rgb or out_index is not 8-B aligned");
+    if (((uintptr_t)out_semantics | (uintptr_t)rows_per_sweep) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "out_semantics or rows_per_sweep is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_rows == 0) {
+        if (rows_per_sweep) SR_HIP(hipMemsetAsync(rows_per_sweep, 0, sizeof(int32_t) * (size_t)n_sweeps, s));
+        return SR_OK;
+    }
+    const LabelCloud c{(uint32_t)n, points, points_f64, sweep_offsets, n_sweeps, (uint32_t)max_sweep_points, rows_per_point};
+    SR_HIP(lidar_label_emit(c, workspace, (uint32_t)n_rows, out_xyz, out_rgb, out_semantics, out_index, rows_per_sweep, s));
+    return SR_OK;
+}
+
+int sr_lidar_vote(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, int32_t n_classes, const uint8_t* label_lut,
+                  void* workspace, size_t workspace_bytes, uint8_t* valid_mask, uint64_t* counts, void* stream) {
+    if (int rc = lidar_arguments(n, points, points_f64, views, n_views, label_lut, 1, workspace, workspace_bytes, true)) return rc;
+    if (n_classes < 1 || n_classes > kLabelMaxClasses) return fail(SR_ERR_INVALID_ARGUMENT, "n_classes = %d: 1..%d", n_classes, kLabelMaxClasses);
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s)); return SR_OK; }
+    if (!valid_mask) return fail(SR_ERR_INVALID_ARGUMENT, "valid_mask is NULL");
+    const LabelCloud c{(uint32_t)n, points, points_f64, nullptr, 1, (uint32_t)n, 1};
+    SR_HIP(lidar_vote(c, static_cast<const SrLabelView*>(views), n_views, n_classes, label_lut, workspace, valid_mask, counts, s));
+    return SR_OK;
+}
+
+}  // extern "C"

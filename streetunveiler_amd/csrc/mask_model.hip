@@ -14,7 +14,7 @@
 // as its output (one source, pitch == row_len, 16-B aligned pointers) is read 16 B per lane too -- the delta only where all four rows
 // of the group are selected.  Everything else (the SH halves, whose rows of 3, 27 or 45 floats end anywhere; a tensor that starts off a
 // 16-B boundary) moves as scalars.
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
 
@@ -167,10 +167,9 @@ struct TableBuilder {
     }
 };
 
-}  // namespace
-
 bool mask_model_supported(int P, int M) { return (unsigned long long)P * 3ull * (unsigned long long)M < 0x7FFFFFFFull; }
 
+// a NULL output / gradient pointer is skipped; a delta whose SR_MASK_FIXED_* bit is set is not read
 hipError_t launch_mask_compose(int P, int M, const SrMaskTensors& base, const SrMaskTensors& delta, const uint8_t* mask, uint32_t fixed_bits,
                                const SrMaskEffective& out, hipStream_t stream) {
     const uint32_t rest = 3u * (uint32_t)(M - 1);
@@ -200,4 +199,84 @@ hipError_t launch_mask_compose_backward(int P, int M, const SrMaskEffective& ups
     return b.launch<true>(mask, stream);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+namespace {
+
+// shared refusals of the two masked-model calls; *work = 0: nothing to do
+int mask_model_args(int32_t P, int32_t sh_coeffs, const uint8_t* mask, uint32_t fixed_bits, int* work) {
+    *work = 0;
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (sh_coeffs < 1) return fail(SR_ERR_INVALID_ARGUMENT, "sh_coeffs %d < 1", sh_coeffs);
+    if (fixed_bits > 63u) return fail(SR_ERR_INVALID_ARGUMENT, "fixed_bits %u has bits beyond the six properties", fixed_bits);
+    if (P == 0) return SR_OK;
+    if (!mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (!mask_model_supported(P, sh_coeffs)) return fail(SR_ERR_UNSUPPORTED, "P * 3 * sh_coeffs = %d * 3 * %d reaches 2^31", P, sh_coeffs);
+    *work = 1;
+    return SR_OK;
+}
+
+int mask_pointer(const char* group, const char* name, const void* p, bool required) {
+    if (!p && required) return fail(SR_ERR_INVALID_ARGUMENT, "%s.%s is NULL", group, name);
+    if ((uintptr_t)p & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "%s.%s is not 4-B aligned", group, name);
+    return SR_OK;
+}
+
+const char* const kMaskNames[6] = {"xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"};
+const uint32_t kMaskBits[6] = {SR_MASK_FIXED_XYZ, SR_MASK_FIXED_FEATURES_DC, SR_MASK_FIXED_FEATURES_REST, SR_MASK_FIXED_OPACITY, SR_MASK_FIXED_SCALING,
+                               SR_MASK_FIXED_ROTATION};
+
+}  // namespace
+
+extern "C" {
+
+int sr_mask_compose(int32_t P, int32_t sh_coeffs, const SrMaskTensors* base, const SrMaskTensors* delta, const uint8_t* mask,
+                    uint32_t fixed_bits, const SrMaskEffective* out, void* stream) {
+    int work;
+    if (int rc = mask_model_args(P, sh_coeffs, mask, fixed_bits, &work)) return rc;
+    if (!work) return SR_OK;
+    if (!base || !delta || !out) return fail(SR_ERR_INVALID_ARGUMENT, "base / delta / out is NULL");
+    const float* b[6] = {base->xyz, base->features_dc, base->features_rest, base->opacity, base->scaling, base->rotation};
+    const float* d[6] = {delta->xyz, delta->features_dc, delta->features_rest, delta->opacity, delta->scaling, delta->rotation};
+    for (int k = 0; k < 6; ++k) {
+        const bool empty = k == 2 && sh_coeffs == 1;   // features_rest of SH degree 0
+        if (int rc = mask_pointer("base", kMaskNames[k], b[k], !empty)) return rc;
+        if (int rc = mask_pointer("delta", kMaskNames[k], d[k], !empty && !(fixed_bits & kMaskBits[k]))) return rc;
+    }
+    const uint32_t both = SR_MASK_FIXED_FEATURES_DC | SR_MASK_FIXED_FEATURES_REST;
+    const float* o[5] = {out->xyz, out->features, out->opacity, out->scaling, out->rotation};
+    const char* names[5] = {"xyz", "features", "opacity", "scaling", "rotation"};
+    const bool fixed[5] = {(fixed_bits & SR_MASK_FIXED_XYZ) != 0, (fixed_bits & both) == both, (fixed_bits & SR_MASK_FIXED_OPACITY) != 0,
+                           (fixed_bits & SR_MASK_FIXED_SCALING) != 0, (fixed_bits & SR_MASK_FIXED_ROTATION) != 0};
+    for (int k = 0; k < 5; ++k)
+        if (int rc = mask_pointer("out", names[k], o[k], !fixed[k])) return rc;
+    SR_HIP(launch_mask_compose(P, sh_coeffs, *base, *delta, mask, fixed_bits, *out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_mask_compose_backward(int32_t P, int32_t sh_coeffs, const SrMaskEffective* upstream, const uint8_t* mask, uint32_t fixed_bits,
+                             const SrMaskTensors* d_delta, void* stream) {
+    int work;
+    if (int rc = mask_model_args(P, sh_coeffs, mask, fixed_bits, &work)) return rc;
+    if (!work) return SR_OK;
+    if (!upstream || !d_delta) return fail(SR_ERR_INVALID_ARGUMENT, "upstream / d_delta is NULL");
+    const float* d[6] = {d_delta->xyz, d_delta->features_dc, d_delta->features_rest, d_delta->opacity, d_delta->scaling, d_delta->rotation};
+    const float* g[6] = {upstream->xyz, upstream->features, upstream->features, upstream->opacity, upstream->scaling, upstream->rotation};
+    const char* from[6] = {"xyz", "features", "features", "opacity", "scaling", "rotation"};
+    for (int k = 0; k < 6; ++k) {
+        if (int rc = mask_pointer("d_delta", kMaskNames[k], d[k], false)) return rc;
+        if (int rc = mask_pointer("upstream", from[k], g[k], false)) return rc;
+        if (!d[k] || (k == 2 && sh_coeffs == 1)) continue;
+        if (fixed_bits & kMaskBits[k]) return fail(SR_ERR_INVALID_ARGUMENT, "d_delta.%s is asked for, but the property is fixed", kMaskNames[k]);
+        if (!g[k]) return fail(SR_ERR_INVALID_ARGUMENT, "d_delta.%s is asked for without upstream.%s", kMaskNames[k], from[k]);
+    }
+    SR_HIP(launch_mask_compose_backward(P, sh_coeffs, *upstream, mask, *d_delta, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

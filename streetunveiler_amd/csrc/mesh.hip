@@ -14,7 +14,7 @@
 #include <cmath>
 
 #include "contraction.h"
-#include "launch.h"
+#include "abi.h"
 #include "mc_table.h"
 #include "scan.h"
 
@@ -24,6 +24,15 @@ constexpr int kMeshThreads = 256;
 constexpr int kMeshRows = 16;                              // rows of kMeshThreads consecutive points a block walks
 constexpr int kMeshChunk = kMeshThreads * kMeshRows;       // 4096 points: at most 12288 vertices and 20480 triangles, 16 bits each
 constexpr int kMeshScanThreads = 1024;
+
+struct MeshGrid {          // kernel parameters, by value
+    int nx, ny, nz;        // every axis at least 2 (a grid without cells never reaches a launch)
+    uint32_t n;            // nx ny nz < 2^31
+    float level;
+};
+struct MeshFrame {         // grid point (ix, iy, iz) sits at fmaf(index, step, lo) per axis
+    float lo[3], step[3];
+};
 
 struct MeshLayout {
     size_t offsets, flags, chunks, total;
@@ -39,7 +48,7 @@ static MeshLayout mesh_layout(uint32_t n) {
     L.total = c.off;
     return L;
 }
-size_t mesh_workspace_bytes(uint32_t n) { return mesh_layout(n).total; }
+static size_t mesh_workspace_bytes(uint32_t n) { return mesh_layout(n).total; }
 
 __device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // (a NaN compares false)
 
@@ -196,7 +205,8 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_faces_kernel(const float* _
     }
 }
 
-hipError_t mesh_count(const float* volume, const MeshGrid& g, void* workspace, uint32_t* counts, hipStream_t s) {
+// counts: device {Nv, Nf}; a count is 0xFFFFFFFF where Nv or 3 Nf is beyond int32
+static hipError_t mesh_count(const float* volume, const MeshGrid& g, void* workspace, uint32_t* counts, hipStream_t s) {
     const MeshLayout L = mesh_layout(g.n);
     uint4* chunks = at<uint4>(workspace, L.chunks);
     hipLaunchKernelGGL(mesh_count_kernel, dim3(L.nchunks), dim3(kMeshThreads), 0, s, volume, g, chunks);
@@ -204,7 +214,8 @@ hipError_t mesh_count(const float* volume, const MeshGrid& g, void* workspace, u
     return hipGetLastError();
 }
 
-hipError_t mesh_emit(const float* volume, const MeshGrid& g, const MeshFrame& frame, const TsdfSpace& space, void* workspace, uint32_t n_vertices,
+// after mesh_count on the same volume, level and workspace; space.contract: the vertices are un-contracted and un-normalised
+static hipError_t mesh_emit(const float* volume, const MeshGrid& g, const MeshFrame& frame, const TsdfSpace& space, void* workspace, uint32_t n_vertices,
                      uint32_t n_faces, float* vertices, int32_t* faces, hipStream_t s) {
     const MeshLayout L = mesh_layout(g.n);
     const uint4* chunks = at<uint4>(workspace, L.chunks);
@@ -218,3 +229,65 @@ hipError_t mesh_emit(const float* volume, const MeshGrid& g, const MeshFrame& fr
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks sr_mesh_count and sr_mesh_emit share -> the kernels' view of the grid; *cells = 0 for a grid with an axis of length 1
+static int mesh_arguments(const float* volume, const int32_t* dims, float level, const void* workspace, size_t workspace_bytes, MeshGrid* g, bool* cells) {
+    if (!volume) return fail(SR_ERR_INVALID_ARGUMENT, "volume is NULL");
+    if (!dims) return fail(SR_ERR_INVALID_ARGUMENT, "dims is NULL");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return fail(SR_ERR_INVALID_ARGUMENT, "dims %d x %d x %d: every axis holds at least one sample", dims[0], dims[1], dims[2]);
+    if (level != level) return fail(SR_ERR_INVALID_ARGUMENT, "level is NaN");
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];   // < 2^62: the product below cannot wrap
+    const unsigned long long n = plane < (1ull << 31) ? plane * (unsigned long long)dims[2] : plane;
+    if (n >= (1ull << 31))
+        return fail(SR_ERR_UNSUPPORTED, "a grid of %d x %d x %d points: fewer than 2^31", dims[0], dims[1], dims[2]);
+    // (a short workspace is an invalid argument here, not SR_ERR_BUFFER_TOO_SMALL as everywhere else: what these two calls have always returned)
+    if (int rc = check_workspace(workspace, workspace_bytes, mesh_workspace_bytes((uint32_t)n), SR_ERR_INVALID_ARGUMENT)) return rc;
+    if ((uintptr_t)volume & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "volume is not 4-B aligned");
+    *g = MeshGrid{dims[0], dims[1], dims[2], (uint32_t)n, level};
+    *cells = dims[0] > 1 && dims[1] > 1 && dims[2] > 1;
+    return SR_OK;
+}
+
+extern "C" {
+
+size_t sr_mesh_workspace_bytes(const int32_t* dims) {
+    if (!dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return 0;
+    const unsigned long long plane = (unsigned long long)dims[0] * (unsigned long long)dims[1];
+    if (plane >= (1ull << 31) || plane * (unsigned long long)dims[2] >= (1ull << 31)) return 0;
+    return mesh_workspace_bytes((uint32_t)(plane * (unsigned long long)dims[2]));
+}
+
+int sr_mesh_count(const float* volume, const int32_t* dims, float level, void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    MeshGrid g; bool cells;
+    if (int rc = mesh_arguments(volume, dims, level, workspace, workspace_bytes, &g, &cells)) return rc;
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!cells) { SR_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s)); return SR_OK; }
+    SR_HIP(mesh_count(volume, g, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_mesh_emit(const float* volume, const int32_t* dims, float level, const float* lo, const float* step, const SrTsdfSpace* space,
+                 void* workspace, size_t workspace_bytes, int32_t n_vertices, int32_t n_faces, float* vertices, int32_t* faces, void* stream) {
+    MeshGrid g; bool cells;
+    if (int rc = mesh_arguments(volume, dims, level, workspace, workspace_bytes, &g, &cells)) return rc;
+    if (!lo || !step) return fail(SR_ERR_INVALID_ARGUMENT, "lo / step is NULL");
+    if (n_vertices < 0 || n_faces < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n_vertices %d / n_faces %d is negative", n_vertices, n_faces);
+    if (n_faces > 0x7FFFFFFF / 3) return fail(SR_ERR_UNSUPPORTED, "%d faces: 3 n_faces does not fit in int32", n_faces);
+    if (n_faces > 0 && n_vertices == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices", n_faces);
+    if (n_vertices > 0 && !vertices) return fail(SR_ERR_INVALID_ARGUMENT, "vertices is NULL");
+    if (n_faces > 0 && !faces) return fail(SR_ERR_INVALID_ARGUMENT, "faces is NULL");
+    if (((uintptr_t)vertices | (uintptr_t)faces) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "vertices / faces is not 4-B aligned");
+    if (!cells || n_vertices == 0) return SR_OK;
+    const MeshFrame frame{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}};
+    TsdfSpace sp{0.f, 0, {0.f, 0.f, 0.f}, 1.f};
+    if (space && space->contract) sp = TsdfSpace{0.f, 1, {space->center[0], space->center[1], space->center[2]}, space->radius};
+    SR_HIP(mesh_emit(volume, g, frame, sp, workspace, (uint32_t)n_vertices, (uint32_t)n_faces, vertices, faces, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

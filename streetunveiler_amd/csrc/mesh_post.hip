@@ -18,7 +18,7 @@
 //
 // A face with an index outside [0, nv) is never used to address anything: it takes part in no bucket, stays a component of its own, is
 // never kept, and is counted.  Integer / latency work only; no LDS beyond the scans', no MFMA.
-#include "launch.h"
+#include "abi.h"
 #include "scan.h"
 #include "union_find.h"
 
@@ -46,7 +46,7 @@ static MeshPostLayout mesh_post_layout(int nv, int nf) {
     L.total = c.off;
     return L;
 }
-size_t mesh_post_workspace_bytes(int nv, int nf) { return mesh_post_layout(nv, nf).total; }
+static size_t mesh_post_workspace_bytes(int nv, int nf) { return mesh_post_layout(nv, nf).total; }
 
 // ---- an exclusive scan of n < 2^31 words in place: the sums of the chunks, their scan by one block, the chunks again with their bases ----
 __global__ __launch_bounds__(kPostThreads) void post_chunk_sums_kernel(const uint32_t* __restrict__ data, uint32_t n, uint32_t* __restrict__ chunk_sum) {
@@ -232,8 +232,8 @@ __global__ __launch_bounds__(kPostThreads) void post_faces_kernel(const int32_t*
 
 static dim3 post_grid(long long n) { return dim3((unsigned)((n + kPostThreads - 1) / kPostThreads)); }
 
-// nv, nf >= 1, 3 nf <= INT32_MAX (api.hip)
-hipError_t mesh_components(const int32_t* faces, int nv, int nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* ws, hipStream_t s) {
+// nv, nf >= 1, 3 nf <= INT32_MAX (mesh_post_arguments)
+static hipError_t mesh_components(const int32_t* faces, int nv, int nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* ws, hipStream_t s) {
     const MeshPostLayout L = mesh_post_layout(nv, nf);
     uint32_t* cursor = at<uint32_t>(ws, L.vert);
     uint2* entries = at<uint2>(ws, L.edge);
@@ -255,7 +255,7 @@ hipError_t mesh_components(const int32_t* faces, int nv, int nf, int32_t* labels
 }
 
 // nv, nf >= 1; counts: device {nv_out, nf_out, n_out_of_range}
-hipError_t mesh_filter_count(const int32_t* faces, int nv, int nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold, void* ws,
+static hipError_t mesh_filter_count(const int32_t* faces, int nv, int nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold, void* ws,
                              uint32_t* counts, hipStream_t s) {
     const MeshPostLayout L = mesh_post_layout(nv, nf);
     uint32_t* vertex_map = at<uint32_t>(ws, L.vert);
@@ -272,7 +272,7 @@ hipError_t mesh_filter_count(const int32_t* faces, int nv, int nf, const int32_t
 }
 
 // after mesh_filter_count on the same faces and workspace, with the counts it left; nv, nf, nv_out >= 1
-hipError_t mesh_filter_emit(const int32_t* faces, int nv, int nf, const float* vertices, const float* colors, void* ws, uint32_t nv_out, uint32_t nf_out,
+static hipError_t mesh_filter_emit(const int32_t* faces, int nv, int nf, const float* vertices, const float* colors, void* ws, uint32_t nv_out, uint32_t nf_out,
                             float* vertices_out, float* colors_out, int32_t* faces_out, hipStream_t s) {
     const MeshPostLayout L = mesh_post_layout(nv, nf);
     const uint32_t* vertex_map = at<uint32_t>(ws, L.vert);
@@ -285,3 +285,72 @@ hipError_t mesh_filter_emit(const int32_t* faces, int nv, int nf, const float* v
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks the three sr_mesh_* post-processing calls share; *work = 0 for a mesh without faces or without vertices
+static int mesh_post_arguments(const int32_t* faces, int32_t nv, int32_t nf, const void* workspace, size_t workspace_bytes, bool* work) {
+    if (nv < 0 || nf < 0) return fail(SR_ERR_INVALID_ARGUMENT, "nv %d / nf %d is negative", nv, nf);
+    if (nf > 0x7FFFFFFF / 3) return fail(SR_ERR_UNSUPPORTED, "%d faces: 3 nf does not fit in int32 (process the mesh in parts)", nf);
+    *work = nv > 0 && nf > 0;
+    if (!*work) return SR_OK;
+    if (!faces) return fail(SR_ERR_INVALID_ARGUMENT, "faces is NULL");
+    if ((uintptr_t)faces & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "faces is not 4-B aligned");
+    return check_workspace(workspace, workspace_bytes, mesh_post_workspace_bytes(nv, nf));
+}
+
+extern "C" {
+
+size_t sr_mesh_post_workspace_bytes(int32_t nv, int32_t nf) {
+    if (nv < 0 || nf < 0 || nf > 0x7FFFFFFF / 3) return 0;
+    return mesh_post_workspace_bytes(nv, nf);
+}
+
+int sr_mesh_components(const int32_t* faces, int32_t nv, int32_t nf, int32_t* labels, int32_t* sizes, uint32_t* n_out_of_range, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (!n_out_of_range) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is NULL");
+    if (nf > 0 && nv > 0 && (!labels || !sizes)) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes is NULL");
+    if (((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)n_out_of_range) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes / n_out_of_range is not 4-B aligned");
+    if (nf == 0) return SR_OK;      // no face: nothing to label, nothing out of range, no work
+    if (nv == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices: every index is out of range", nf);
+    SR_HIP(mesh_components(faces, nv, nf, labels, sizes, n_out_of_range, workspace, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_mesh_filter_count(const int32_t* faces, int32_t nv, int32_t nf, const int32_t* labels, const int32_t* sizes, const int32_t* threshold,
+                         void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) { SR_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s)); return SR_OK; }
+    if (!labels || !sizes) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes is NULL");
+    if (!threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NULL");
+    if (((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)threshold) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "labels / sizes / threshold is not 4-B aligned");
+    SR_HIP(mesh_filter_count(faces, nv, nf, labels, sizes, threshold, workspace, counts, s));
+    return SR_OK;
+}
+
+int sr_mesh_filter_emit(const int32_t* faces, int32_t nv, int32_t nf, const float* vertices, const float* colors, void* workspace,
+                        size_t workspace_bytes, int32_t nv_out, int32_t nf_out, float* vertices_out, float* colors_out, int32_t* faces_out, void* stream) {
+    bool work;
+    if (int rc = mesh_post_arguments(faces, nv, nf, workspace, workspace_bytes, &work)) return rc;
+    if (nv_out < 0 || nf_out < 0) return fail(SR_ERR_INVALID_ARGUMENT, "nv_out %d / nf_out %d is negative", nv_out, nf_out);
+    if (nv_out > nv || nf_out > nf) return fail(SR_ERR_INVALID_ARGUMENT, "nv_out %d / nf_out %d: more than the %d vertices / %d faces that came in", nv_out, nf_out, nv, nf);
+    if (nf_out > 0 && nv_out == 0) return fail(SR_ERR_INVALID_ARGUMENT, "%d faces without vertices", nf_out);
+    if (nv_out > 0 && (!vertices || !vertices_out)) return fail(SR_ERR_INVALID_ARGUMENT, "vertices / vertices_out is NULL");
+    if (nv_out > 0 && colors && !colors_out) return fail(SR_ERR_INVALID_ARGUMENT, "colors_out is NULL (colors is given)");
+    if (nf_out > 0 && !faces_out) return fail(SR_ERR_INVALID_ARGUMENT, "faces_out is NULL");
+    if (((uintptr_t)vertices | (uintptr_t)colors | (uintptr_t)vertices_out | (uintptr_t)colors_out | (uintptr_t)faces_out) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "vertices / colors / vertices_out / colors_out / faces_out is not 4-B aligned");
+    if (!work || nv_out == 0) return SR_OK;
+    SR_HIP(mesh_filter_emit(faces, nv, nf, vertices, colors, workspace, (uint32_t)nv_out, (uint32_t)nf_out, vertices_out, colors_out, faces_out,
+                            static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@
 // search over the (at most 8) first-chunk numbers of the table -- selects over wave-uniform values, no private array, nothing indexed
 // with a run-time value.  A tensor whose four pointers are all 16-B aligned moves as dwordx4 (its n mod 4 tail as scalars); one that is
 // not moves as coalesced scalars.
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
 
@@ -188,11 +188,6 @@ bool adam_chunks_fit(const Segment* segments, int n_segments) {
     return chunks < 0x7FFFFFFFull;
 }
 
-}  // namespace
-
-bool adam_supported(const SrAdamSegment* segments, int n_segments) { return adam_chunks_fit(segments, n_segments); }
-bool adam_rows_supported(const SrAdamRowSegment* segments, int n_segments) { return adam_chunks_fit(segments, n_segments); }
-
 hipError_t launch_adam_step(const SrAdamSegment* segments, int n_segments, double beta1, double beta2, double eps, hipStream_t stream) {
     AdamLaunch l;
     for (int k = 0; k < n_segments; ++k) {
@@ -212,6 +207,8 @@ hipError_t launch_adam_step_rows(const SrAdamRowSegment* segments, int n_segment
     return l.launch(mask, beta1, beta2, eps, stream);
 }
 
+}  // namespace
+
 // [REF train.py:168-169, scene/gaussian_model.py:555-557] with visibility_filter = radii > 0: rows of invisible Gaussians are neither
 // read (their gradient row may hold anything) nor written.
 __global__ __launch_bounds__(256) void densification_stats_kernel(int P, const float* __restrict__ viewspace_grad, const int* __restrict__ radii,
@@ -227,12 +224,84 @@ __global__ __launch_bounds__(256) void densification_stats_kernel(int P, const f
     max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
 }
 
-hipError_t launch_densification_stats(int P, const float* viewspace_grad, const int* radii, float* xyz_gradient_accum, float* denom,
-                                      float* max_radii2D, hipStream_t stream) {
-    if (P == 0) return hipSuccess;
-    hipLaunchKernelGGL(densification_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, viewspace_grad, radii,
-                       xyz_gradient_accum, denom, max_radii2D);
-    return hipGetLastError();
+}  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the refusals the two Adam calls share: the hyper-parameters ...
+static int adam_hyper(double beta1, double beta2, double eps) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta1 %g not in [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(SR_ERR_INVALID_ARGUMENT, "beta2 %g not in [0, 1)", beta2);
+    if (!(eps >= 0.0)) return fail(SR_ERR_INVALID_ARGUMENT, "eps %g is negative", eps);
+    return SR_OK;
+}
+// ... and the four arrays of segment k
+template <class Segment>
+static int adam_pointers(int k, const Segment& a) {
+    const void* ptrs[4] = {a.param, a.grad, a.exp_avg, a.exp_avg_sq};
+    const char* names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+    for (int j = 0; j < 4; ++j) {
+        if (!ptrs[j]) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is NULL", k, names[j]);
+        if ((uintptr_t)ptrs[j] & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: %s is not 4-B aligned", k, names[j]);
+    }
+    return SR_OK;
 }
 
-}  // namespace sr
+extern "C" {
+
+int sr_adam_step(const SrAdamSegment* segments, int32_t n_segments, double beta1, double beta2, double eps, void* stream) {
+    if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 1..%d", n_segments, SR_ADAM_MAX_SEGMENTS);
+    if (int rc = adam_hyper(beta1, beta2, eps)) return rc;
+    for (int k = 0; k < n_segments; ++k) {
+        const SrAdamSegment& a = segments[k];
+        if (a.n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: n %lld is negative", k, (long long)a.n);
+        if (int rc = adam_pointers(k, a)) return rc;
+    }
+    if (!adam_chunks_fit(segments, n_segments)) return fail(SR_ERR_UNSUPPORTED, "the segments hold more than 2^31 chunks of %d elements", SR_ADAM_CHUNK);
+    SR_HIP(launch_adam_step(segments, n_segments, beta1, beta2, eps, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_adam_step_rows(const SrAdamRowSegment* segments, int32_t n_segments, int32_t P, const uint8_t* mask, double beta1, double beta2,
+                      double eps, void* stream) {
+    if (!segments) return fail(SR_ERR_INVALID_ARGUMENT, "segments is NULL");
+    if (n_segments < 1 || n_segments > SR_ADAM_MAX_SEGMENTS)
+        return fail(SR_ERR_INVALID_ARGUMENT, "n_segments %d not in 1..%d", n_segments, SR_ADAM_MAX_SEGMENTS);
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P > 0 && !mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (int rc = adam_hyper(beta1, beta2, eps)) return rc;
+    for (int k = 0; k < n_segments; ++k) {
+        const SrAdamRowSegment& a = segments[k];
+        if (a.row_len < 1 || a.row_len >= (1ll << 30)) return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: row_len %lld not in [1, 2^30)", k, (long long)a.row_len);
+        if (a.n != (int64_t)P * a.row_len)
+            return fail(SR_ERR_INVALID_ARGUMENT, "segment %d: n %lld is not P * row_len = %d * %lld", k, (long long)a.n, P, (long long)a.row_len);
+        if (a.n == 0) continue;
+        if (int rc = adam_pointers(k, a)) return rc;
+    }
+    if (P == 0) return SR_OK;
+    if (!adam_chunks_fit(segments, n_segments)) return fail(SR_ERR_UNSUPPORTED, "the segments hold more than 2^31 chunks of %d elements", SR_ADAM_CHUNK);
+    SR_HIP(launch_adam_step_rows(segments, n_segments, mask, beta1, beta2, eps, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_densification_stats(int32_t P, const float* viewspace_grad, const int32_t* radii, float* xyz_gradient_accum, float* denom,
+                           float* max_radii2D, void* stream) {
+    if (P < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P == 0) return SR_OK;
+    if (!viewspace_grad) return fail(SR_ERR_INVALID_ARGUMENT, "viewspace_grad is NULL");
+    if (!radii) return fail(SR_ERR_INVALID_ARGUMENT, "radii is NULL");
+    if (!xyz_gradient_accum) return fail(SR_ERR_INVALID_ARGUMENT, "xyz_gradient_accum is NULL");
+    if (!denom) return fail(SR_ERR_INVALID_ARGUMENT, "denom is NULL");
+    if (!max_radii2D) return fail(SR_ERR_INVALID_ARGUMENT, "max_radii2D is NULL");
+    if (((uintptr_t)viewspace_grad | (uintptr_t)radii | (uintptr_t)xyz_gradient_accum | (uintptr_t)denom | (uintptr_t)max_radii2D) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "viewspace_grad / radii / xyz_gradient_accum / denom / max_radii2D: a pointer is not 4-B aligned");
+    hipLaunchKernelGGL(densification_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), P, viewspace_grad, radii,
+                       xyz_gradient_accum, denom, max_radii2D);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+}  // extern "C"

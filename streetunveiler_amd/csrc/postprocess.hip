@@ -12,9 +12,17 @@
 // On a rigid camera V3^T and inverse(V3) agree to an ulp; on a scaled 3x3 they differ by the scale squared, and only the rays and the
 // camera position take the inverse.  NaN and +inf depths become 0 (with a zero gradient); -inf is not handled like torch.nan_to_num(x, 0, 0)
 // handles it (that maps it to the lowest finite float, this maps it to 0): depths are never negative, so it never occurs.
-#include "launch.h"   // PostCam
+#include <cmath>
+
+#include "abi.h"
 
 namespace sr {
+
+struct PostCam {         // a kernel parameter, by value
+    int W, H;
+    float fx, fy, depth_ratio;
+    const float* view;   // device [16] world_view_transform (W2C^T, row-major)
+};
 
 // c2w rotation (row-major R[9]) and position from W2C^T: general 3x3 inverse via the adjugate (the reference calls inverse()); for the ray
 // directions and the camera position only -- the normals go through the view matrix itself (rotate_normal / rotate_normal_adjoint)
@@ -173,20 +181,45 @@ __global__ __launch_bounds__(256) void postprocess_backward_gather_kernel(PostCa
 
 static dim3 post_grid(int W, int H) { return dim3((W + 63) / 64, (H + 3) / 4); }
 
-hipError_t launch_postprocess_forward(const PostCam& cam, const float* allmap, float* rend_normal, float* surf_depth,
-                                      float* surf_normal, float* surf_point, hipStream_t s) {
-    hipLaunchKernelGGL(postprocess_forward_kernel, post_grid(cam.W, cam.H), dim3(256), 0, s, cam, allmap, rend_normal, surf_depth,
-                       surf_normal, surf_point);
-    return hipGetLastError();
-}
-
-hipError_t launch_postprocess_backward(const PostCam& cam, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
-                                       const float* g_surf_normal, const float* g_surf_point, float* scratch6, float* g_allmap,
-                                       hipStream_t s) {
-    hipLaunchKernelGGL(postprocess_backward_stencil_kernel, post_grid(cam.W, cam.H), dim3(256), 0, s, cam, allmap, g_surf_normal, scratch6);
-    hipLaunchKernelGGL(postprocess_backward_gather_kernel, post_grid(cam.W, cam.H), dim3(256), 0, s, cam, allmap, g_rend_normal,
-                       g_surf_depth, g_surf_point, scratch6, g_allmap);
-    return hipGetLastError();
-}
-
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+static int post_cam(int32_t W, int32_t H, float fovx, float fovy, float depth_ratio, const float* viewmatrix, PostCam* cam) {
+    if (W <= 0 || H <= 0 || !viewmatrix) return fail(SR_ERR_INVALID_ARGUMENT, "bad image size / NULL viewmatrix");
+    cam->W = W; cam->H = H;
+    cam->fx = (float)W / (2.f * tanf(fovx * 0.5f)); cam->fy = (float)H / (2.f * tanf(fovy * 0.5f));
+    cam->depth_ratio = depth_ratio; cam->view = viewmatrix;
+    return SR_OK;
+}
+
+extern "C" {
+
+int sr_postprocess_forward(int32_t W, int32_t H, float fovx, float fovy, float depth_ratio, const float* viewmatrix,
+                           const float* allmap, float* rend_normal, float* surf_depth, float* surf_normal, float* surf_point,
+                           void* stream) {
+    PostCam cam;
+    if (int rc = post_cam(W, H, fovx, fovy, depth_ratio, viewmatrix, &cam)) return rc;
+    if (!allmap || !rend_normal || !surf_depth || !surf_normal || !surf_point) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
+    hipLaunchKernelGGL(postprocess_forward_kernel, post_grid(W, H), dim3(256), 0, static_cast<hipStream_t>(stream), cam, allmap, rend_normal,
+                       surf_depth, surf_normal, surf_point);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+int sr_postprocess_backward(int32_t W, int32_t H, float fovx, float fovy, float depth_ratio, const float* viewmatrix,
+                            const float* allmap, const float* g_rend_normal, const float* g_surf_depth, const float* g_surf_normal,
+                            const float* g_surf_point, float* scratch6, float* g_allmap, void* stream) {
+    PostCam cam;
+    if (int rc = post_cam(W, H, fovx, fovy, depth_ratio, viewmatrix, &cam)) return rc;
+    if (!allmap || !scratch6 || !g_allmap) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(postprocess_backward_stencil_kernel, post_grid(W, H), dim3(256), 0, s, cam, allmap, g_surf_normal, scratch6);
+    hipLaunchKernelGGL(postprocess_backward_gather_kernel, post_grid(W, H), dim3(256), 0, s, cam, allmap, g_rend_normal, g_surf_depth,
+                       g_surf_point, scratch6, g_allmap);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -13,9 +13,18 @@
 //              workgroups' sets in index order and rounds once.  No atomics: the order of every addition follows from (W, H, the
 //              workgroup count) alone, so two calls on equal inputs give equal bits.
 // relu keeps a NaN (x < 0 ? 0 : x) and its derivative is torch's threshold_backward (h <= 0 ? 0 : g).
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
+
+constexpr int kSkyParams = 64 * 16 + 64 + 2 * (64 * 64 + 64) + 3 * 64 + 3;   // 9603: {W0sh c W1 b1 W2 b2 W3 b3}
+constexpr int kSkyParamsPadded = kSkyParams + 1;
+constexpr int kSkyDefaultForwardGroups = 1024;    // workgroups of 256 pixels where max_workgroups == 0: a few per CU
+constexpr int kSkyDefaultBackwardGroups = 256;    // one per CU: its sums, weights and panels take most of a CU's LDS
+constexpr int kSkyMaxGroups = 1 << 16;
+struct SkyWeights {        // a kernel parameter, by value: device pointers
+    const float *w0sh, *c, *w1, *b1, *w2, *b2, *w3, *b3;
+};
 
 namespace {
 
@@ -299,17 +308,11 @@ int sky_groups(size_t N, int max_workgroups, int fallback) {
     return (int)(need < cap ? need : cap);
 }
 
-}  // namespace
-
 int sky_backward_groups(int max_workgroups) { return max_workgroups > 0 ? max_workgroups : kSkyDefaultBackwardGroups; }
+// the float64 parameter-gradient set of every workgroup of the backward
 size_t sky_workspace_bytes(int max_workgroups) { return align_up((size_t)sky_backward_groups(max_workgroups) * kSkyParams * sizeof(double), 256); }
 
-hipError_t launch_sky_forward(int W, int H, const float* cam, const SkyWeights& p, int max_workgroups, float* out, hipStream_t s) {
-    const size_t N = (size_t)W * (size_t)H;
-    hipLaunchKernelGGL(sky_forward_kernel, dim3(sky_groups(N, max_workgroups, kSkyDefaultForwardGroups)), dim3(kSkyThreads), 0, s, W, N, cam, p, out);
-    return hipGetLastError();
-}
-
+// grads: g_w0sh, g_c, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3; a NULL pointer is skipped
 hipError_t launch_sky_backward(int W, int H, const float* cam, const SkyWeights& p, const float* g_out, int max_workgroups, void* workspace,
                                float* const (&grads)[8], hipStream_t s) {
     const size_t N = (size_t)W * (size_t)H;
@@ -326,4 +329,56 @@ hipError_t launch_sky_backward(int W, int H, const float* cam, const SkyWeights&
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+static int sky_args(const char* what, int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1,
+                    const float* w2, const float* b2, const float* w3, const float* b3, int32_t max_workgroups, SkyWeights* p) {
+    if (W < 0 || H < 0) return fail(SR_ERR_INVALID_ARGUMENT, "%s: bad image size %dx%d", what, W, H);
+    if (max_workgroups < 0 || max_workgroups > kSkyMaxGroups)
+        return fail(SR_ERR_INVALID_ARGUMENT, "%s: max_workgroups %d not in 0..%d", what, max_workgroups, kSkyMaxGroups);
+    if ((int64_t)W * (int64_t)H > 0x7fffffffll) return fail(SR_ERR_UNSUPPORTED, "%s: %dx%d is 2^31 pixels or more", what, W, H);
+    if (!cam || !w0sh || !c || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return fail(SR_ERR_INVALID_ARGUMENT, "%s: cam or a weight pointer is NULL", what);
+    *p = SkyWeights{w0sh, c, w1, b1, w2, b2, w3, b3};
+    return SR_OK;
+}
+
+extern "C" {
+
+size_t sr_sky_workspace_bytes(int32_t max_workgroups) { return max_workgroups >= 0 ? sky_workspace_bytes(max_workgroups) : 0; }
+
+int sr_sky_forward(int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1, const float* w2,
+                   const float* b2, const float* w3, const float* b3, int32_t max_workgroups, float* out, void* stream) {
+    SkyWeights p;
+    if (int rc = sky_args("sr_sky_forward", W, H, cam, w0sh, c, w1, b1, w2, b2, w3, b3, max_workgroups, &p)) return rc;
+    if (W == 0 || H == 0) return SR_OK;
+    if (!out) return fail(SR_ERR_INVALID_ARGUMENT, "sr_sky_forward: out is NULL");
+    const size_t N = (size_t)W * (size_t)H;
+    hipLaunchKernelGGL(sky_forward_kernel, dim3(sky_groups(N, max_workgroups, kSkyDefaultForwardGroups)), dim3(kSkyThreads), 0,
+                       static_cast<hipStream_t>(stream), W, N, cam, p, out);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+int sr_sky_backward(int32_t W, int32_t H, const float* cam, const float* w0sh, const float* c, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* w3, const float* b3, const float* g_out, int32_t max_workgroups, void* workspace,
+                    size_t workspace_bytes, float* g_w0sh, float* g_c, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3,
+                    void* stream) {
+    SkyWeights p;
+    if (int rc = sky_args("sr_sky_backward", W, H, cam, w0sh, c, w1, b1, w2, b2, w3, b3, max_workgroups, &p)) return rc;
+    if (W == 0 || H == 0) return SR_OK;
+    if (!g_out) return fail(SR_ERR_INVALID_ARGUMENT, "sr_sky_backward: g_out is NULL");
+    float* const grads[8] = {g_w0sh, g_c, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+    bool any = false;
+    for (float* g : grads) any = any || g != nullptr;
+    if (!any) return SR_OK;
+    if (int rc = check_workspace_size(workspace, workspace_bytes, sky_workspace_bytes(max_workgroups), "sr_sky_backward")) return rc;
+    SR_HIP(launch_sky_backward(W, H, cam, p, g_out, max_workgroups, workspace, grads, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

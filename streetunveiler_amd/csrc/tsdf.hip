@@ -10,11 +10,21 @@
 #include <cmath>
 
 #include "contraction.h"
-#include "launch.h"
+#include "abi.h"
 
 namespace sr {
 
 constexpr int kTsdfThreads = 256;
+
+struct TsdfViewsDev {      // kernel parameters, by value
+    const float* maps;     // device [V,H,W] depths (channels 1) or [V,H,W,4] (depth, r, g, b) records (channels 4)
+    const float* full_proj;   // device [V,16]
+    int V, H, W, channels;
+};
+struct TsdfGrid {          // sample (ix, iy, iz) = fmaf(index, step, lo) per axis; thread i is ix - ix0 = i / (ny nz), iy, iz
+    float lo[3], step[3];
+    int ny, nz, ix0;
+};
 
 // [REF extract_mesh_unbounded.uncontract, unnormalize; compute_unbounded_tsdf lines 199-204] y in contracted space -> the world point
 // and the truncation of the sample.  The "> 1" test is taken on the norm of the WORLD point, as the reference's line 201 does after
@@ -104,8 +114,9 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_fuse_kernel(const TsdfViews
     if (out_weight) out_weight[i] = weight;
 }
 
-hipError_t launch_tsdf_fuse(const TsdfViewsDev& views, const TsdfSpace& space, const TsdfGrid* grid, int n, const float* samples, float* tsdf,
-                            float* rgb, float* weight, hipStream_t s) {
+// grid == nullptr: the n samples are read from `samples` [n,3]; rgb (with channels 4) and weight may be nullptr
+static hipError_t launch_tsdf_fuse(const TsdfViewsDev& views, const TsdfSpace& space, const TsdfGrid* grid, int n, const float* samples, float* tsdf,
+                                   float* rgb, float* weight, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 blocks((unsigned)(((size_t)n + kTsdfThreads - 1) / kTsdfThreads)), threads(kTsdfThreads);
     const TsdfGrid g = grid ? *grid : TsdfGrid{};
@@ -118,3 +129,56 @@ hipError_t launch_tsdf_fuse(const TsdfViewsDev& views, const TsdfSpace& space, c
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks sr_tsdf_fuse and sr_tsdf_fuse_grid share -> the kernels' view of the arguments
+static int tsdf_arguments(const SrTsdfViews* views, const SrTsdfSpace* space, long long n, const float* tsdf, const float* rgb, TsdfViewsDev* v,
+                          TsdfSpace* sp) {
+    if (!views || !space) return fail(SR_ERR_INVALID_ARGUMENT, "views / space is NULL");
+    if (!views->maps) return fail(SR_ERR_INVALID_ARGUMENT, "maps is NULL");
+    if (!views->full_proj) return fail(SR_ERR_INVALID_ARGUMENT, "full_proj is NULL");
+    if (views->V < 1) return fail(SR_ERR_INVALID_ARGUMENT, "V = %d: at least one view", views->V);
+    if (views->H < 2 || views->W < 2) return fail(SR_ERR_INVALID_ARGUMENT, "maps of %d x %d: H and W must be at least 2", views->H, views->W);
+    if (views->channels != 1 && views->channels != 4) return fail(SR_ERR_INVALID_ARGUMENT, "channels = %d: 1 (depth) or 4 (depth, r, g, b)", views->channels);
+    if ((uintptr_t)views->maps & (views->channels == 4 ? 15u : 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "maps is not %d-B aligned", 4 * views->channels);
+    if ((uintptr_t)views->full_proj & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "full_proj is not 4-B aligned");
+    if (!(space->voxel_size > 0.0)) return fail(SR_ERR_INVALID_ARGUMENT, "voxel_size = %g: must be positive", space->voxel_size);
+    if (rgb && views->channels != 4) return fail(SR_ERR_INVALID_ARGUMENT, "rgb asked for, but the maps hold depths only (channels = 1)");
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n < 0");
+    if (n >= (1ll << 31)) return fail(SR_ERR_UNSUPPORTED, "%lld samples in one call: fewer than 2^31 (split the call)", n);
+    if (n > 0 && !tsdf) return fail(SR_ERR_INVALID_ARGUMENT, "tsdf is NULL");
+    *v = TsdfViewsDev{views->maps, views->full_proj, views->V, views->H, views->W, views->channels};
+    *sp = TsdfSpace{(float)(5.0 * space->voxel_size), space->contract ? 1 : 0, {space->center[0], space->center[1], space->center[2]}, space->radius};
+    return SR_OK;
+}
+
+extern "C" {
+
+int sr_tsdf_fuse(const SrTsdfViews* views, const SrTsdfSpace* space, int32_t n, const float* samples, float* tsdf, float* rgb, float* weight,
+                 void* stream) {
+    TsdfViewsDev v; TsdfSpace sp;
+    if (int rc = tsdf_arguments(views, space, n, tsdf, rgb, &v, &sp)) return rc;
+    if (n == 0) return SR_OK;
+    if (!samples) return fail(SR_ERR_INVALID_ARGUMENT, "samples is NULL");
+    SR_HIP(launch_tsdf_fuse(v, sp, nullptr, n, samples, tsdf, rgb, weight, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_tsdf_fuse_grid(const SrTsdfViews* views, const SrTsdfSpace* space, const int32_t* dims, const float* lo, const float* step,
+                      int32_t ix_begin, int32_t ix_end, float* tsdf, float* rgb, float* weight, void* stream) {
+    if (!dims || !lo || !step) return fail(SR_ERR_INVALID_ARGUMENT, "dims / lo / step is NULL");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return fail(SR_ERR_INVALID_ARGUMENT, "dims %d x %d x %d: every axis holds at least one sample", dims[0], dims[1], dims[2]);
+    if (ix_begin < 0 || ix_end < ix_begin || ix_end > dims[0]) return fail(SR_ERR_INVALID_ARGUMENT, "slab [%d, %d) is not inside [0, %d)", ix_begin, ix_end, dims[0]);
+    if ((long long)dims[1] * dims[2] >= (1ll << 31)) return fail(SR_ERR_UNSUPPORTED, "one plane of %d x %d samples: fewer than 2^31", dims[1], dims[2]);
+    const long long n = (long long)(ix_end - ix_begin) * dims[1] * dims[2];
+    TsdfViewsDev v; TsdfSpace sp;
+    if (int rc = tsdf_arguments(views, space, n, tsdf, rgb, &v, &sp)) return rc;
+    if (n == 0) return SR_OK;
+    const TsdfGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, dims[1], dims[2], ix_begin};
+    SR_HIP(launch_tsdf_fuse(v, sp, &g, (int)n, nullptr, tsdf, rgb, weight, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

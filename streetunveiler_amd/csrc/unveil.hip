@@ -25,13 +25,29 @@
 // below, one rounding each, as the stock-torch lines they restate evaluate them.
 #include <cmath>
 
-#include "launch.h"
+#include "abi.h"
 #include "reduce.h"
 
 namespace sr {
 
+constexpr int kUnveilCamFloats = 24;   // a camera row: w2c rows 0..2 (12), K (9), max_z (+inf: none), reso_scale (0: none), one unused
+constexpr int kDilateRows = 32;        // output rows of a dilation tile (64 columns wide); the tile rows are grid.y: H <= 32 * 65535
+struct UnveilSemantic {    // a kernel parameter, by value: device pointers
+    int P, F, Hm, Wm;
+    uint32_t remain_bit;   // bits 0..30
+    const float* xyz;      // [P,3]
+    const float* cams;     // [F,kUnveilCamFloats]
+    const int32_t* hw;     // [F,2] = (h, w)
+    const uint8_t* maps;   // [F,Hm,Wm] labels
+};
+struct UnveilConditions {  // a kernel parameter, by value: device pointers; the images are [C,H,W] float32, the outputs [H,W,C] uint8
+    int H, W;
+    const float *full_render, *full_alpha, *background_render, *background_alpha, *background_depth, *background_normal, *sky;
+    uint8_t *original_rgb, *inpainted_rgb, *empty_opacity, *inpainted_depth, *inpainted_normal;
+};
+
 constexpr int kUnveilThreads = 256;
-constexpr int kVisRows = 8;                                  // points a thread of frame_visibility_kernel holds
+constexpr int kVisRows = 8;                                 // points a thread of frame_visibility_kernel holds
 constexpr int kVisChunk = kVisRows * kReduceThreads;         // 2048 points a block
 constexpr int kDilateMaxK = 31;
 constexpr int kDilateStaged = kDilateRows + kDilateMaxK - 1;
@@ -280,10 +296,10 @@ static UnveilLayout unveil_layout(int P, int F) {
     L.total = c.off;
     return L;
 }
-size_t unveil_workspace_bytes(int P, int F) { return unveil_layout(P, F).total; }
+static size_t unveil_workspace_bytes(int P, int F) { return unveil_layout(P, F).total; }
 
 // P >= 1.  count == nullptr: the mask alone; else the offsets of the admitted points are left in the workspace and *count (device) = n
-hipError_t points_in_frame(int P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* ws, uint32_t* count, hipStream_t s) {
+static hipError_t points_in_frame(int P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* ws, uint32_t* count, hipStream_t s) {
     uint32_t* offsets = count ? at<uint32_t>(ws, unveil_layout(P, 1).offsets) : nullptr;
     hipLaunchKernelGGL(points_in_frame_kernel, unveil_grid(P), dim3(kUnveilThreads), 0, s, P, xyz, cam, hw, mask, offsets);
     hipError_t e = hipGetLastError();
@@ -292,7 +308,7 @@ hipError_t points_in_frame(int P, const float* xyz, const float* cam, const int3
 }
 
 // after points_in_frame with a count on the same points, camera and workspace; n >= 1 rows
-hipError_t points_in_frame_emit(int P, const float* xyz, const float* cam, const int32_t* hw, const void* ws, uint32_t n, int64_t* pix, float* depth,
+static hipError_t points_in_frame_emit(int P, const float* xyz, const float* cam, const int32_t* hw, const void* ws, uint32_t n, int64_t* pix, float* depth,
                                 hipStream_t s) {
     const uint32_t* offsets = at<const uint32_t>(const_cast<void*>(ws), unveil_layout(P, 1).offsets);
     hipLaunchKernelGGL(points_emit_kernel, unveil_grid(P), dim3(kUnveilThreads), 0, s, P, xyz, cam, hw, offsets, n, reinterpret_cast<long long*>(pix), depth);
@@ -300,7 +316,7 @@ hipError_t points_in_frame_emit(int P, const float* xyz, const float* cam, const
 }
 
 // P, F >= 1
-hipError_t frame_visibility(int P, int F, const float* xyz, const float* cams, const int32_t* hw, void* ws, int64_t* count, double* depth_sum,
+static hipError_t frame_visibility(int P, int F, const float* xyz, const float* cams, const int32_t* hw, void* ws, int64_t* count, double* depth_sum,
                             hipStream_t s) {
     double* partials = at<double>(ws, unveil_layout(P, F).partials);
     const int n_blocks = visibility_blocks(P);
@@ -311,28 +327,162 @@ hipError_t frame_visibility(int P, int F, const float* xyz, const float* cams, c
 }
 
 // a.P, a.F >= 1; n_out_of_range: device [1]
-hipError_t semantic_mask_of_points(const UnveilSemantic& a, uint8_t* mask, uint64_t* n_out_of_range, hipStream_t s) {
+static hipError_t semantic_mask_of_points(const UnveilSemantic& a, uint8_t* mask, uint64_t* n_out_of_range, hipStream_t s) {
     hipError_t e = hipMemsetAsync(n_out_of_range, 0, 8, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(semantic_mask_kernel, unveil_grid(a.P), dim3(kUnveilThreads), 0, s, a, mask, reinterpret_cast<unsigned long long*>(n_out_of_range));
     return hipGetLastError();
 }
 
-hipError_t dilate_mask(int H, int W, int k, const uint8_t* mask, uint8_t* out, hipStream_t s) {
-    return launch_dilate(H, W, k, MaskSource{mask}, out, s);
-}
-hipError_t instance_pixel_mask(int H, int W, int k, const float* alpha_a, const float* alpha_b, float threshold, uint8_t* out, hipStream_t s) {
-    return launch_dilate(H, W, k, AlphaDiffSource{alpha_a, alpha_b, threshold}, out, s);
-}
-hipError_t refill_mask(int H, int W, int C, int k, const float* render_a, const float* render_b, const uint8_t* mask, float eps, uint8_t* out,
-                       hipStream_t s) {
-    return launch_dilate(H, W, k, RefillSource{render_a, render_b, mask, eps, C}, out, s);
-}
-
-// two launches: the five images, the dilated instance mask
-hipError_t inpaint_conditions(const UnveilConditions& a, float threshold, int k, uint8_t* mask_out, hipStream_t s) {
-    hipLaunchKernelGGL(conditions_kernel, unveil_grid((size_t)a.H * (size_t)a.W), dim3(kUnveilThreads), 0, s, a);
-    return instance_pixel_mask(a.H, a.W, k, a.full_alpha, a.background_alpha, threshold, mask_out, s);
-}
-
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks the per-point sr_* calls share; *work = 0 where there is no point or no frame
+static int unveil_point_arguments(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, bool* work) {
+    if (P < 0 || F < 0) return fail(SR_ERR_INVALID_ARGUMENT, "P %d / F %d is negative", P, F);
+    *work = P > 0 && F > 0;
+    if (!*work) return SR_OK;
+    if (!xyz || !cams || !hw) return fail(SR_ERR_INVALID_ARGUMENT, "xyz / cams / hw is NULL");
+    if (((uintptr_t)xyz | (uintptr_t)cams | (uintptr_t)hw) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "xyz / cams / hw is not 4-B aligned");
+    return SR_OK;
+}
+
+// the checks the per-pixel sr_* calls share
+static int unveil_image_arguments(int32_t H, int32_t W, int32_t k) {
+    if (H < 1 || W < 1) return fail(SR_ERR_INVALID_ARGUMENT, "an image of %d x %d: H and W must be at least 1", H, W);
+    if ((long long)H * W > 0x7FFFFFFFll) return fail(SR_ERR_UNSUPPORTED, "an image of %d x %d: H W must fit in int32", H, W);
+    // a tile is 64 x kDilateRows pixels: the tile rows are the launch's grid.y, and a tile's halo reaches 64 columns past its own
+    if (H > kDilateRows * 65535) return fail(SR_ERR_UNSUPPORTED, "an image of %d rows: at most %d", H, kDilateRows * 65535);
+    if (W > 0x7FFFFFFF - 128) return fail(SR_ERR_UNSUPPORTED, "an image of %d columns: at most %d", W, 0x7FFFFFFF - 128);
+    if (k < 1 || k > 31) return fail(SR_ERR_INVALID_ARGUMENT, "k = %d not in 1..31", k);
+    return SR_OK;
+}
+
+extern "C" {
+
+size_t sr_unveil_workspace_bytes(int32_t P, int32_t F) {
+    if (P < 0 || F < 0) return 0;
+    return unveil_workspace_bytes(P, F);
+}
+
+int sr_points_in_frame(int32_t P, const float* xyz, const float* cam, const int32_t* hw, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                       uint32_t* count, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, 1, xyz, cam, hw, &work)) return rc;
+    if ((uintptr_t)count & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "count is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {
+        if (count) SR_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
+        return SR_OK;
+    }
+    if (!mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    if (count) if (int rc = check_workspace(workspace, workspace_bytes, unveil_workspace_bytes(P, 1))) return rc;
+    SR_HIP(points_in_frame(P, xyz, cam, hw, mask, workspace, count, s));
+    return SR_OK;
+}
+
+int sr_points_in_frame_emit(int32_t P, const float* xyz, const float* cam, const int32_t* hw, void* workspace, size_t workspace_bytes, int32_t n,
+                            int64_t* pix, float* depth, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, 1, xyz, cam, hw, &work)) return rc;
+    if (n < 0 || n > P) return fail(SR_ERR_INVALID_ARGUMENT, "n = %d: not in 0..P = %d", n, P);
+    if (n == 0) return SR_OK;
+    if (int rc = check_workspace(workspace, workspace_bytes, unveil_workspace_bytes(P, 1))) return rc;
+    if (!pix || !depth) return fail(SR_ERR_INVALID_ARGUMENT, "pix / depth is NULL");
+    if (((uintptr_t)pix & 7u) || ((uintptr_t)depth & 3u)) return fail(SR_ERR_INVALID_ARGUMENT, "pix is not 8-B or depth not 4-B aligned");
+    SR_HIP(points_in_frame_emit(P, xyz, cam, hw, workspace, (uint32_t)n, pix, depth, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_frame_visibility(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, void* workspace, size_t workspace_bytes,
+                        int64_t* count, double* depth_sum, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, F, xyz, cams, hw, &work)) return rc;
+    if (F == 0) return SR_OK;
+    if (!count || !depth_sum) return fail(SR_ERR_INVALID_ARGUMENT, "count / depth_sum is NULL");
+    if (((uintptr_t)count | (uintptr_t)depth_sum) & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "count / depth_sum is not 8-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {   // no point: every count and sum is 0 (all bits zero)
+        SR_HIP(hipMemsetAsync(count, 0, sizeof(int64_t) * (size_t)F, s));
+        SR_HIP(hipMemsetAsync(depth_sum, 0, sizeof(double) * (size_t)F, s));
+        return SR_OK;
+    }
+    if (int rc = check_workspace(workspace, workspace_bytes, unveil_workspace_bytes(P, F))) return rc;
+    SR_HIP(frame_visibility(P, F, xyz, cams, hw, workspace, count, depth_sum, s));
+    return SR_OK;
+}
+
+int sr_semantic_mask_of_points(int32_t P, int32_t F, const float* xyz, const float* cams, const int32_t* hw, const uint8_t* maps, int32_t Hm,
+                               int32_t Wm, uint32_t remain_bit, uint8_t* mask, uint64_t* n_out_of_range, void* stream) {
+    bool work;
+    if (int rc = unveil_point_arguments(P, F, xyz, cams, hw, &work)) return rc;
+    if (Hm < 1 || Wm < 1) return fail(SR_ERR_INVALID_ARGUMENT, "maps of %d x %d: Hm and Wm must be at least 1", Hm, Wm);
+    if (!n_out_of_range) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is NULL");
+    if ((uintptr_t)n_out_of_range & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "n_out_of_range is not 8-B aligned");
+    if (P > 0 && !mask) return fail(SR_ERR_INVALID_ARGUMENT, "mask is NULL");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!work) {   // no frame sets anything
+        SR_HIP(hipMemsetAsync(n_out_of_range, 0, sizeof(uint64_t), s));
+        if (P > 0) SR_HIP(hipMemsetAsync(mask, 0, (size_t)P, s));
+        return SR_OK;
+    }
+    if (!maps) return fail(SR_ERR_INVALID_ARGUMENT, "maps is NULL");
+    const UnveilSemantic a{P, F, Hm, Wm, remain_bit & 0x7FFFFFFFu, xyz, cams, hw, maps};
+    SR_HIP(semantic_mask_of_points(a, mask, n_out_of_range, s));
+    return SR_OK;
+}
+
+int sr_dilate_mask(int32_t H, int32_t W, int32_t k, const uint8_t* mask, uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!mask || !out) return fail(SR_ERR_INVALID_ARGUMENT, "mask / out is NULL");
+    if (mask == out) return fail(SR_ERR_INVALID_ARGUMENT, "out must not be the mask: a tile reads its neighbours' pixels");
+    SR_HIP(launch_dilate(H, W, k, MaskSource{mask}, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_instance_pixel_mask(int32_t H, int32_t W, const float* alpha_a, const float* alpha_b, float threshold, int32_t k, uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!alpha_a || !alpha_b || !out) return fail(SR_ERR_INVALID_ARGUMENT, "alpha_a / alpha_b / out is NULL");
+    if (((uintptr_t)alpha_a | (uintptr_t)alpha_b) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "alpha_a / alpha_b is not 4-B aligned");
+    if (threshold != threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NaN");
+    SR_HIP(launch_dilate(H, W, k, AlphaDiffSource{alpha_a, alpha_b, threshold}, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_refill_mask(int32_t H, int32_t W, int32_t C, const float* render_a, const float* render_b, const uint8_t* mask, float eps, int32_t k,
+                   uint8_t* out, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (C < 1 || C > 16) return fail(SR_ERR_UNSUPPORTED, "C = %d channels: 1..16", C);
+    if (!render_a || !render_b || !mask || !out) return fail(SR_ERR_INVALID_ARGUMENT, "render_a / render_b / mask / out is NULL");
+    if (mask == out) return fail(SR_ERR_INVALID_ARGUMENT, "out must not be the mask: a tile reads its neighbours' pixels");
+    if (((uintptr_t)render_a | (uintptr_t)render_b) & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "render_a / render_b is not 4-B aligned");
+    if (eps != eps) return fail(SR_ERR_INVALID_ARGUMENT, "eps is NaN");
+    SR_HIP(launch_dilate(H, W, k, RefillSource{render_a, render_b, mask, eps, C}, out, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_inpaint_conditions(int32_t H, int32_t W, const float* full_render, const float* full_alpha, const float* background_render,
+                          const float* background_alpha, const float* background_depth, const float* background_normal, const float* sky,
+                          float threshold, int32_t k, uint8_t* mask, uint8_t* original_rgb, uint8_t* inpainted_rgb, uint8_t* empty_opacity,
+                          uint8_t* inpainted_depth, uint8_t* inpainted_normal, void* stream) {
+    if (int rc = unveil_image_arguments(H, W, k)) return rc;
+    if (!full_render || !full_alpha || !background_render || !background_alpha || !background_depth || !background_normal || !sky)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an input image is NULL");
+    if (((uintptr_t)full_render | (uintptr_t)full_alpha | (uintptr_t)background_render | (uintptr_t)background_alpha | (uintptr_t)background_depth |
+         (uintptr_t)background_normal | (uintptr_t)sky) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an input image is not 4-B aligned");
+    if (!mask || !original_rgb || !inpainted_rgb || !empty_opacity || !inpainted_depth || !inpainted_normal)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an output is NULL");
+    if (threshold != threshold) return fail(SR_ERR_INVALID_ARGUMENT, "threshold is NaN");
+    const UnveilConditions a{H, W, full_render, full_alpha, background_render, background_alpha, background_depth, background_normal, sky,
+                             original_rgb, inpainted_rgb, empty_opacity, inpainted_depth, inpainted_normal};
+    // two launches: the five images, the dilated instance mask
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(conditions_kernel, unveil_grid((size_t)H * (size_t)W), dim3(kUnveilThreads), 0, s, a);
+    SR_HIP(launch_dilate(H, W, k, AlphaDiffSource{full_alpha, background_alpha, threshold}, mask, s));
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -22,9 +22,10 @@
 // Every index is tested before it is used: a permutation entry and a member range against n, a voxel id against the voxel count on the
 // device, an output row against the rows the caller allocated, a queue slot against the queue's capacity.
 // Built with -ffp-contract=off: the voxel coordinate is a bit-exact contract.
+#include <cfloat>
 #include <cmath>
 
-#include "launch.h"
+#include "abi.h"
 #include "scan.h"
 
 namespace sr {
@@ -33,6 +34,8 @@ constexpr int kVoxelThreads = 256;
 constexpr int kVoxelBoundRows = 8;                                   // points a thread of the bounds kernel takes
 constexpr int kVoxelBoundChunk = kVoxelBoundRows * kVoxelThreads;    // 2048 points a block
 constexpr int kVoxelHeavyBlocks = 1024;                              // blocks of four waves that drain the heavy queue
+constexpr int kVoxelHeavy = 128;                                     // a voxel of more members than this gets a wave instead of a lane
+constexpr long long kVoxelMaxOffset = 1ll << 21;                     // offset^3 must stay inside int64
 
 // ---- loads ------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double load_real(const void* __restrict__ p, int is_f64, size_t i) {
@@ -380,10 +383,10 @@ static VoxelLayout voxel_layout(uint32_t n) {
     L.total = c.off;
     return L;
 }
-size_t voxel_workspace_bytes(uint32_t n) { return voxel_layout(n).total; }
+static size_t voxel_workspace_bytes(uint32_t n) { return voxel_layout(n).total; }
 
 // n >= 1.  bounds: device [7] doubles
-hipError_t voxel_bounds(uint32_t n, const void* points, int points_f64, void* ws, double* bounds, hipStream_t s) {
+static hipError_t voxel_bounds(uint32_t n, const void* points, int points_f64, void* ws, double* bounds, hipStream_t s) {
     double* partials = at<double>(ws, voxel_layout(n).partials);
     const int nb = voxel_bound_blocks(n);
     hipLaunchKernelGGL(voxel_bounds_kernel, dim3(nb), dim3(kVoxelThreads), 0, s, n, points, points_f64, partials);
@@ -394,7 +397,7 @@ hipError_t voxel_bounds(uint32_t n, const void* points, int points_f64, void* ws
 static int bits_of(unsigned long long x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
 
 // n >= 1, 1 <= offset < 2^21.  counts (device, may be nullptr): {voxels, kept, bad labels}
-hipError_t voxel_group(uint32_t n, const void* points, int points_f64, const void* labels, int label_bytes, const double* lo, double voxel_size,
+static hipError_t voxel_group(uint32_t n, const void* points, int points_f64, const void* labels, int label_bytes, const double* lo, double voxel_size,
                        long long offset, void* ws, uint32_t* counts, RankMode rank_mode, hipStream_t s) {
     const VoxelLayout L = voxel_layout(n);
     uint32_t* meta = at<uint32_t>(ws, L.meta);
@@ -460,7 +463,7 @@ hipError_t voxel_group(uint32_t n, const void* points, int points_f64, const voi
 }
 
 // after voxel_group on the same points and workspace; rows >= 1: the kept count the caller read back
-hipError_t voxel_emit(uint32_t n, const void* points, int points_f64, const void* colors, int colors_f64, const void* normals, int normals_f64,
+static hipError_t voxel_emit(uint32_t n, const void* points, int points_f64, const void* colors, int colors_f64, const void* normals, int normals_f64,
                       const void* ws, uint32_t n_voxels, uint32_t rows, float* out_points, float* out_colors, float* out_normals, int32_t* out_labels,
                       int32_t* out_counts, int64_t* out_index, hipStream_t s) {
     const VoxelLayout L = voxel_layout(n);
@@ -479,3 +482,73 @@ hipError_t voxel_emit(uint32_t n, const void* points, int points_f64, const void
 }
 
 }  // namespace sr
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
+using namespace sr;
+
+// the checks the three launching sr_voxel_* calls share: the cloud and the workspace
+static int voxel_arguments(int32_t n, const void* points, int32_t points_f64, const void* workspace, size_t workspace_bytes) {
+    if (n < 0) return fail(SR_ERR_INVALID_ARGUMENT, "n %d is negative", n);
+    if (int rc = check_f32_or_f64("points", nullptr, points_f64)) return rc;   // the flag; the address once there are points
+    if (n == 0) return SR_OK;
+    if (!points) return fail(SR_ERR_INVALID_ARGUMENT, "points is NULL");
+    if (int rc = check_f32_or_f64("points", points, points_f64)) return rc;
+    return check_workspace(workspace, workspace_bytes, voxel_workspace_bytes((uint32_t)n));
+}
+
+extern "C" {
+
+size_t sr_voxel_workspace_bytes(int32_t n) { return n < 0 ? 0 : voxel_workspace_bytes((uint32_t)n); }
+
+int sr_voxel_bounds(int32_t n, const void* points, int32_t points_f64, void* workspace, size_t workspace_bytes, double* bounds, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (!bounds) return fail(SR_ERR_INVALID_ARGUMENT, "bounds is NULL");
+    if ((uintptr_t)bounds & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "bounds is not 8-B aligned");
+    if (n == 0) return fail(SR_ERR_INVALID_ARGUMENT, "an empty cloud has no bounds");
+    SR_HIP(voxel_bounds((uint32_t)n, points, points_f64, workspace, bounds, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+int sr_voxel_group(int32_t n, const void* points, int32_t points_f64, const void* semantics, int32_t semantics_bytes, const double* lo,
+                   double voxel_size, int64_t offset, void* workspace, size_t workspace_bytes, uint32_t* counts, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (!(voxel_size > 0.0 && voxel_size <= DBL_MAX)) return fail(SR_ERR_INVALID_ARGUMENT, "voxel_size %g is not a positive finite number", voxel_size);
+    if (!lo) return fail(SR_ERR_INVALID_ARGUMENT, "lo is NULL");
+    if (!(std::isfinite(lo[0]) && std::isfinite(lo[1]) && std::isfinite(lo[2])))
+        return fail(SR_ERR_INVALID_ARGUMENT, "lo = (%g, %g, %g) is not finite: the cloud has a NaN or infinite coordinate", lo[0], lo[1], lo[2]);
+    if (offset < 1) return fail(SR_ERR_INVALID_ARGUMENT, "offset %lld < 1", (long long)offset);
+    if (offset >= kVoxelMaxOffset)
+        return fail(SR_ERR_UNSUPPORTED, "offset %lld >= 2^21: offset^3 would leave int64 (a larger voxel_size, or the cloud in parts)", (long long)offset);
+    if (semantics && semantics_bytes != 4 && semantics_bytes != 8) return fail(SR_ERR_INVALID_ARGUMENT, "semantics_bytes = %d: 4 (int32) or 8 (int64)", semantics_bytes);
+    if (semantics && ((uintptr_t)semantics & (uintptr_t)(semantics_bytes - 1))) return fail(SR_ERR_INVALID_ARGUMENT, "semantics is not aligned to its element size");
+    if (!counts) return fail(SR_ERR_INVALID_ARGUMENT, "counts is NULL");
+    if ((uintptr_t)counts & 3u) return fail(SR_ERR_INVALID_ARGUMENT, "counts is not 4-B aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) { SR_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s)); return SR_OK; }
+    RankMode sort_mode = kRankUnknown;
+    if (int rc = rank_mode(s, false, &sort_mode)) return rc;
+    SR_HIP(voxel_group((uint32_t)n, points, points_f64, semantics, semantics_bytes, lo, voxel_size, (long long)offset, workspace, counts, sort_mode, s));
+    return SR_OK;
+}
+
+int sr_voxel_emit(int32_t n, const void* points, int32_t points_f64, const void* colors, int32_t colors_f64, const void* normals,
+                  int32_t normals_f64, void* workspace, size_t workspace_bytes, int32_t n_voxels, int32_t n_kept, float* out_points,
+                  float* out_colors, float* out_normals, int32_t* out_semantics, int32_t* out_counts, int64_t* out_index, void* stream) {
+    if (int rc = voxel_arguments(n, points, points_f64, workspace, workspace_bytes)) return rc;
+    if (int rc = check_f32_or_f64("colors", colors, colors_f64)) return rc;
+    if (int rc = check_f32_or_f64("normals", normals, normals_f64)) return rc;
+    if (n_voxels < 0 || n_voxels > n) return fail(SR_ERR_INVALID_ARGUMENT, "n_voxels = %d: not in 0..n = %d", n_voxels, n);
+    if (n_kept < 0 || n_kept > n_voxels) return fail(SR_ERR_INVALID_ARGUMENT, "n_kept = %d: not in 0..n_voxels = %d", n_kept, n_voxels);
+    if (n_kept == 0) return SR_OK;
+    if (!out_points) return fail(SR_ERR_INVALID_ARGUMENT, "out_points is NULL");
+    if (colors && !out_colors) return fail(SR_ERR_INVALID_ARGUMENT, "out_colors is NULL (colors is given)");
+    if (normals && !out_normals) return fail(SR_ERR_INVALID_ARGUMENT, "out_normals is NULL (normals is given)");
+    if (((uintptr_t)out_points | (uintptr_t)out_colors | (uintptr_t)out_normals | (uintptr_t)out_semantics | (uintptr_t)out_counts) & 3u)
+        return fail(SR_ERR_INVALID_ARGUMENT, "an output is not 4-B aligned");
+    if ((uintptr_t)out_index & 7u) return fail(SR_ERR_INVALID_ARGUMENT, "out_index is not 8-B aligned");
+    SR_HIP(voxel_emit((uint32_t)n, points, points_f64, colors, colors_f64, normals, normals_f64, workspace, (uint32_t)n_voxels, (uint32_t)n_kept, out_points,
+                      out_colors, out_normals, out_semantics, out_counts, out_index, static_cast<hipStream_t>(stream)));
+    return SR_OK;
+}
+
+}  // extern "C"

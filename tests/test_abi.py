@@ -257,6 +257,104 @@ def test_refused_flag_combinations_without_gpu(lib):
         check(fn(*args), (UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY"), (name, "capacity"))
 
 
+# ---- workspace refusals ----------------------------------------------------------------------------------------------------------------
+TOO_SMALL = -3   # SR_ERR_BUFFER_TOO_SMALL
+
+
+def _workspace_calls(lib, p):
+    """Every entry point that takes (workspace, workspace_bytes) as name -> (the bytes its *_bytes function reports, call(workspace, bytes)),
+    with the smallest arguments it accepts otherwise: `p` is a 16-B aligned address inside a host buffer (nothing is launched, so nothing
+    dereferences it on a device; the few host arrays -- dims, counts, lo, step, the segment -- are real)."""
+    n = 10
+    dims = (ctypes.c_int32 * 3)(3, 3, 3)
+    f3 = (ctypes.c_float * 3)(0.0, 0.0, 0.0)
+    d3 = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+    plan_counts = (ctypes.c_uint32 * 4)()
+    apply_counts = (ctypes.c_uint32 * 4)(1, 0, 0, 0)
+    segment = (_lib.SrDensifySegment * 1)(_lib.SrDensifySegment(p, p, 1, _lib.SR_DENSIFY_ROLE_COPY))
+    aux = lib.sr_aux_loss_workspace_bytes(n)
+    post = lib.sr_mesh_post_workspace_bytes(n, n)
+    voxel = lib.sr_voxel_workspace_bytes(n)
+    lidar = lib.sr_lidar_label_workspace_bytes(n, 1)
+    return {
+        "sr_knn_mean_dist2": (lib.sr_knn_workspace_bytes(0, n), lambda w, b: lib.sr_knn_mean_dist2(0, None, n, p, 3, 0, p, w, b, None)),
+        "sr_cluster_radius": (lib.sr_cluster_workspace_bytes(n), lambda w, b: lib.sr_cluster_radius(n, p, None, 1.0, p, w, b, None)),
+        "sr_image_loss_forward": (lib.sr_image_loss_workspace_bytes(16, 8, 3),
+                                  lambda w, b: lib.sr_image_loss_forward(16, 8, 3, 0.2, p, p, None, None, w, b, p, None)),
+        "sr_image_loss_backward": (lib.sr_image_loss_workspace_bytes(16, 8, 3),
+                                   lambda w, b: lib.sr_image_loss_backward(16, 8, 3, 0.2, p, p, None, None, w, b, p, p, None, None, None)),
+        "sr_semantic_ce_forward": (aux, lambda w, b: lib.sr_semantic_ce_forward(n, 1, 3, p, p, 1, None, w, b, p, None)),
+        "sr_surface_reg_forward": (aux, lambda w, b: lib.sr_surface_reg_forward(n, 1, p, p, p, 0.05, 100.0, w, b, p, None)),
+        "sr_opacity_shrink_forward": (aux, lambda w, b: lib.sr_opacity_shrink_forward(n, p, 0, w, b, p, None)),
+        "sr_sky_backward": (lib.sr_sky_workspace_bytes(0),
+                            lambda w, b: lib.sr_sky_backward(n, 1, *[p] * 10, 0, w, b, *[p] * 8, None)),
+        "sr_densify_plan": (lib.sr_densify_workspace_bytes(n),
+                            lambda w, b: lib.sr_densify_plan(n, p, p, p, p, 0.0002, 0.005, 0.01, -1.0, None, w, b, plan_counts, None)),
+        "sr_densify_apply": (lib.sr_densify_workspace_bytes(n), lambda w, b: lib.sr_densify_apply(n, apply_counts, p, p, p, segment, 1, w, b, None)),
+        "sr_mesh_count": (lib.sr_mesh_workspace_bytes(dims), lambda w, b: lib.sr_mesh_count(p, dims, 0.0, w, b, p, None)),
+        "sr_mesh_emit": (lib.sr_mesh_workspace_bytes(dims), lambda w, b: lib.sr_mesh_emit(p, dims, 0.0, f3, f3, None, w, b, 1, 1, p, p, None)),
+        "sr_mesh_components": (post, lambda w, b: lib.sr_mesh_components(p, n, n, p, p, p, w, b, None)),
+        "sr_mesh_filter_count": (post, lambda w, b: lib.sr_mesh_filter_count(p, n, n, p, p, p, w, b, p, None)),
+        "sr_mesh_filter_emit": (post, lambda w, b: lib.sr_mesh_filter_emit(p, n, n, p, None, w, b, 1, 1, p, None, p, None)),
+        "sr_points_in_frame": (lib.sr_unveil_workspace_bytes(n, 1), lambda w, b: lib.sr_points_in_frame(n, p, p, p, p, w, b, p, None)),
+        "sr_points_in_frame_emit": (lib.sr_unveil_workspace_bytes(n, 1), lambda w, b: lib.sr_points_in_frame_emit(n, p, p, p, w, b, 1, p, p, None)),
+        "sr_frame_visibility": (lib.sr_unveil_workspace_bytes(n, 2), lambda w, b: lib.sr_frame_visibility(n, 2, p, p, p, w, b, p, p, None)),
+        "sr_voxel_bounds": (voxel, lambda w, b: lib.sr_voxel_bounds(n, p, 0, w, b, p, None)),
+        "sr_voxel_group": (voxel, lambda w, b: lib.sr_voxel_group(n, p, 1, None, 0, d3, 0.1, 100, w, b, p, None)),
+        "sr_voxel_emit": (voxel, lambda w, b: lib.sr_voxel_emit(n, p, 0, None, 0, None, 0, w, b, 1, 1, p, None, None, None, None, None, None)),
+        "sr_lidar_label_decide": (lidar, lambda w, b: lib.sr_lidar_label_decide(n, p, 1, None, 1, n, p, 1, 1, 3, 0, None, 0, w, b, p, None)),
+        "sr_lidar_label_emit": (lidar, lambda w, b: lib.sr_lidar_label_emit(n, p, 1, None, 1, n, 1, w, b, 1, p, None, None, None, None, None)),
+        "sr_lidar_vote": (lidar, lambda w, b: lib.sr_lidar_vote(n, p, 1, p, 1, 3, None, w, b, p, p, None)),
+    }
+
+
+# name -> what the library of commit 287dd84 (every entry point still in api.hip, every check written out) answers to a NULL workspace, to
+# one a byte short, and to an address with & 15 == 8: (status, the whole text of sr_last_error()).  Mesh's short workspace is -1 where every
+# other is -3.  None: that library has no alignment test there and, the other arguments being acceptable, nothing refuses the call before its
+# first launch (knn, cluster, the image loss, the three auxiliary losses, the sky backward, sr_densify_apply) -- never called here.
+_NULL, _MISALIGNED = (INVALID, "workspace is NULL"), (INVALID, "workspace is not 16-B aligned")
+WORKSPACE_REFUSALS = {
+    "sr_knn_mean_dist2": ((INVALID, "NULL argument"), (TOO_SMALL, "workspace 9983 < 9984"), None),
+    "sr_cluster_radius": ((INVALID, "NULL argument"), (TOO_SMALL, "workspace 9215 < 9216"), None),
+    "sr_image_loss_forward": ((INVALID, "image / gt / workspace is NULL"), (TOO_SMALL, "workspace 37375 < 37376"), None),
+    "sr_image_loss_backward": ((INVALID, "image / gt / workspace is NULL"), (TOO_SMALL, "workspace 37375 < 37376"), None),
+    "sr_semantic_ce_forward": ((INVALID, "sr_semantic_ce_forward: workspace is NULL"), (TOO_SMALL, "sr_semantic_ce_forward: workspace 15 < 16"), None),
+    "sr_surface_reg_forward": ((INVALID, "sr_surface_reg_forward: workspace is NULL"), (TOO_SMALL, "sr_surface_reg_forward: workspace 15 < 16"), None),
+    "sr_opacity_shrink_forward": ((INVALID, "sr_opacity_shrink_forward: workspace is NULL"), (TOO_SMALL, "sr_opacity_shrink_forward: workspace 15 < 16"), None),
+    "sr_sky_backward": ((INVALID, "sr_sky_backward: workspace is NULL"), (TOO_SMALL, "sr_sky_backward: workspace 19666943 < 19666944"), None),
+    "sr_densify_plan": (_NULL, (TOO_SMALL, "workspace 1023 < 1024"), _MISALIGNED),
+    "sr_densify_apply": (_NULL, (TOO_SMALL, "workspace 1023 < 1024"), None),
+    "sr_mesh_count": (_NULL, (INVALID, "workspace 767 < 768"), _MISALIGNED),
+    "sr_mesh_emit": (_NULL, (INVALID, "workspace 767 < 768"), _MISALIGNED),
+    "sr_mesh_components": (_NULL, (TOO_SMALL, "workspace 1023 < 1024"), _MISALIGNED),
+    "sr_mesh_filter_count": (_NULL, (TOO_SMALL, "workspace 1023 < 1024"), _MISALIGNED),
+    "sr_mesh_filter_emit": (_NULL, (TOO_SMALL, "workspace 1023 < 1024"), _MISALIGNED),
+    "sr_points_in_frame": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+    "sr_points_in_frame_emit": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+    "sr_frame_visibility": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+    "sr_voxel_bounds": (_NULL, (TOO_SMALL, "workspace 11007 < 11008"), _MISALIGNED),
+    "sr_voxel_group": (_NULL, (TOO_SMALL, "workspace 11007 < 11008"), _MISALIGNED),
+    "sr_voxel_emit": (_NULL, (TOO_SMALL, "workspace 11007 < 11008"), _MISALIGNED),
+    "sr_lidar_label_decide": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+    "sr_lidar_label_emit": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+    "sr_lidar_vote": (_NULL, (TOO_SMALL, "workspace 767 < 768"), _MISALIGNED),
+}
+
+
+def test_workspace_refusals_are_the_recorded_ones(lib):
+    dummy = ctypes.create_string_buffer(4096)
+    p = ctypes.addressof(dummy) + (-ctypes.addressof(dummy)) % 16
+    calls = _workspace_calls(lib, p)
+    assert sorted(calls) == sorted(WORKSPACE_REFUSALS) and len(calls) == 24
+    for name, (need, call) in calls.items():
+        assert need >= 16, name
+        for what, args, want in zip(("NULL", "short", "misaligned"), ((None, need), (p, need - 1), (p + 8, need)), WORKSPACE_REFUSALS[name]):
+            if want is None:
+                continue
+            got = (call(*args), lib.sr_last_error().decode())
+            assert got == want, (name, what, got)
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import torch
     from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
