@@ -4,7 +4,11 @@
 
 Per case and per quantity: (deviation of the HIP kernels from the float64 truth) / max(d_ref, floor), d_ref = the deviation of the
 reference's own float32 run (fixture cases) or of photometric_loss_torch in float32 on the CPU (the other sizes).  The same cases, the same
-functions as tests/test_gpu_image_loss.py; the tests assert ratio <= 4, this tool records the figures."""
+functions as tests/test_gpu_image_loss.py; the tests assert ratio <= 4, this tool records the figures.
+
+The edge cases (ilc.EDGE_CASES) follow under "edge_cases", each with the ratios of both bars: "per_element" (e = |v - truth| / (|truth| + u),
+u = 1 / (C*H*W); max and 99.9th percentile over the twin's same statistic or the floor; scalars as above) and "max_norm" (the rule above, on
+the quantities it can judge: a finite truth that is not identically zero).  null: no ratio exists (a NaN scalar, an all-zero truth)."""
 import argparse
 import json
 import os
@@ -36,11 +40,25 @@ def main():
             if v > worst[2]:
                 worst = (case["name"], k, v)
         print(case["name"], {k: round(v, 3) for k, v in r.items()}, flush=True)
-    doc = dict(device=torch.cuda.get_device_name(0), bar=ilc.BAR, floor=ilc.FLOOR, largest=dict(case=worst[0], quantity=worst[1], ratio=worst[2]), cases=rows)
+    edge_rows, edge_worst = [], ("", "", "", 0.0)
+    for name in ilc.EDGE_CASES:
+        case = ilc.edge_case(name)
+        got = ilc.run_hip(case)
+        per_element = ilc.edge_ratios(got, case)
+        max_norm = ilc.ratios(*ilc.where_the_old_rule_applies(got, case))
+        edge_rows.append(dict(case=name, shape=list(case["image"].shape), lambda_dssim=case["lambda_dssim"], per_element=per_element, max_norm=max_norm,
+                              violations=[list(v) for v in ilc.edge_violations(got, case)]))
+        for k, v in per_element.items():
+            for stat, r in (v.items() if isinstance(v, dict) else [("", v)] if v is not None else []):
+                if r > edge_worst[3]:
+                    edge_worst = (name, k, stat, r)
+        print(name, per_element, {k: round(v, 3) for k, v in max_norm.items()}, flush=True)
+    doc = dict(device=torch.cuda.get_device_name(0), bar=ilc.BAR, floor=ilc.FLOOR, largest=dict(case=worst[0], quantity=worst[1], ratio=worst[2]), cases=rows,
+               largest_per_element=dict(case=edge_worst[0], quantity=edge_worst[1], statistic=edge_worst[2], ratio=edge_worst[3]), edge_cases=edge_rows)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
-    print("largest ratio %.3f (%s, %s) -> %s" % (worst[2], worst[0], worst[1], args.out))
+    print("largest ratio %.3f (%s, %s); largest per-element ratio %.3f (%s, %s %s) -> %s" % (worst[2], worst[0], worst[1], edge_worst[3], *edge_worst[:3], args.out))
 
 
 if __name__ == "__main__":
