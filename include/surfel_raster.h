@@ -87,8 +87,9 @@ typedef struct SrFrame {
                                * pairs, [5] / [6] tests with a contributing pixel in rows 0-3 / rows 4-7 of the quadrant, [7] entries with a
                                * contributing pixel anywhere in the tile (= the gradient records the backward writes), [8] (entry, 4x4 cell) pairs
                                * with a contributing pixel, [9] the wave steps a 16-lane-row mapping would take (sum over rounds of 64
-                               * entries and quadrants of the busiest cell's pair count), [10] / [11] the same two counting the pairs an octagon-vs-cell
-                               * culling at staging would keep (hits and misses), [12] / [13] the same two with an octagon + oriented-box culling, [14] exact (entry, cell) hits that box would DROP (must be 0); [15] reserved.  16x16 tile with
+                               * entries and quadrants of the busiest cell's pair count), [10] / [11] the same two counting the pairs the row-mapped
+                               * forward's cell culling at staging keeps (hits and misses; the slab-extent test), [12] / [13] unused (zero), [14] exact
+                               * (entry, cell) hits that culling would DROP (must be 0), [15] the pairs of [10] as an octagon-vs-cell test keeps them.  16x16 tile with
                                * 3 or 6 colour channels; any other request returns SR_ERR_UNSUPPORTED (never silent zeros) */
 } SrFrame;
 #define SR_FLAG_NO_QUADRANT_CULL 1u  /* forward blend: run every list entry against every 8x8 quadrant instead of dropping entries that

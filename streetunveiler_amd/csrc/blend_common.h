@@ -4,6 +4,7 @@
 // decoder, the forward's per-pixel state / step / stores (ForwardPixel ...) and the backward's per-pair arithmetic (BackwardPixel ...).
 #pragma once
 #include "common.h"
+#include "footprint_cull.h"   // fast_rcp, the quadrant / cell culling of the staging lane (also compiled on the host by its test)
 
 namespace sr {
 
@@ -11,8 +12,6 @@ constexpr int kWave = 64;
 constexpr int kXcds = 8;   // MI355X: 8 accelerator dies, workgroup i runs on XCD i % 8
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kFN = kFar / (kFar - kNear);
-
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 // s_waitcnt vmcnt(0) (gfx9 encoding: vmcnt = bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 left at their maxima), placed by hand at the
 // top of a round of the list walks: everything in flight there was issued a round earlier, and a wait that sits on EVERY control-flow
@@ -24,140 +23,16 @@ __device__ __forceinline__ void wait_vector_memory() { __builtin_amdgcn_s_waitcn
 // non-zero quadrant mask, [2] quadrant tests executed, [3] quadrant tests with >= 1 valid lane, [4] valid (pixel, entry) pairs,
 // [5] / [6] tests with a valid pixel in rows 0-3 / rows 4-7 of the quadrant, [7] entries with a valid pixel anywhere in the tile,
 // [8] (entry, 4x4 cell) pairs with a valid pixel, [9] sum over (round of 64 entries, quadrant) of the busiest cell's pair count,
-// [10] / [11] the same two with the pairs an octagon-vs-cell culling at staging would KEEP (hits and misses) instead of the exact hits,
-// [12] / [13] ... an octagon + oriented-box culling would keep, [14] exact (entry, cell) pairs that the oriented box would DROP (must be 0)
+// [10] / [11] the same two with the pairs the row-mapped forward's cell culling at staging KEEPS (hits and misses) instead of the exact hits
+// (cell_mask_rows: slab extents since the octagon-vs-cell test left; the benchmark still prints them under the octagon's name),
+// [12] / [13] unused, zero (an octagon + oriented-box culling, measured and removed: DESIGN.md 4), [14] exact (entry, cell) pairs that
+// the staging test of [10] would DROP (must be 0), [15] the pairs of [10] as the octagon-vs-cell test would keep them
 
-// ---------------------------------------------------------------------------------------------
-// Quadrant culling.  A list entry can only contribute to a pixel if alpha = min(0.99, opacity*G) >= 1/255,
-// i.e. rho = min(rho3d, rho2d) <= thr = 2 ln(255 opacity).  {rho3d <= thr} is the image of the disc
-// u^2+v^2 <= thr under the splat's homography -- an ellipse with dual conic C* = Q diag(thr,thr,-1) Q^T --
-// and {rho2d <= thr} is a disc of radius sqrt(thr/2) around means2D.  The staging lane bounds that union by
-// an octagon (support in directions x, y, x+y, x-y from the tangent-line equation l^T C* l = 0) and tests it
-// against the tile's 8x8 quadrants (QX x QY of them; 2 x 2 for the reference's 16x16 tile).  (A second, nearly exact test in the splat's (u,v) plane removes another
-// 9 % of the tests but costs more at staging than it saves -- measured, not kept.)  Entries dropped here are entries the per-pixel test would skip anyway (`continue` in Appendix A.4),
-// so results are unchanged; the bound has 0.3 px / 1 % slack for float rounding and keeps the entry whenever
-// anything is degenerate or NaN.  Inputs are tile-local (origin at
-// the tile centre), which keeps the conic free of cancellation.
-// ---------------------------------------------------------------------------------------------
-// octagon of the entry's footprint in tile-local coordinates: lo / hi of x, y, x + y, x - y.  Returns 0 = empty footprint, 2 = unbounded
-// (the cutoff disc reaches the camera plane, or something is degenerate: keep the entry everywhere), 1 = bounds valid.
-__device__ __forceinline__ int octagon_bounds(const float Tu[3], const float Tv[3], const float Tw[3], float mx, float my, float opacity,
-                                              float (&lo)[4], float (&hi)[4]) {
-    float thr = 2.f * __logf(255.f * opacity);
-    thr = thr * 1.01f + 0.01f;
-    if (thr <= 0.f) return 0;
-    const float c22 = thr * (Tw[0] * Tw[0] + Tw[1] * Tw[1]) - Tw[2] * Tw[2];
-    if (!(c22 < 0.f)) return 2;  // the cutoff disc reaches the camera plane: unbounded footprint
-    const float c00 = thr * (Tu[0] * Tu[0] + Tu[1] * Tu[1]) - Tu[2] * Tu[2];
-    const float c01 = thr * (Tu[0] * Tv[0] + Tu[1] * Tv[1]) - Tu[2] * Tv[2];
-    const float c11 = thr * (Tv[0] * Tv[0] + Tv[1] * Tv[1]) - Tv[2] * Tv[2];
-    const float c02 = thr * (Tu[0] * Tw[0] + Tu[1] * Tw[1]) - Tu[2] * Tw[2];
-    const float c12 = thr * (Tv[0] * Tw[0] + Tv[1] * Tw[1]) - Tv[2] * Tw[2];
-    const float inv = fast_rcp(c22);
-    const float r = __builtin_amdgcn_sqrtf(0.5f * thr);
-    const float QA[4] = {c00, c11, c00 + 2.f * c01 + c11, c00 - 2.f * c01 + c11};
-    const float QB[4] = {c02, c12, c02 + c12, c02 - c12};
-    const float ctr[4] = {mx, my, mx + my, mx - my};
-    const float rad[4] = {r, r, r * 1.4142137f, r * 1.4142137f};
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const float disc = QB[d] * QB[d] - QA[d] * c22;
-        const float half = __builtin_amdgcn_sqrtf(fmaxf(disc, 0.f)) * (-inv) * 1.01f;
-        const float dc = QB[d] * inv;
-        lo[d] = fminf(dc - half, ctr[d] - rad[d]);
-        hi[d] = fmaxf(dc + half, ctr[d] + rad[d]);
-    }
-    return 1;
-}
-// does the octagon reach the pixel-centre rectangle [x0, x1] x [y0, y1] (0.3 px of slack for float rounding)?
-__device__ __forceinline__ bool octagon_reaches(const float (&lo)[4], const float (&hi)[4], float x0, float x1, float y0, float y1) {
-    const float m = 0.3f;
-    x0 -= m; y0 -= m; x1 += m; y1 += m;
-    return !(lo[0] > x1 || hi[0] < x0 || lo[1] > y1 || hi[1] < y0 || lo[2] > x1 + y1 || hi[2] < x0 + y0 || lo[3] > x1 - y0 || hi[3] < x0 - y1);
-}
-
-template <int QX, int QY>
-__device__ __forceinline__ uint32_t quadrant_mask(const float Tu[3], const float Tv[3], const float Tw[3], float mx, float my,
-                                                  float opacity, float yshift) {
-    constexpr uint32_t kAll = (1u << (QX * QY)) - 1u;
-    float lo[4], hi[4];
-    const int kind = octagon_bounds(Tu, Tv, Tw, mx, my, opacity, lo, hi);
-    if (kind != 1) return kind ? kAll : 0u;
-    // the wave's quadrants sit `yshift` below the local origin: shift the bounds instead of the (compile-time) rectangles
-    lo[1] -= yshift; hi[1] -= yshift; lo[2] -= yshift; hi[2] -= yshift; lo[3] += yshift; hi[3] += yshift;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int q = 0; q < QX * QY; ++q) {   // quadrant (q % QX, q / QX) of the tile, coordinates relative to the tile centre
-        const float x0 = (float)((q % QX) * 8 - QX * 4), y0 = (float)((q / QX) * 8 - QY * 4);
-        if (octagon_reaches(lo, hi, x0, x0 + 7.f, y0, y0 + 7.f)) mask |= 1u << q;
-    }
-    return mask;
-}
-// The same test against the four 4x4 cells of each of the wave's quadrants: bit 4 q + c = cell c of quadrant q, cell c at (c & 1, c >> 1)
-// inside its quadrant (the row-mapped forward blend: one 16-lane row per cell).  (Two more slabs along the principal axes of the footprint
-// ellipse -- cell_mask16's oriented box -- keep 6 % fewer (entry, cell) pairs and cost as much at staging as they save: measured, not kept.)
-template <int QX, int QY>
-__device__ __forceinline__ uint32_t cell_mask_rows(const float Tu[3], const float Tv[3], const float Tw[3], float mx, float my,
-                                                   float opacity, float yshift) {
-    constexpr uint32_t kAll = (QX * QY >= 8) ? 0xFFFFFFFFu : (1u << (4 * QX * QY)) - 1u;
-    float lo[4], hi[4];
-    const int kind = octagon_bounds(Tu, Tv, Tw, mx, my, opacity, lo, hi);
-    if (kind != 1) return kind ? kAll : 0u;
-    lo[1] -= yshift; hi[1] -= yshift; lo[2] -= yshift; hi[2] -= yshift; lo[3] += yshift; hi[3] += yshift;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int q = 0; q < QX * QY; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float x0 = (float)((q % QX) * 8 + (c & 1) * 4 - QX * 4), y0 = (float)((q / QX) * 8 + (c >> 1) * 4 - QY * 4);
-            if (!octagon_reaches(lo, hi, x0, x0 + 3.f, y0, y0 + 3.f)) continue;
-            mask |= 1u << (4 * q + c);
-        }
-    return mask;
-}
-// (counter variant only) the same test against the sixteen 4x4 cells of a 16x16 tile: bit 4 q + c = cell c of quadrant q, cell c at
-// (c & 1, c >> 1) inside its quadrant.  Bits 16..31: the same with two more slabs, along the principal axes of the footprint ellipse
-// (an oriented box around ellipse and filter disc): what a tighter -- still conservative -- cell culling would keep.
+// (counter variant only) the sixteen 4x4 cells of a 16x16 tile, bit 4 q + c = cell c of quadrant q, cell c at (c & 1, c >> 1) inside its
+// quadrant: bits 0..15 by the test the row-mapped forward stages with (cell_mask_rows: slab extents), bits 16..31 by the octagon test it
+// replaced -- the yardstick of slot [15].
 __device__ __forceinline__ uint32_t cell_mask16(const float Tu[3], const float Tv[3], const float Tw[3], float mx, float my, float opacity) {
-    float lo[4], hi[4];
-    const int kind = octagon_bounds(Tu, Tv, Tw, mx, my, opacity, lo, hi);
-    if (kind != 1) return kind ? 0xFFFFFFFFu : 0u;
-    // oriented box: centre c, axes u / v, half extents E1 / E2 (support of the ellipse {rho3d <= thr} = sqrt(d^T S d), S from the dual conic)
-    float thr = 2.f * __logf(255.f * opacity);
-    thr = thr * 1.01f + 0.01f;
-    const float c22 = thr * (Tw[0] * Tw[0] + Tw[1] * Tw[1]) - Tw[2] * Tw[2];
-    const float c00 = thr * (Tu[0] * Tu[0] + Tu[1] * Tu[1]) - Tu[2] * Tu[2];
-    const float c01 = thr * (Tu[0] * Tv[0] + Tu[1] * Tv[1]) - Tu[2] * Tv[2];
-    const float c11 = thr * (Tv[0] * Tv[0] + Tv[1] * Tv[1]) - Tv[2] * Tv[2];
-    const float c02 = thr * (Tu[0] * Tw[0] + Tu[1] * Tw[1]) - Tu[2] * Tw[2];
-    const float c12 = thr * (Tv[0] * Tw[0] + Tv[1] * Tw[1]) - Tv[2] * Tw[2];
-    const float inv = fast_rcp(c22), inv2 = inv * inv;
-    const float cx = c02 * inv, cy = c12 * inv;
-    const float sxx = (c02 * c02 - c22 * c00) * inv2, syy = (c12 * c12 - c22 * c11) * inv2, sxy = (c02 * c12 - c22 * c01) * inv2;
-    const float a = 0.5f * (sxx - syy), r = __builtin_amdgcn_sqrtf(a * a + sxy * sxy), mid = 0.5f * (sxx + syy);
-    float ux = a >= 0.f ? a + r : sxy, uy = a >= 0.f ? sxy : r - a;
-    const float ul = ux * ux + uy * uy;
-    const float un = ul > 0.f ? __builtin_amdgcn_rsqf(ul) : 0.f;
-    ux = ul > 0.f ? ux * un : 1.f; uy = ul > 0.f ? uy * un : 0.f;
-    const float rd = __builtin_amdgcn_sqrtf(0.5f * thr);
-    const float ox = mx - cx, oy = my - cy;
-    const float E1 = fmaxf(__builtin_amdgcn_sqrtf(fmaxf(mid + r, 0.f)) * 1.01f, fabsf(ox * ux + oy * uy) + rd);
-    const float E2 = fmaxf(__builtin_amdgcn_sqrtf(fmaxf(mid - r, 0.f)) * 1.01f, fabsf(oy * ux - ox * uy) + rd);
-    const bool box_ok = E1 == E1 && E2 == E2;   // anything degenerate: the box says nothing
-    uint32_t mask = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float x0 = (float)((q % 2) * 8 + (c & 1) * 4 - 8), y0 = (float)((q / 2) * 8 + (c >> 1) * 4 - 8);
-            if (!octagon_reaches(lo, hi, x0, x0 + 3.f, y0, y0 + 3.f)) continue;
-            mask |= 1u << (4 * q + c);
-            const float rx = x0 + 1.5f - cx, ry = y0 + 1.5f - cy, h = 1.8f;
-            const float R = h * (fabsf(ux) + fabsf(uy));
-            const bool out = fabsf(rx * ux + ry * uy) > E1 + R || fabsf(ry * ux - rx * uy) > E2 + R;
-            if (!(box_ok && out)) mask |= 1u << (16 + 4 * q + c);
-        }
-    return mask;
+    return cell_mask_rows<2, 2>(Tu, Tv, Tw, mx, my, opacity, 0.f) | (cell_mask_octagon<2, 2>(Tu, Tv, Tw, mx, my, opacity, 0.f) << 16);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -178,7 +53,8 @@ __device__ __forceinline__ float4 load_extra(const float* __restrict__ colors6, 
 
 template <int QX, int QY, int NC>
 __device__ __forceinline__ uint32_t stage_entry(const float4 (&q)[kRecQuads], const float4 ex, const float4 ey, float Xc, float Yc, int cull,
-                                                float4 (*s_e)[kWave], int slot, float yshift = 0.f, uint32_t* cells16 = nullptr, uint32_t* cells_rows = nullptr) {
+                                                float4 (*s_e)[kWave], int slot, float yshift = 0.f, uint32_t* cells16 = nullptr, uint32_t* cells_rows = nullptr,
+                                                bool slab_cells = true) {
     const float Tw[3] = {q[1].z, q[1].w, q[2].x};
     const float Tu[3] = {q[0].x - Xc * Tw[0], q[0].y - Xc * Tw[1], q[0].z - Xc * Tw[2]};
     const float Tv[3] = {q[0].w - Yc * Tw[0], q[1].x - Yc * Tw[1], q[1].y - Yc * Tw[2]};
@@ -201,7 +77,8 @@ __device__ __forceinline__ uint32_t stage_entry(const float4 (&q)[kRecQuads], co
     if (NC == 9) s_e[6][slot] = make_float4(ey.x, ey.y, ey.z, 0.f);
     if (cells16) *cells16 = cell_mask16(Tu, Tv, Tw, mx, my, opacity);   // (counter variant: what a 4x4-cell culling would keep)
     if (cells_rows) {   // (row-mapped forward: per-cell bits; a quadrant is visited if one of its cells is)
-        *cells_rows = cell_mask_rows<QX, QY>(Tu, Tv, Tw, mx, my, opacity, yshift);
+        // slab_cells = false: the octagon test -- the forward that writes cell-granular hit masks spills at its 80 registers with the slab extents
+        *cells_rows = slab_cells ? cell_mask_rows<QX, QY>(Tu, Tv, Tw, mx, my, opacity, yshift) : cell_mask_octagon<QX, QY>(Tu, Tv, Tw, mx, my, opacity, yshift);
         uint32_t qm = 0;
 #pragma unroll
         for (int q = 0; q < QX * QY; ++q) qm |= ((*cells_rows >> (4 * q)) & 15u) ? (1u << q) : 0u;

@@ -145,8 +145,8 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
                     // bit of pixel (x, y) of the quadrant = 8 y + x: the four 4x4 cells
                     cell_round[q][0] += (vb & 0x000000000F0F0F0Full) != 0; cell_round[q][1] += (vb & 0x00000000F0F0F0F0ull) != 0;
                     cell_round[q][2] += (vb & 0x0F0F0F0F00000000ull) != 0; cell_round[q][3] += (vb & 0xF0F0F0F000000000ull) != 0;
-                    if (NQ == 4) {   // is the oriented-box cell mask conservative?  an exact hit in a cell whose box bit is clear is counted in [14]
-                        const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cells16, j) >> (16 + 4 * q);
+                    if (NQ == 4) {   // is the row-mapped forward's cell mask conservative?  an exact hit in a cell whose bit is clear is counted in [14]
+                        const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cells16, j) >> (4 * q);
                         const uint32_t exact = ((vb & 0x000000000F0F0F0Full) != 0 ? 1u : 0u) | ((vb & 0x00000000F0F0F0F0ull) != 0 ? 2u : 0u) |
                                                ((vb & 0x0F0F0F0F00000000ull) != 0 ? 4u : 0u) | ((vb & 0xF0F0F0F000000000ull) != 0 ? 8u : 0u);
                         if (lane == 0 && (exact & ~cj & 15u)) atomicAdd(&g_stats[14], (unsigned long long)__popc(exact & ~cj & 15u));
@@ -175,7 +175,7 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
             }
             atomicAdd(&g_stats[8], cells); atomicAdd(&g_stats[9], steps);
         }
-        if (kStats && NQ == 4) {   // ... and with the (entry, cell) pairs a conservative octagon-vs-cell test at staging would hand to the rows
+        if (kStats && NQ == 4) {   // ... and with the (entry, cell) pairs the conservative cell test at staging (cell_mask_rows) hands to the rows
             unsigned long long kept = 0ull, steps = 0ull;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -188,18 +188,13 @@ __device__ __forceinline__ void render_forward_body(float4 (*s_e)[kWave], const 
                 steps += busiest;
             }
             if (lane == 0) { atomicAdd(&g_stats[10], kept); atomicAdd(&g_stats[11], steps); }
-            kept = 0ull; steps = 0ull;
+            kept = 0ull;   // [15]: the same pairs as the octagon-vs-cell test would keep them
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t busiest = 0;
+            for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const uint32_t k = (uint32_t)__popcll(ballot64(((cells16 >> (16 + 4 * q + c)) & 1u) != 0u && ((m >> q) & 1u) != 0u && ((alive_at_round_start >> q) & 1u) != 0u));
-                    kept += k; busiest = max(busiest, k);
-                }
-                steps += busiest;
-            }
-            if (lane == 0) { atomicAdd(&g_stats[12], kept); atomicAdd(&g_stats[13], steps); }
+                for (int c = 0; c < 4; ++c)
+                    kept += (uint32_t)__popcll(ballot64(((cells16 >> (16 + 4 * q + c)) & 1u) != 0u && ((m >> q) & 1u) != 0u && ((alive_at_round_start >> q) & 1u) != 0u));
+            if (lane == 0) atomicAdd(&g_stats[15], kept);
         }
         // exact (entry, quadrant) hit mask for the backward: K7 visits only the pairs that reached a pixel here
         if (hit_mask) {   // (NULL with SR_FLAG_FORWARD_ONLY: no backward will read it)
@@ -233,7 +228,7 @@ void render_forward_kernel(FrameDev f, const uint2* __restrict__ ranges, const u
 
 // ---------------------------------------------------------------------------------------------
 // K6, row-mapped (three colour channels): the wave's four 16-lane rows are the four 4x4 cells of a quadrant, and every row walks ITS
-// OWN list -- the entries of the round whose octagon reaches its cell -- so a wave step serves four different entries, one per row,
+// OWN list -- the entries of the round whose footprint reaches its cell (cell_mask_rows) -- so a wave step serves four different entries, one per row,
 // instead of one entry on 64 lanes of which a thin splat uses a dozen.  Same staging, same `intersect`, same blend_forward_step
 // as render_forward_kernel: bit-identical images, state and hit masks.  The rows' entry indices travel packed in one SGPR
 // (next set bit of the row's 64-bit mask: scalar unit), every lane extracts its row's byte and reads the staged entry at ITS address.
@@ -285,9 +280,9 @@ __device__ __forceinline__ void render_forward_rows_body(float4 (*s_e)[kWave], u
         const uint32_t n = min((uint32_t)kWave, n_total - base);
         int ys = yshift_px;
         asm volatile("" : "+s"(ys));
-        uint32_t cm = 0;   // this lane's ENTRY: bit 4 q + c = its octagon reaches cell c of quadrant q
+        uint32_t cm = 0;   // this lane's ENTRY: bit 4 q + c = its footprint reaches cell c of quadrant q
         wait_vector_memory();
-        if ((uint32_t)lane < n) (void)stage_entry<QX, QY, NC>(nr, nx, nx, Xc, Yc, 1, s_e, lane, (float)ys, nullptr, &cm);
+        if ((uint32_t)lane < n) (void)stage_entry<QX, QY, NC>(nr, nx, nx, Xc, Yc, 1, s_e, lane, (float)ys, nullptr, &cm, !kCells);
         const uint32_t gid = gid_ahead;
         if (hit_mask && (uint32_t)lane < n_prev) store_hit_mask<QX, QY, SPLIT>(hit_mask, range.x + base_prev + lane, part, hm_prev);
         if (base + 2 * kWave + lane < n_total) gid_ahead = point_list[range.x + base + 2 * kWave + lane];
@@ -492,9 +487,12 @@ __global__ __launch_bounds__(4 * kWave) void render_forward_coop_kernel(FrameDev
 // The reference's 16x16 tile with three colour channels picks its mapping per FRAME, on the device: counts[0] = D, the frame's duplicates,
 // counts[1] = its visible Gaussians (both fall out of the emission scan, radix_sort.hip).  Splats that touch few tiles touch few 4x4 cells
 // of a quadrant, and the rows win; large splats fill quadrants, and one entry on all 64 lanes wins (3 M Gaussians: 1280x720, D / visible
-// = 3.4: 0.620 vs 0.696 ms; 1920x1080, 5.2: 0.858 vs 0.885; 2560x1440, 7.4: 1.182 vs 1.164; 3840x2160, 13: 2.13 vs 1.94).  Both bodies
-// produce the same bits, so the choice is invisible in the results.
-constexpr uint32_t kRowsBelowDuplicatesPerVisibleX2 = 13;   // rows if D / visible < 6.5
+// = 3.4: 0.620 vs 0.696 ms; 1920x1080, 5.2: 0.858 vs 0.885; 2560x1440, 7.4: 1.182 vs 1.164; 3840x2160, 13: 2.13 vs 1.94 -- with the
+// octagon-vs-cell test at staging, break-even 6.5).  The slab extents hand the rows 11 % fewer steps and moved it: whole step, forward +
+// backward, rows vs quadrants forced, one box: 2560x1440 (7.4) 4.132 vs 4.229 ms, 3840x2160 (13) 6.489 vs 6.441; the two differences
+// interpolate to zero near 11, and the threshold stays below that, on the side that was measured to win.  Both bodies produce the same bits, so the choice is
+// invisible in the results.
+constexpr uint32_t kRowsBelowDuplicatesPerVisibleX2 = 18;   // rows if D / visible < 9
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(6, 6)))
 void render_forward_auto_kernel(FrameDev f, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ point_list,
                                 const float4* __restrict__ recs, float* __restrict__ out_color, float* __restrict__ out_allmap, float* __restrict__ final_T,
