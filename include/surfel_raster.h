@@ -252,7 +252,13 @@ int sr_forward_plan(const SrFrame* frame, const SrGaussians* g, void* geom, size
 /* Forward, phase 2 (K3 / K4 expanding tile partition: column pass over the Gaussians, row pass over the column items; K5 ranges + dispatch
  * order; K6 blend).
  * out_color [NC,H,W], out_allmap [7,H,W] (0 sum w*depth, 1 alpha, 2-4 sum w*normal (view space),
- * 5 median depth, 6 distortion). */
+ * 5 median depth, 6 distortion).
+ * geom: the buffer sr_forward_plan of this frame filled.  It is required where there is anything to bin (P > 0 and num_rendered > 0), and
+ * where the forward kernel is the one the device picks per frame, which reads the frame counts in it: the 16x16 tile with three colour
+ * channels, no blend_counters and none of SR_FLAG_NO_QUADRANT_CULL, SR_FLAG_ROW_MAPPED_FORWARD, SR_FLAG_QUADRANT_MAPPED_FORWARD,
+ * SR_FLAG_COOP_BACKWARD, SR_FLAG_ROW_BACKWARD (SR_FLAG_ONE_WAVE_BACKWARD and SR_FLAG_FORWARD_ONLY do not change the forward kernel).  NULL is
+ * then refused (SR_ERR_INVALID_ARGUMENT, "geom is NULL") before anything is launched.  Otherwise it may be NULL; a buffer that is given is
+ * held to sr_geom_bytes(P) like any other. */
 int sr_forward_render(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning,
                       size_t binning_bytes, void* image, size_t image_bytes, uint32_t num_rendered,
                       float* out_color, float* out_allmap, void* stream);

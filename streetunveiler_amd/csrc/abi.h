@@ -1,6 +1,7 @@
 // abi.h -- what every file that defines C entry points (include/surfel_raster.h) needs: the refusal, the HIP-error macro, the per-device
 // and per-thread services api.hip keeps, and the two argument checks that more than two ops state word for word.  An op's own entry points
-// sit at the end of its .hip file, under "---- C-ABI ----"; a check that is specific to one op stays written out there.
+// sit at the end of its .hip file, under "---- C-ABI ----"; a check that is specific to one op stays written out there.  (The rasteriser's
+// entry points, in api.hip, check (frame, g) and their state buffers in one place of their own: api.hip Call.)
 // No device code.  Defined in api.hip: fail, stream_device, rank_mode, pinned_words.
 #pragma once
 #include "launch.h"

@@ -1,6 +1,7 @@
 // api.hip -- the rasteriser's part of the C-ABI (include/surfel_raster.h): its state-buffer layouts, argument checks, blend choice and stage
 // sequencing; the class passes; the debug and timing entry points; and what every entry point of the library shares (abi.h): the error
 // text, the per-device ranking mode, the per-thread pinned words.  The entry points of a stand-alone op sit at the end of its own file.
+// Every rasteriser entry point resolves (frame, g) and its state buffers through one Call; it keeps its own checks, early-outs and stages.
 // No torch types, no exceptions across the boundary, nothing allocated persistently.
 #include <cstdarg>
 #include <cstdio>
@@ -139,7 +140,7 @@ namespace {
 
 // ---- buffer layouts ------------------------------------------------------------------------------
 // A layout = the byte offsets of a state buffer's regions (every region 256-B aligned) + its total; a view = the typed pointers of one
-// buffer carved by that layout.  Every entry point carves once, through these (launch.h: Carver, at<T>).
+// buffer carved by that layout.  A call carves each buffer once, in Call::bind below (launch.h: Carver, at<T>).
 constexpr int kMaxTilesPerAxis = SR_MAX_TILES_PER_AXIS;   // binning.hip kXpMaxBins: 10-bit row / column fields, 1024-entry LDS histograms
 
 struct GeomLayout {
@@ -254,9 +255,50 @@ WorkspaceLayout workspace_layout(uint32_t D, int color_channels) {
     return L;
 }
 struct WorkspaceView { float4* records; uint8_t* written; };
-WorkspaceView workspace_view(void* workspace, uint32_t D, int color_channels) {
-    const WorkspaceLayout L = workspace_layout(D, color_channels);
+WorkspaceView workspace_view(void* workspace, const WorkspaceLayout& L) {
     return WorkspaceView{at<float4>(workspace, L.records), at<uint8_t>(workspace, L.written)};
+}
+
+// per-class state between the forward and the backward of the class pass.  (The class-ordered copy of the tile lists lives in the binning
+// buffer's `columns` region -- the column items of the expanding partition are dead once pass Y has run -- and the class id bytes in the
+// geometry buffer's `sh_jac` region: the class pass has no SH colour.)
+struct ClassLayout { size_t state, last, tile_total, ranges, total; };
+ClassLayout class_layout(int W, int H, int n_classes) {
+    ClassLayout L{};
+    const size_t hw = (size_t)(W > 0 ? W : 1) * (size_t)(H > 0 ? H : 1), n = (size_t)(n_classes > 0 ? n_classes : 1);
+    const size_t tiles = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);   // (sized for the smallest tile of the sweep, 8x8)
+    Carver c;
+    L.state = c.take(n * 3 * hw * 4);
+    L.last = c.take(n * hw * 4);
+    L.tile_total = c.take((tiles > 0 ? tiles : 1) * n * 4);
+    L.ranges = c.take((tiles > 0 ? tiles : 1) * n * 8);
+    L.total = c.off;
+    return L;
+}
+struct ClassView {
+    float* state; uint32_t* last; uint32_t* tile_total; uint2* ranges;
+    uint8_t* ids; uint16_t* hit;   // of the class-shared state alone (below); nullptr in a class image
+};
+ClassView class_view(void* class_image, const ClassLayout& L) {
+    return ClassView{at<float>(class_image, L.state), at<uint32_t>(class_image, L.last), at<uint32_t>(class_image, L.tile_total), at<uint2>(class_image, L.ranges),
+                     nullptr, nullptr};
+}
+
+// The state of the per-class pass on the binning of a colour pass (sr_class_*_shared): a class image + what the colour pass keeps for itself.
+struct ClassSharedLayout { ClassLayout C; size_t ids, hit, total; };
+ClassSharedLayout class_shared_layout(int P, int W, int H, int n_classes, uint32_t D) {
+    ClassSharedLayout L{};
+    L.C = class_layout(W, H, n_classes);
+    Carver c{L.C.total};                           // behind the stand-alone pass's regions
+    L.ids = c.take((size_t)(P > 0 ? P : 1));       // class byte per Gaussian (the colour pass owns the sh_jac region here)
+    L.hit = c.take((size_t)(D > 0 ? D : 1) * 2);   // this pass's own (entry, quadrant) hit masks: the colour pass keeps the binning buffer's
+    L.total = c.off;
+    return L;
+}
+ClassView class_shared_view(void* class_state, const ClassSharedLayout& L) {
+    ClassView C = class_view(class_state, L.C);
+    C.ids = at<uint8_t>(class_state, L.ids); C.hit = at<uint16_t>(class_state, L.hit);
+    return C;
 }
 
 struct TileShape { int w, h; };
@@ -306,6 +348,21 @@ int check_backward_frame(const SrFrame* frame) {
     return SR_OK;
 }
 
+// The preconditions of the four class entry points.  They differ in where the class ids come from -- column 0 of colors_precomp[P,3] (the
+// stand-alone pass) or an int32 array of their own (the pass on the binning of a colour pass, whose colours stay what they are) -- and in
+// whether a precomputed transMat is refused.
+enum class ClassIds { kInColors, kOwnArray };
+int check_class_pass(const SrFrame* frame, const SrGaussians* g, int n_classes, ClassIds ids, bool refuse_transmat) {
+    if (int rc = check_common(frame, g)) return rc;
+    if (frame->flags & SR_FLAG_BINNING_CAPACITY) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY serves the operator (sr_forward_* / sr_backward*), not the per-class pass");
+    if (n_classes < 1 || n_classes > 6) return fail(SR_ERR_UNSUPPORTED, "n_classes %d not in 1..6", n_classes);
+    // (every tile shape check_common accepts: 8x8, 16x8, 16x16, 32x8, 32x16)
+    if (ids == ClassIds::kInColors && g->P > 0 && (g->shs || !g->colors_precomp || (g->color_channels != 0 && g->color_channels != 3)))
+        return fail(SR_ERR_INVALID_ARGUMENT, "the per-class distortion pass takes the class ids in colors_precomp[P,3] (column 0), no SHs");
+    if (refuse_transmat && g->transMat_precomp) return fail(SR_ERR_UNSUPPORTED, "the per-class pass takes scales and rotations, not a precomputed transMat");
+    return SR_OK;
+}
+
 FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
     FrameDev f{};
     f.W = frame->image_width; f.H = frame->image_height;
@@ -330,9 +387,11 @@ FrameDev make_frame(const SrFrame* frame, const SrGaussians* g) {
     f.overflow = nullptr;   // (set by the backward entry points in capacity mode)
     return f;
 }
-// what the per-Gaussian backward kernels read of the geometry state
-void set_backward_state(FrameDev* f, const SrFrame* frame, const GeomView& G) {
-    f->first = G.first; f->first_base = G.block_base; f->sh_jac = G.sh_jac;
+// what the per-Gaussian backward kernels read of the geometry state (`with_sh_jac` false: the class pass on a colour pass's binning, whose
+// sh_jac region is the colour pass's)
+void set_backward_state(FrameDev* f, const SrFrame* frame, const GeomView& G, bool with_sh_jac) {
+    f->first = G.first; f->first_base = G.block_base;
+    if (with_sh_jac) f->sh_jac = G.sh_jac;
     if (frame->flags & SR_FLAG_BINNING_CAPACITY) f->overflow = G.counts + kCountOverflow;
 }
 
@@ -390,6 +449,84 @@ int choose_blend(const SrFrame* frame, const FrameDev& f, bool forward_call, Ble
     return SR_OK;
 }
 
+// ---- one call's arguments, resolved once ---------------------------------------------------------------------------------------------
+// The two refusals of a caller's buffer; each text stands here and nowhere else.
+enum BufferKind { kGeom, kBinning, kImage, kClassImage, kClassState, kWorkspace };
+int check_present(BufferKind kind, const void* p) {
+    static const char* const text[] = {"geom is NULL", "binning is NULL", "image is NULL", "class_image is NULL", "class_state is NULL", "workspace is NULL"};
+    return p ? SR_OK : fail(SR_ERR_INVALID_ARGUMENT, "%s", text[kind]);
+}
+int check_size(BufferKind kind, size_t have, size_t need) {
+    static const char* const text[] = {"geom buffer %zu < %zu", "binning buffer %zu < %zu", "image buffer %zu < %zu",
+                                       "class image buffer %zu < %zu", "class state buffer %zu < %zu", "workspace %zu < %zu"};
+    return have >= need ? SR_OK : fail(SR_ERR_BUFFER_TOO_SMALL, text[kind], have, need);
+}
+
+// The buffers an entry point asks bind() for, named where it asks; `wanted` false: not needed in this call.  cls: the class image, or the
+// class-shared state where the call's ClassPass has the ids in an array of their own.  channels: of the workspace's gradient records.
+struct Raw { void* p = nullptr; size_t bytes = 0; bool wanted = false; };
+struct Buffers {
+    Raw geom_, binning_, image_, cls_, workspace_; int channels_ = 0;
+    Buffers& geom(void* p, size_t n, bool wanted = true) { geom_ = Raw{p, n, wanted}; return *this; }
+    Buffers& binning(void* p, size_t n) { binning_ = Raw{p, n, true}; return *this; }
+    Buffers& image(void* p, size_t n, bool wanted = true) { image_ = Raw{p, n, wanted}; return *this; }
+    Buffers& cls(void* p, size_t n) { cls_ = Raw{p, n, true}; return *this; }
+    Buffers& workspace(void* p, size_t n, int channels) { workspace_ = Raw{p, n, true}; channels_ = channels; return *this; }
+};
+// Where bind() looks at the geometry buffer: before the call's other buffers (the backward calls and sr_debug_pair_decisions), or after
+// all of them (the forward calls, which did so inside bin_duplicates).  Each entry point keeps the order it had; the two are not unified.
+enum class GeomOrder { kFirst, kLast };
+
+// The checks of (frame, g): check_common alone; with choose_blend (the colour pass's calls that blend); check_class_pass with a ClassPass.
+enum class Checks { kCommon, kBlend, kClassPass };
+struct ClassPass { int n_classes = 0; ClassIds ids = ClassIds::kInColors; bool refuse_transmat = false; };
+
+// What an entry point works with, in two steps because its own argument checks and P == 0 / D == 0 early-outs lie between them: open()
+// checks (frame, g) and fills P, f, blend and s; bind() checks the buffers the call needs and carves their views, each layout computed
+// once and each view carved from the layout its size was checked against.  The views of a buffer that was not bound stay NULL.
+struct Call {
+    const SrFrame* frame; const SrGaussians* g; bool backward; ClassPass cp;
+    int P; FrameDev f; BlendChoice blend; hipStream_t s;
+    GeomLayout GL;   // (the scan and the sort take region sizes of it)
+    GeomView G; BinView B; ImgView I; ClassView C; WorkspaceView ws;
+
+    int open(const SrFrame* frame_, const SrGaussians* g_, Checks checks, bool backward_, void* stream, ClassPass cp_ = ClassPass{}) {
+        frame = frame_; g = g_; backward = backward_; cp = cp_;
+        if (int rc = checks == Checks::kClassPass ? check_class_pass(frame, g, cp.n_classes, cp.ids, cp.refuse_transmat) : check_common(frame, g)) return rc;
+        if (backward) if (int rc = check_backward_frame(frame)) return rc;
+        P = g->P; f = make_frame(frame, g); s = static_cast<hipStream_t>(stream);
+        return checks == Checks::kBlend ? choose_blend(frame, f, !backward, &blend) : SR_OK;
+    }
+
+    // Within one look the NULL buffers are refused before the short ones, each in argument order, as every entry point did.
+    int bind(uint32_t D, GeomOrder geom_order, const Buffers& b) {
+        const bool shared = cp.ids == ClassIds::kOwnArray;
+        const BinLayout BL = b.binning_.wanted ? bin_layout(D, f.W, f.H) : BinLayout{};
+        const ImgLayout IL = b.image_.wanted ? img_layout(f.W, f.H) : ImgLayout{};
+        const ClassLayout CL = b.cls_.wanted && !shared ? class_layout(f.W, f.H, cp.n_classes) : ClassLayout{};
+        const ClassSharedLayout SL = b.cls_.wanted && shared ? class_shared_layout(P, f.W, f.H, cp.n_classes, D) : ClassSharedLayout{};
+        const WorkspaceLayout WL = b.workspace_.wanted ? workspace_layout(D, b.channels_) : WorkspaceLayout{};
+        if (b.geom_.wanted) GL = geom_layout(P);
+        const struct { const Raw& raw; BufferKind kind; size_t need; } all[] = {
+            {b.geom_, kGeom, GL.total}, {b.binning_, kBinning, BL.total}, {b.image_, kImage, IL.total},
+            {b.cls_, shared ? kClassState : kClassImage, shared ? SL.total : CL.total}, {b.workspace_, kWorkspace, WL.total}};
+        auto refusal = [&](int from, int to) {   // of all[from, to): the first NULL one, else the first short one
+            for (int i = from; i < to; ++i) if (all[i].raw.wanted) if (int rc = check_present(all[i].kind, all[i].raw.p)) return rc;
+            for (int i = from; i < to; ++i) if (all[i].raw.wanted) if (int rc = check_size(all[i].kind, all[i].raw.bytes, all[i].need)) return rc;
+            return (int)SR_OK;
+        };
+        if (int rc = refusal(geom_order == GeomOrder::kFirst ? 0 : 1, 5)) return rc;
+        if (geom_order == GeomOrder::kLast) if (int rc = refusal(0, 1)) return rc;
+        if (b.geom_.wanted) G = geom_view(b.geom_.p, GL);
+        if (b.binning_.wanted) B = bin_view(b.binning_.p, BL);
+        if (b.image_.wanted) I = img_view(b.image_.p, IL);
+        if (b.cls_.wanted) C = shared ? class_shared_view(b.cls_.p, SL) : class_view(b.cls_.p, CL);
+        if (b.workspace_.wanted) ws = workspace_view(b.workspace_.p, WL);
+        if (backward && b.geom_.wanted) set_backward_state(&f, frame, G, !shared);
+        return SR_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -406,7 +543,7 @@ size_t sr_backward_workspace_bytes(int32_t P, uint32_t num_rendered, int32_t col
 int sr_geom_view(void* geom, size_t geom_bytes, int32_t P, SrGeomView* out) {
     if (!geom || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const GeomLayout L = geom_layout(P);
-    if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
+    if (int rc = check_size(kGeom, geom_bytes, L.total)) return rc;
     const GeomView G = geom_view(geom, L);
     out->splats = reinterpret_cast<float*>(G.recs); out->depth_keys = G.depth_keys;
     out->tiles_touched = G.tiles_touched; out->clamped = G.clamped;
@@ -419,7 +556,7 @@ int sr_binning_view(void* binning, size_t binning_bytes, int32_t P, uint32_t D, 
     (void)P;
     if (!binning || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const BinLayout L = bin_layout(D, W, H);
-    if (binning_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, L.total);
+    if (int rc = check_size(kBinning, binning_bytes, L.total)) return rc;
     const BinView B = bin_view(binning, L);
     out->point_list = B.point_list;
     out->ranges = reinterpret_cast<uint32_t*>(B.ranges); out->tile_order = B.order;
@@ -429,7 +566,7 @@ int sr_binning_view(void* binning, size_t binning_bytes, int32_t P, uint32_t D, 
 int sr_image_view(void* image, size_t image_bytes, int32_t W, int32_t H, SrImageView* out) {
     if (!image || !out) return fail(SR_ERR_INVALID_ARGUMENT, "NULL argument");
     const ImgLayout L = img_layout(W, H);
-    if (image_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, L.total);
+    if (int rc = check_size(kImage, image_bytes, L.total)) return rc;
     const ImgView I = img_view(image, L);
     out->final_T = I.final_T; out->n_contrib = I.n_contrib;
     return SR_OK;
@@ -437,17 +574,15 @@ int sr_image_view(void* image, size_t image_bytes, int32_t W, int32_t H, SrImage
 
 int sr_forward_plan(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, int32_t* radii,
                     uint32_t* num_rendered_host, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kCommon, false, stream)) return rc;
     if (!num_rendered_host) return fail(SR_ERR_INVALID_ARGUMENT, "num_rendered_host is NULL");
     *num_rendered_host = 0;
-    const int P = g->P;
+    const int P = c.P;
     if (P == 0) return SR_OK;
     if (!geom || !radii) return fail(SR_ERR_INVALID_ARGUMENT, "geom / radii is NULL");
-    const GeomLayout L = geom_layout(P);
-    if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-    const GeomView G = geom_view(geom, L);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    FrameDev f = make_frame(frame, g);
+    if (int rc = c.bind(0, GeomOrder::kLast, Buffers{}.geom(geom, geom_bytes))) return rc;
+    const GeomLayout& L = c.GL; const GeomView& G = c.G; hipStream_t s = c.s; FrameDev& f = c.f;
     f.sh_jac = (frame->flags & SR_FLAG_FORWARD_ONLY) ? nullptr : G.sh_jac;   // (forward only: K8, its one reader, will not run)
     {
         StageTimer t(SR_STAGE_PREPROCESS, s);
@@ -502,18 +637,13 @@ int sr_forward_plan(const SrFrame* frame, const SrGaussians* g, void* geom, size
 }
 
 namespace {
-// K3..K5 (duplicate emission, tile partition, tile ranges + dispatch order): shared by the blend forward and the per-class pass
-int bin_duplicates(const SrFrame* frame, const SrGaussians* g, const FrameDev& f, void* geom, size_t geom_bytes, const BinView& B,
-                   uint32_t D, hipStream_t s, float4** recs_out) {
-    const int P = g->P;
-    const int n_tiles = f.tiles_x * f.tiles_y;
-    *recs_out = nullptr;
+// K3..K5 (duplicate emission, tile partition, tile ranges + dispatch order): shared by the blend forward and the per-class pass.  The call
+// has bound its binning buffer and, where there is anything to bin (P > 0 and D > 0), its geometry buffer.
+int bin_duplicates(const Call& c, uint32_t D) {
+    const SrFrame* frame = c.frame; const FrameDev& f = c.f; hipStream_t s = c.s;
+    const GeomLayout& L = c.GL; const GeomView& G = c.G; const BinView& B = c.B;
+    const int P = c.P, n_tiles = f.tiles_x * f.tiles_y;
     if (P > 0 && D > 0) {
-        if (!geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL");
-        const GeomLayout L = geom_layout(P);
-        if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-        const GeomView G = geom_view(geom, L);
-        *recs_out = G.recs;
         if (f.tiles_x > kMaxTilesPerAxis || f.tiles_y > kMaxTilesPerAxis)
             return fail(SR_ERR_INVALID_ARGUMENT, "%d x %d tiles: at most %d per axis (use a larger tile)", f.tiles_x, f.tiles_y, kMaxTilesPerAxis);
         if (L.temp_bytes < expand_x_hist_bytes(P, f.tiles_x)) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom scratch too small for the column histogram");
@@ -541,100 +671,51 @@ int bin_duplicates(const SrFrame* frame, const SrGaussians* g, const FrameDev& f
     }
     return debug_sync(frame, s, "tile_ranges");
 }
-
-// per-class state between the forward and the backward of the class pass.  (The class-ordered copy of the tile lists lives in the binning
-// buffer's `columns` region -- the column items of the expanding partition are dead once pass Y has run -- and the class id bytes in the
-// geometry buffer's `sh_jac` region: the class pass has no SH colour.)
-struct ClassLayout { size_t state, last, tile_total, ranges, total; };
-ClassLayout class_layout(int W, int H, int n_classes) {
-    ClassLayout L{};
-    const size_t hw = (size_t)(W > 0 ? W : 1) * (size_t)(H > 0 ? H : 1), n = (size_t)(n_classes > 0 ? n_classes : 1);
-    const size_t tiles = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);   // (sized for the smallest tile of the sweep, 8x8)
-    Carver c;
-    L.state = c.take(n * 3 * hw * 4);
-    L.last = c.take(n * hw * 4);
-    L.tile_total = c.take((tiles > 0 ? tiles : 1) * n * 4);
-    L.ranges = c.take((tiles > 0 ? tiles : 1) * n * 8);
-    L.total = c.off;
-    return L;
-}
-struct ClassView { float* state; uint32_t* last; uint32_t* tile_total; uint2* ranges; };
-ClassView class_view(void* class_image, const ClassLayout& L) {
-    return ClassView{at<float>(class_image, L.state), at<uint32_t>(class_image, L.last), at<uint32_t>(class_image, L.tile_total), at<uint2>(class_image, L.ranges)};
-}
-
-// The preconditions of the four class entry points.  They differ in where the class ids come from -- column 0 of colors_precomp[P,3] (the
-// stand-alone pass) or an int32 array of their own (the pass on the binning of a colour pass, whose colours stay what they are) -- and in
-// whether a precomputed transMat is refused.
-enum class ClassIds { kInColors, kOwnArray };
-int check_class_pass(const SrFrame* frame, const SrGaussians* g, int n_classes, ClassIds ids, bool refuse_transmat) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (frame->flags & SR_FLAG_BINNING_CAPACITY) return fail(SR_ERR_UNSUPPORTED, "SR_FLAG_BINNING_CAPACITY serves the operator (sr_forward_* / sr_backward*), not the per-class pass");
-    if (n_classes < 1 || n_classes > 6) return fail(SR_ERR_UNSUPPORTED, "n_classes %d not in 1..6", n_classes);
-    // (every tile shape check_common accepts: 8x8, 16x8, 16x16, 32x8, 32x16)
-    if (ids == ClassIds::kInColors && g->P > 0 && (g->shs || !g->colors_precomp || (g->color_channels != 0 && g->color_channels != 3)))
-        return fail(SR_ERR_INVALID_ARGUMENT, "the per-class distortion pass takes the class ids in colors_precomp[P,3] (column 0), no SHs");
-    if (refuse_transmat && g->transMat_precomp) return fail(SR_ERR_UNSUPPORTED, "the per-class pass takes scales and rotations, not a precomputed transMat");
-    return SR_OK;
-}
 }  // namespace
 
 int sr_forward_render(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning,
                       size_t binning_bytes, void* image, size_t image_bytes, uint32_t D, float* out_color,
                       float* out_allmap, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
-    const FrameDev f = make_frame(frame, g);
-    BlendChoice blend;
-    if (int rc = choose_blend(frame, f, true, &blend)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kBlend, false, stream)) return rc;
     const bool fwd_only = (frame->flags & SR_FLAG_FORWARD_ONLY) != 0;   // no backward follows: its state (image buffer, hit masks) is not written
     if (!binning || (!image && !fwd_only) || !out_color || !out_allmap) return fail(SR_ERR_INVALID_ARGUMENT, "binning / image / out_color / out_allmap is NULL");
-    const int W = frame->image_width, H = frame->image_height;
-    const BinLayout BL = bin_layout(D, W, H);
-    const ImgLayout IL = img_layout(W, H);
-    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
-    if (!fwd_only && image_bytes < IL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, IL.total);
-    const BinView B = bin_view(binning, BL);
-    const ImgView I = fwd_only ? ImgView{nullptr, nullptr} : img_view(image, IL);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float4* recs = nullptr;
-    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, B, D, s, &recs)) return rc;
+    // The geometry buffer: needed where there is anything to bin; otherwise taken (and then checked like any other) if the caller gives one,
+    // for the frame counts the emission scan left in it -- which the device-picked kernel reads, so that kernel insists on it.
+    const bool binned = c.P > 0 && D > 0;
+    if (int rc = c.bind(D, GeomOrder::kLast, Buffers{}.geom(geom, geom_bytes, binned || geom).binning(binning, binning_bytes).image(image, image_bytes, !fwd_only))) return rc;
+    if (c.blend.forward == ForwardBlend::kDevicePicked) if (int rc = check_present(kGeom, geom)) return rc;
+    if (int rc = bin_duplicates(c, D)) return rc;
     {
-        StageTimer t(SR_STAGE_BLEND_FWD, s);
-        const GeomView G = geom_view(geom, geom_layout(g->P));   // (D and the visible count, left in the geometry state by the emission scan)
-        SR_HIP(launch_render_forward(f, B.ranges, B.order, B.point_list, recs, g->colors_precomp, out_color, out_allmap, I.final_T, I.n_contrib,
-                                     fwd_only ? nullptr : B.hit_mask, blend, reinterpret_cast<unsigned long long*>(frame->blend_counters), G.counts, s));
+        StageTimer t(SR_STAGE_BLEND_FWD, c.s);
+        SR_HIP(launch_render_forward(c.f, c.B.ranges, c.B.order, c.B.point_list, binned ? c.G.recs : nullptr, g->colors_precomp, out_color, out_allmap,
+                                     c.I.final_T, c.I.n_contrib, fwd_only ? nullptr : c.B.hit_mask, c.blend,
+                                     reinterpret_cast<unsigned long long*>(frame->blend_counters), c.G.counts, c.s));
     }
-    return debug_sync(frame, s, "render_forward");
+    return debug_sync(frame, c.s, "render_forward");
 }
 
 size_t sr_class_image_bytes(int32_t W, int32_t H, int32_t n_classes) { return class_layout(W, H, n_classes).total; }
 
 int sr_class_forward_render(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, void* geom, size_t geom_bytes, void* binning,
                             size_t binning_bytes, void* class_image, size_t class_image_bytes, uint32_t D, float* out_dist, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kInColors, false)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kClassPass, false, stream, ClassPass{n_classes, ClassIds::kInColors, false})) return rc;
     if (!binning || !class_image || !out_dist) return fail(SR_ERR_INVALID_ARGUMENT, "binning / class_image / out_dist is NULL");
-    if (g->P > 0 && !geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL (the class ids of the P Gaussians are staged in it, even when no duplicate was emitted)");
-    const int W = frame->image_width, H = frame->image_height;
-    const BinLayout BL = bin_layout(D, W, H);
-    const ClassLayout CL = class_layout(W, H, n_classes);
-    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
-    if (class_image_bytes < CL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class image buffer %zu < %zu", class_image_bytes, CL.total);
-    const BinView B = bin_view(binning, BL);
-    const ClassView C = class_view(class_image, CL);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const FrameDev f = make_frame(frame, g);
-    float4* recs = nullptr;
-    if (int rc = bin_duplicates(frame, g, f, geom, geom_bytes, B, D, s, &recs)) return rc;
+    if (c.P > 0 && !geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL (the class ids of the P Gaussians are staged in it, even when no duplicate was emitted)");
+    if (int rc = c.bind(D, GeomOrder::kLast, Buffers{}.geom(geom, geom_bytes, c.P > 0).binning(binning, binning_bytes).cls(class_image, class_image_bytes))) return rc;
+    const FrameDev& f = c.f; const BinView& B = c.B; const ClassView& C = c.C; hipStream_t s = c.s;
+    if (int rc = bin_duplicates(c, D)) return rc;
     {
         // every tile list, stably partitioned by class: [class 0 by depth | class 1 by depth | ...] + a (begin, end) pair per (tile, class)
         StageTimer t(SR_STAGE_CLASS_PARTITION, s);
-        uint8_t* ids = g->P > 0 && geom ? reinterpret_cast<uint8_t*>(geom_view(geom, geom_layout(g->P)).sh_jac) : nullptr;
-        SR_HIP(launch_class_partition(g->P, f.tiles_x * f.tiles_y, n_classes, g->colors_precomp, nullptr, B.ranges, B.point_list, ids, B.class_list(), C.ranges, s));
+        uint8_t* ids = reinterpret_cast<uint8_t*>(c.G.sh_jac);   // (nullptr where P == 0: no geometry buffer was bound)
+        SR_HIP(launch_class_partition(c.P, f.tiles_x * f.tiles_y, n_classes, g->colors_precomp, nullptr, B.ranges, B.point_list, ids, B.class_list(), C.ranges, s));
     }
     if (int rc = debug_sync(frame, s, "class_partition")) return rc;
     {
         StageTimer t(SR_STAGE_CLASS_FWD, s);
-        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), recs, out_dist, C.state, C.last, C.tile_total, B.hit_mask,
+        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), c.P > 0 && D > 0 ? c.G.recs : nullptr, out_dist, C.state, C.last, C.tile_total, B.hit_mask,
                                     (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
     }
     return debug_sync(frame, s, "class_forward");
@@ -643,25 +724,14 @@ int sr_class_forward_render(const SrFrame* frame, const SrGaussians* g, int32_t 
 int sr_class_backward(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, const int32_t* radii, void* geom, size_t geom_bytes,
                       void* binning, size_t binning_bytes, void* class_image, size_t class_image_bytes, uint32_t D, const float* dL_ddist,
                       void* workspace, size_t workspace_bytes, const SrGradients* grads, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kInColors, false)) return rc;
-    if (int rc = check_backward_frame(frame)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kClassPass, true, stream, ClassPass{n_classes, ClassIds::kInColors, false})) return rc;
     if (!grads) return fail(SR_ERR_INVALID_ARGUMENT, "grads is NULL");
-    const int P = g->P;
+    const int P = c.P;
     if (P == 0) return SR_OK;
-    if (!radii || !geom || !binning || !class_image || !dL_ddist || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
-    const int W = frame->image_width, H = frame->image_height;
-    const GeomLayout L = geom_layout(P);
-    const BinLayout BL = bin_layout(D, W, H);
-    const ClassLayout CL = class_layout(W, H, n_classes);
-    if (geom_bytes < L.total || binning_bytes < BL.total || class_image_bytes < CL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
-    if (workspace_bytes < workspace_layout(D, 3).total) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, workspace_layout(D, 3).total);
-    const GeomView G = geom_view(geom, L);
-    const BinView B = bin_view(binning, BL);
-    const ClassView C = class_view(class_image, CL);
-    const WorkspaceView ws = workspace_view(workspace, D, 3);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    FrameDev f = make_frame(frame, g);
-    f.first = G.first; f.first_base = G.block_base; f.sh_jac = G.sh_jac;
+    if (!radii || !dL_ddist) return fail(SR_ERR_INVALID_ARGUMENT, "radii / dL_ddist is NULL");
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).binning(binning, binning_bytes).cls(class_image, class_image_bytes).workspace(workspace, workspace_bytes, 3))) return rc;
+    const FrameDev& f = c.f; const GeomView& G = c.G; const BinView& B = c.B; const ClassView& C = c.C; const WorkspaceView& ws = c.ws; hipStream_t s = c.s;
     {
         StageTimer t(SR_STAGE_CLASS_BWD, s);
         if (D > 0) SR_HIP(launch_zero_bytes(ws.written, D, s));
@@ -678,50 +748,25 @@ int sr_class_backward(const SrFrame* frame, const SrGaussians* g, int32_t n_clas
 }
 
 // ---- the per-class pass on the binning of a colour pass (one plan, one binning, one K8 for both: SURVEY.md 8f N1 in full) -------------
-namespace {
-struct ClassSharedLayout { ClassLayout C; size_t ids, hit, total; };
-ClassSharedLayout class_shared_layout(int P, int W, int H, int n_classes, uint32_t D) {
-    ClassSharedLayout L{};
-    L.C = class_layout(W, H, n_classes);
-    Carver c{L.C.total};                           // behind the stand-alone pass's regions
-    L.ids = c.take((size_t)(P > 0 ? P : 1));       // class byte per Gaussian (the colour pass owns the sh_jac region here)
-    L.hit = c.take((size_t)(D > 0 ? D : 1) * 2);   // this pass's own (entry, quadrant) hit masks: the colour pass keeps the binning buffer's
-    L.total = c.off;
-    return L;
-}
-}  // namespace
-
 size_t sr_class_shared_bytes(int32_t P, int32_t W, int32_t H, int32_t n_classes, uint32_t D) { return class_shared_layout(P, W, H, n_classes, D).total; }
 
 int sr_class_forward_shared(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, const int32_t* classes, void* geom, size_t geom_bytes,
                             void* binning, size_t binning_bytes, void* class_state, size_t class_state_bytes, uint32_t D, float* out_dist, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kOwnArray, true)) return rc;
-    if (!binning || !class_state || !out_dist || (g->P > 0 && !classes)) return fail(SR_ERR_INVALID_ARGUMENT, "binning / class_state / out_dist / classes is NULL");
-    const int W = frame->image_width, H = frame->image_height, P = g->P;
-    const BinLayout BL = bin_layout(D, W, H);
-    const ClassSharedLayout SL = class_shared_layout(P, W, H, n_classes, D);
-    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
-    if (class_state_bytes < SL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "class state buffer %zu < %zu", class_state_bytes, SL.total);
-    float4* recs = nullptr;
-    if (P > 0 && D > 0) {
-        if (!geom) return fail(SR_ERR_INVALID_ARGUMENT, "geom is NULL");
-        const GeomLayout L = geom_layout(P);
-        if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-        recs = geom_view(geom, L).recs;
-    }
-    const BinView B = bin_view(binning, BL);
-    const ClassView C = class_view(class_state, SL.C);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const FrameDev f = make_frame(frame, g);
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kClassPass, false, stream, ClassPass{n_classes, ClassIds::kOwnArray, true})) return rc;
+    const int P = c.P;
+    if (!binning || !class_state || !out_dist || (P > 0 && !classes)) return fail(SR_ERR_INVALID_ARGUMENT, "binning / class_state / out_dist / classes is NULL");
+    // (the geometry buffer: for the records alone, so only where something was binned)
+    if (int rc = c.bind(D, GeomOrder::kLast, Buffers{}.geom(geom, geom_bytes, P > 0 && D > 0).binning(binning, binning_bytes).cls(class_state, class_state_bytes))) return rc;
+    const FrameDev& f = c.f; const BinView& B = c.B; const ClassView& C = c.C; hipStream_t s = c.s;
     {
         StageTimer t(SR_STAGE_CLASS_PARTITION, s);
-        SR_HIP(launch_class_partition(P, f.tiles_x * f.tiles_y, n_classes, nullptr, classes, B.ranges, B.point_list, at<uint8_t>(class_state, SL.ids), B.class_list(),
-                                      C.ranges, s));
+        SR_HIP(launch_class_partition(P, f.tiles_x * f.tiles_y, n_classes, nullptr, classes, B.ranges, B.point_list, C.ids, B.class_list(), C.ranges, s));
     }
     if (int rc = debug_sync(frame, s, "class_partition")) return rc;
     {
         StageTimer t(SR_STAGE_CLASS_FWD, s);
-        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), recs, out_dist, C.state, C.last, C.tile_total, at<uint16_t>(class_state, SL.hit),
+        SR_HIP(launch_class_forward(f, n_classes, C.ranges, B.order, B.class_list(), c.G.recs, out_dist, C.state, C.last, C.tile_total, C.hit,
                                     (frame->flags & SR_FLAG_NO_QUADRANT_CULL) ? 0 : 1, s));
     }
     return debug_sync(frame, s, "class_forward");
@@ -730,71 +775,30 @@ int sr_class_forward_shared(const SrFrame* frame, const SrGaussians* g, int32_t 
 int sr_class_backward_shared(const SrFrame* frame, const SrGaussians* g, int32_t n_classes, void* geom, size_t geom_bytes, void* binning,
                              size_t binning_bytes, void* class_state, size_t class_state_bytes, uint32_t D, const float* dL_ddist, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    if (int rc = check_class_pass(frame, g, n_classes, ClassIds::kOwnArray, false)) return rc;
-    if (int rc = check_backward_frame(frame)) return rc;
-    const int P = g->P;
-    if (P == 0 || D == 0) return SR_OK;
-    if (!geom || !binning || !class_state || !dL_ddist || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
-    const int W = frame->image_width, H = frame->image_height;
-    const GeomLayout L = geom_layout(P);
-    const BinLayout BL = bin_layout(D, W, H);
-    const ClassSharedLayout SL = class_shared_layout(P, W, H, n_classes, D);
-    if (geom_bytes < L.total || binning_bytes < BL.total || class_state_bytes < SL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
-    const size_t ws_bytes = workspace_layout(D, g->color_channels).total;
-    if (workspace_bytes < ws_bytes) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, ws_bytes);
-    const GeomView G = geom_view(geom, L);
-    const BinView B = bin_view(binning, BL);
-    const ClassView C = class_view(class_state, SL.C);
-    // the records and flags sr_backward_blend of the SAME frame left in the workspace: this pass adds to them
-    const WorkspaceView ws = workspace_view(workspace, D, g->color_channels);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    FrameDev f = make_frame(frame, g);
-    f.first = G.first; f.first_base = G.block_base;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kClassPass, true, stream, ClassPass{n_classes, ClassIds::kOwnArray, false})) return rc;
+    if (c.P == 0 || D == 0) return SR_OK;
+    if (!dL_ddist) return fail(SR_ERR_INVALID_ARGUMENT, "dL_ddist is NULL");
+    // (the workspace: the records and flags sr_backward_blend of the SAME frame left in it -- this pass adds to them)
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).binning(binning, binning_bytes).cls(class_state, class_state_bytes)
+                                                       .workspace(workspace, workspace_bytes, g->color_channels))) return rc;
+    const BinView& B = c.B; const ClassView& C = c.C;
     {
-        StageTimer t(SR_STAGE_CLASS_BWD, s);
-        SR_HIP(launch_class_backward(f, n_classes, C.ranges, B.order, B.class_list(), G.recs, C.state, C.last, C.tile_total, dL_ddist, at<uint16_t>(class_state, SL.hit),
-                                     ws.records, ws.written, (int)(record_bytes(g->color_channels) / 16), s));
+        StageTimer t(SR_STAGE_CLASS_BWD, c.s);
+        SR_HIP(launch_class_backward(c.f, n_classes, C.ranges, B.order, B.class_list(), c.G.recs, C.state, C.last, C.tile_total, dL_ddist, C.hit,
+                                     c.ws.records, c.ws.written, (int)(record_bytes(g->color_channels) / 16), c.s));
     }
-    return debug_sync(frame, s, "class_backward_shared");
+    return debug_sync(frame, c.s, "class_backward_shared");
 }
-
-namespace {
-struct BackwardCtx {
-    int P; GeomView G; BinView B; ImgView I; WorkspaceView ws; FrameDev f; BlendChoice blend; hipStream_t s;
-};
-// argument checks and buffer carving shared by the backward entry points
-int backward_ctx(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes,
-                 void* image, size_t image_bytes, uint32_t D, void* workspace, size_t workspace_bytes, void* stream, BackwardCtx* c) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (int rc = check_backward_frame(frame)) return rc;
-    c->f = make_frame(frame, g);
-    if (int rc = choose_blend(frame, c->f, false, &c->blend)) return rc;
-    c->P = g->P;
-    if (c->P == 0) return SR_OK;
-    if (!geom || !binning || !image || !workspace) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
-    const int W = frame->image_width, H = frame->image_height;
-    const GeomLayout L = geom_layout(c->P);
-    const BinLayout BL = bin_layout(D, W, H);
-    const ImgLayout IL = img_layout(W, H);
-    if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-    if (binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "binning buffer %zu < %zu", binning_bytes, BL.total);
-    if (image_bytes < IL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "image buffer %zu < %zu", image_bytes, IL.total);
-    const size_t ws_bytes = workspace_layout(D, g->color_channels).total;
-    if (workspace_bytes < ws_bytes) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace %zu < %zu", workspace_bytes, ws_bytes);
-    c->G = geom_view(geom, L); c->B = bin_view(binning, BL); c->I = img_view(image, IL);
-    c->ws = workspace_view(workspace, D, g->color_channels);
-    c->s = static_cast<hipStream_t>(stream);
-    set_backward_state(&c->f, frame, c->G);
-    return SR_OK;
-}
-}  // namespace
 
 int sr_backward_blend(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes,
                       void* image, size_t image_bytes, uint32_t D, const float* dL_dcolor, const float* dL_dallmap, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    BackwardCtx c;
-    if (int rc = backward_ctx(frame, g, geom, geom_bytes, binning, binning_bytes, image, image_bytes, D, workspace, workspace_bytes, stream, &c)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kBlend, true, stream)) return rc;
     if (c.P == 0) return SR_OK;
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).binning(binning, binning_bytes).image(image, image_bytes)
+                                                       .workspace(workspace, workspace_bytes, g->color_channels))) return rc;
     if (!dL_dcolor || !dL_dallmap) return fail(SR_ERR_INVALID_ARGUMENT, "dL_dcolor / dL_dallmap is NULL");
     {
         StageTimer t(SR_STAGE_BLEND_BWD, c.s);
@@ -808,32 +812,26 @@ int sr_backward_blend(const SrFrame* frame, const SrGaussians* g, void* geom, si
 
 int sr_backward_colors(const SrFrame* frame, const SrGaussians* g, const int32_t* radii, void* geom, size_t geom_bytes, uint32_t D,
                        void* workspace, size_t workspace_bytes, float* dL_dcolors, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (int rc = check_backward_frame(frame)) return rc;
-    const int P = g->P;
-    if (P == 0) return SR_OK;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kCommon, true, stream)) return rc;
+    if (c.P == 0) return SR_OK;
     if (g->color_channels == 6 || g->color_channels == 9) return fail(SR_ERR_UNSUPPORTED, "sr_backward_colors serves the 3-channel pass");
-    if (!radii || !geom || !workspace || !dL_dcolors) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
-    const GeomLayout L = geom_layout(P);
-    if (geom_bytes < L.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "geom buffer %zu < %zu", geom_bytes, L.total);
-    if (workspace_bytes < workspace_layout(D, g->color_channels).total) return fail(SR_ERR_BUFFER_TOO_SMALL, "workspace too small");
-    const GeomView G = geom_view(geom, L);
-    const WorkspaceView ws = workspace_view(workspace, D, g->color_channels);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    FrameDev f = make_frame(frame, g);
-    set_backward_state(&f, frame, G);
-    StageTimer t(SR_STAGE_PREPROCESS_BWD, s);
-    SR_HIP(launch_color_gradients(P, f, radii, G.clamped, G.recs, ws.records, ws.written, G.tiles_touched, g->shs != nullptr, dL_dcolors, s));
-    return debug_sync(frame, s, "color_gradients");
+    if (!radii || !dL_dcolors) return fail(SR_ERR_INVALID_ARGUMENT, "radii / dL_dcolors is NULL");
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).workspace(workspace, workspace_bytes, g->color_channels))) return rc;
+    StageTimer t(SR_STAGE_PREPROCESS_BWD, c.s);
+    SR_HIP(launch_color_gradients(c.P, c.f, radii, c.G.clamped, c.G.recs, c.ws.records, c.ws.written, c.G.tiles_touched, g->shs != nullptr, dL_dcolors, c.s));
+    return debug_sync(frame, c.s, "color_gradients");
 }
 
 int sr_backward_geometry(const SrFrame* frame, const SrGaussians* g, const int32_t* radii, void* geom, size_t geom_bytes,
                          void* binning, size_t binning_bytes, void* image, size_t image_bytes, uint32_t D, void* workspace,
                          size_t workspace_bytes, const SrGradients* grads, void* stream) {
     if (!grads) return fail(SR_ERR_INVALID_ARGUMENT, "grads is NULL");
-    BackwardCtx c;
-    if (int rc = backward_ctx(frame, g, geom, geom_bytes, binning, binning_bytes, image, image_bytes, D, workspace, workspace_bytes, stream, &c)) return rc;
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kBlend, true, stream)) return rc;
     if (c.P == 0) return SR_OK;
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).binning(binning, binning_bytes).image(image, image_bytes)
+                                                       .workspace(workspace, workspace_bytes, g->color_channels))) return rc;
     if (!radii) return fail(SR_ERR_INVALID_ARGUMENT, "radii is NULL");
     {
         StageTimer t(SR_STAGE_PREPROCESS_BWD, c.s);
@@ -852,16 +850,13 @@ int sr_backward(const SrFrame* frame, const SrGaussians* g, const int32_t* radii
 
 int sr_debug_pair_decisions(const SrFrame* frame, const SrGaussians* g, void* geom, size_t geom_bytes, void* binning, size_t binning_bytes,
                             uint32_t D, uint64_t* valid_bits, uint64_t* use3d_bits, void* stream) {
-    if (int rc = check_common(frame, g)) return rc;
-    if (g->P == 0 || D == 0) return SR_OK;
-    if (!geom || !binning || !valid_bits || !use3d_bits) return fail(SR_ERR_INVALID_ARGUMENT, "NULL buffer argument");
-    const GeomLayout L = geom_layout(g->P);
-    const BinLayout BL = bin_layout(D, frame->image_width, frame->image_height);
-    if (geom_bytes < L.total || binning_bytes < BL.total) return fail(SR_ERR_BUFFER_TOO_SMALL, "state buffer too small");
-    const BinView B = bin_view(binning, BL);
-    const FrameDev f = make_frame(frame, g);
-    SR_HIP(launch_pair_decisions(f, B.ranges, B.point_list, geom_view(geom, L).recs,
-                                 reinterpret_cast<unsigned long long*>(valid_bits), reinterpret_cast<unsigned long long*>(use3d_bits), static_cast<hipStream_t>(stream)));
+    Call c{};
+    if (int rc = c.open(frame, g, Checks::kCommon, false, stream)) return rc;
+    if (c.P == 0 || D == 0) return SR_OK;
+    if (!valid_bits || !use3d_bits) return fail(SR_ERR_INVALID_ARGUMENT, "valid_bits / use3d_bits is NULL");
+    if (int rc = c.bind(D, GeomOrder::kFirst, Buffers{}.geom(geom, geom_bytes).binning(binning, binning_bytes))) return rc;
+    SR_HIP(launch_pair_decisions(c.f, c.B.ranges, c.B.point_list, c.G.recs,
+                                 reinterpret_cast<unsigned long long*>(valid_bits), reinterpret_cast<unsigned long long*>(use3d_bits), c.s));
     return SR_OK;
 }
 

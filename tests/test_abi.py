@@ -355,6 +355,49 @@ def test_workspace_refusals_are_the_recorded_ones(lib):
             assert got == want, (name, what, got)
 
 
+# ---- state-buffer refusals -------------------------------------------------------------------------------------------------------------
+# entry point -> the state buffers it takes: what tests/golden/state_buffer_refusals.json must hold a NULL and a short row for
+STATE_BUFFERS = {
+    "sr_geom_view": ["geom"], "sr_binning_view": ["binning"], "sr_image_view": ["image"],
+    "sr_forward_plan": ["geom"], "sr_forward_render": ["geom", "binning", "image"],
+    "sr_backward_blend": ["geom", "binning", "image", "workspace"], "sr_backward_geometry": ["geom", "binning", "image", "workspace"],
+    "sr_backward": ["geom", "binning", "image", "workspace"], "sr_backward_colors": ["geom", "workspace"],
+    "sr_class_forward_render": ["geom", "binning", "class_image"], "sr_class_backward": ["geom", "binning", "class_image", "workspace"],
+    "sr_class_forward_shared": ["geom", "binning", "class_state"], "sr_class_backward_shared": ["geom", "binning", "class_state", "workspace"],
+    "sr_debug_pair_decisions": ["geom", "binning"],
+}
+
+
+def test_state_buffer_refusals_are_the_recorded_ones(lib):
+    """What every rasteriser entry point answers to a NULL or short state buffer, and to a NULL radii / grads / dL_* / out_* argument: status
+    and whole text as tools/record_state_buffer_refusals.py recorded them from the library of commit d9479ec, whose api.hip is byte for byte
+    that of 01339f2, the last commit with every entry point's argument resolution written out.  The calls are tests/state_buffer_cases.py's.
+    Where that library said "NULL buffer argument", "state buffer too small" or "workspace too small", the row holds the text that names the
+    buffer (and both sizes) instead, with the recorded one beside it as "recorded_text"; the status is the recorded one in every row."""
+    import json
+    from tests import state_buffer_cases as cases
+    with open(os.path.join(ROOT, "tests", "golden", "state_buffer_refusals.json")) as f:
+        recorded = json.load(f)
+    assert recorded["recorded_from_source_digest"] != lib.sr_source_digest().decode()      # not recorded from the library under test
+    key = lambda r: (r["entry"], r["argument"], r["fault"], r.get("case"), tuple(tuple(x) for x in r.get("also", ())))
+    rows = {key(r): (r["status"], r["text"]) for r in recorded["refusals"]}
+    assert len(rows) == len(recorded["refusals"])
+    assert sorted(cases.ARGUMENTS) == sorted(STATE_BUFFERS) and len(STATE_BUFFERS) == 14
+    for entry, buffers in STATE_BUFFERS.items():
+        assert cases.buffers_of(entry) == buffers, entry
+        for b in buffers:
+            assert (entry, b, "null", None, ()) in rows and (entry, b, "short", None, ()) in rows, (entry, b)
+        assert sorted(k[1:3] for k in rows if k[0] == entry and k[3:] == (None, ())) == sorted(cases.faults(entry)), entry      # the other pointers too, nothing else
+    # the rows of another case are the ones without a recorded value ("recorded_text" null), the rows with two faults the listed ones, and
+    # the rows whose recorded text named no buffer and was restated had one of those three texts
+    assert sorted(k for k in rows if k[3] is not None) == sorted(cases.UNRECORDED) and sorted(k for k in rows if k[4]) == sorted(cases.DOUBLE_FAULTS)
+    assert [key(r) for r in recorded["refusals"] if r.get("recorded_text", "") is None] == cases.UNRECORDED
+    assert {r["recorded_text"] for r in recorded["refusals"] if r.get("recorded_text")} == {"NULL buffer argument", "state buffer too small", "workspace too small"}
+    scene = cases.Scene(lib)
+    for k, want in rows.items():
+        assert scene.refusal(*k) == want, k
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import torch
     from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer

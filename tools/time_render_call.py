@@ -1,12 +1,14 @@
 #!/usr/bin/env python
-"""render() (operator + fused map post-processing + the python around it) vs the bare operator, fwd+bwd at the C3 size."""
+"""render() (operator + fused map post-processing + the python around it) vs the bare operator, fwd+bwd at the C3 size.
+    python tools/time_render_call.py [P W H calls]   -- e.g. 1000 160 96 2000: a size at which the host binds, so the figure is host time per call"""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from streetunveiler_amd.gaussian_renderer import PipelineParams, SurfelModel, render
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
-P, W, H, dev = 3_000_000, 1920, 1080, "cuda:0"
+P, W, H, N = (int(a) for a in sys.argv[1:5]) if len(sys.argv) > 4 else (3_000_000, 1920, 1080, 10)
+dev = "cuda:0"
 cam = synthetic_camera(W, H).to(dev)
 g = {k: v.to(dev).requires_grad_() for k, v in synthetic_gaussians(P, W, H).items()}
 pc = SurfelModel(g["means3D"], g["scales"], g["rotations"], g["opacities"], g["shs"], None, 3, 3)
@@ -26,6 +28,6 @@ for name, fn in (("bare operator + sum losses", bare), ("render() + regulariser-
     torch.cuda.synchronize()
     t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
     t0.record()
-    for _ in range(10): fn()
+    for _ in range(N): fn()
     t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / 10:.3f} ms fwd+bwd")
+    print(f"{name}: {t0.elapsed_time(t1) / N:.4f} ms fwd+bwd")
