@@ -882,6 +882,42 @@ int sr_lidar_label_emit(int32_t n, const void* points, int32_t points_f64, const
 int sr_lidar_vote(int32_t n, const void* points, int32_t points_f64, const void* views, int32_t n_views, int32_t n_classes, const uint8_t* label_lut,
                   void* workspace, size_t workspace_bytes, uint8_t* valid_mask, uint64_t* counts, void* stream);
 
+/* Frame resizing with Pillow's 8-bit arithmetic, and nearest label maps (csrc/resize.hip): how a camera frame, an inpainted frame and a
+ * label map reach the training resolution [REF utils/camera_utils.py:22-73, utils/general_utils.py:21-27,
+ * inpainting_pipeline/3_reoptimization/1_optimization.py:140-199] -- Image.resize(size, BICUBIC or BILINEAR) of an "L" or "RGB" image bit
+ * for bit, and transforms.Resize(NEAREST) of a label tensor.  All pointers are device pointers and both calls CHECK that (an address the
+ * HIP runtime does not know as device or managed memory is refused); nothing is read back, nothing allocated.
+ *   A frame is N pictures of H x W pixels of C = 1 or 3 dense bytes; a row's pixels are dense, row y of picture n starts at byte
+ *     n in_batch_stride + y in_row_stride (in_row_stride >= W C, in_batch_stride >= 0; sr_resize_nearest: the same in ELEMENTS, C = 1).
+ *   sr_resize_u8_pass: ONE pass of the separable resize.  axis 0 resamples the columns (W -> out_size, the output is [N,H,out_size,C]),
+ *     axis 1 the rows (H -> out_size, [N,out_size,W,C]), axis -1 neither (out_size, bounds, coeffs and ksize are ignored).  For output
+ *     index o: first = bounds[2 o], count = bounds[2 o + 1] (int32 [out_size,2]), k = coeffs + o ksize (int32 [out_size,ksize]) and
+ *       v = clamp((2^21 + sum over i < count of in[first + i] k[i]) >> 22, 0, 255)
+ *     with a 32-bit wrapping sum and an arithmetic shift.  first is clamped into [0, in_size] and count into [0, min(ksize, in_size -
+ *     first)] before anything is read: no table reads outside the picture.  The tables are the caller's (Pillow's precompute_coeffs and
+ *     normalize_coeffs_8bpc in host float64; streetunveiler_amd.frames.resize_tables); the loop runs to count, whatever ksize is.
+ *     A resize is axis 0, then axis 1 on its uint8 output; a pass whose axis keeps its size is left out; a resize that changes neither is
+ *     axis -1 (a copy).  flags, the epilogue of the LAST pass of a resize: 0 = out is uint8 [N,h,w,C]; SR_RESIZE_BINARISE = uint8, 255
+ *     where v > 0, else 0; SR_RESIZE_F32_CHW = out is float32 [N,C,h,w] holding v / 255.0f by IEEE division (not a product with a
+ *     reciprocal).
+ *   sr_resize_nearest: out[n, y, x] = in[n, min(floor(y sy), H - 1), min(floor(x sx), W - 1)] with sy = float32(H) / float32(h), sx
+ *     likewise and the products in float32 -- F.interpolate(mode="nearest").  elem_bytes = 1, 4 or 8 (uint8, int32, int64: the elements
+ *     are copied as they are); out is dense [N,h,w].
+ * Every call checks its arguments before its first launch (SR_ERR_INVALID_ARGUMENT: N, H, W, out_size, h, w or ksize < 1, an axis outside
+ * -1..1, unknown flag bits, SR_RESIZE_BINARISE together with SR_RESIZE_F32_CHW, a NULL, misaligned or HOST pointer -- "in is not device
+ * memory (a host address?)" --, out == in, a row stride below a dense row, a negative batch stride; SR_ERR_UNSUPPORTED: C other than 1 or
+ * 3 -- Pillow resizes an alpha channel through premultiplied alpha, which is not built --, elem_bytes other than 1, 4, 8, a size above
+ * 2^24, more than 262 140 output rows, more than 65535 pictures (x C for the float output) a call) and runs on the caller's stream.
+ * Integers throughout but for the one division: equal inputs give equal bits.  Added without a new SR_ABI_VERSION: nothing that existed
+ * changed. */
+#define SR_RESIZE_BINARISE 1u
+#define SR_RESIZE_F32_CHW 2u
+int sr_resize_u8_pass(int32_t N, int32_t H, int32_t W, int32_t C, const uint8_t* in, int64_t in_batch_stride, int64_t in_row_stride,
+                      int32_t axis, int32_t out_size, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, uint32_t flags, void* out,
+                      void* stream);
+int sr_resize_nearest(int32_t N, int32_t H, int32_t W, int32_t elem_bytes, const void* in, int64_t in_batch_stride, int64_t in_row_stride,
+                      int32_t h, int32_t w, void* out, void* stream);
+
 /* Test hook of the parity bars: the hard decisions the blend kernels take, dumped per (list entry, pixel) pair.  For list position
  * j (index into SrBinningView.point_list) and 8x8 quadrant q of its tile (q = (y / 8) * (tile_width / 8) + x / 8, bit = (y % 8) * 8 + x % 8
  * in tile-local pixel coordinates): valid_bits[j * nq + q] = pixels where the entry passes the chain of skips of the forward blend

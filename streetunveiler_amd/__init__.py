@@ -25,8 +25,9 @@ _UNVEIL = ("FrameCamera", "FrameCameras", "pack_cameras", "points_in_frame", "fr
 _VOXEL = ("SemanticCloud", "voxel_down_sample", "voxel_down_sample_torch", "create_from_pcd")
 _LIDAR_LABEL = ("LabelViews", "LabelledSweeps", "label_sweeps", "vote_semantics", "label_sweeps_numpy", "vote_semantics_numpy", "label_sweeps_torch",
                 "vote_semantics_torch", "in_frame_numpy", "certain_mask_numpy")
+_FRAMES = ("resize_u8", "pil_to_torch", "frame_tensor", "resize_labels", "resize_u8_numpy", "resize_labels_numpy", "resize_tables")
 __all__ = list(_IMAGE_LOSS + _OPTIM + _CLUSTER + _DENSIFY + _TSDF + _MASK_MODEL + _AUX_LOSS + _SKY + _MESH + _MESH_PLY + _MESH_POST + _UNVEIL + _VOXEL +
-               _LIDAR_LABEL)
+               _LIDAR_LABEL + _FRAMES)
 
 
 def __getattr__(name):   # the fused image loss, the optimizer step, the radius clustering, densify / prune, the TSDF fusion and the masked model, imported on first use (this package does not import torch by itself)
@@ -72,4 +73,7 @@ def __getattr__(name):   # the fused image loss, the optimizer step, the radius 
     if name in _LIDAR_LABEL:
         from . import lidar_label
         return getattr(lidar_label, name)
+    if name in _FRAMES:
+        from . import frames
+        return getattr(frames, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -103,6 +103,7 @@ SR_DENSIFY_MAX_SEGMENTS = 8
 SR_DENSIFY_FLAG_CLONE, SR_DENSIFY_FLAG_SPLIT, SR_DENSIFY_FLAG_KEEP_SELF, SR_DENSIFY_FLAG_KEEP_CHILD = 1, 2, 4, 8
 SR_DENSIFY_KIND_ORIGINAL, SR_DENSIFY_KIND_CLONE, SR_DENSIFY_KIND_CHILD0, SR_DENSIFY_KIND_CHILD1 = 0, 1, 2, 3
 SR_DENSIFY_ROLE_COPY, SR_DENSIFY_ROLE_MOMENT, SR_DENSIFY_ROLE_XYZ, SR_DENSIFY_ROLE_SCALING = 0, 1, 2, 3
+SR_RESIZE_BINARISE, SR_RESIZE_F32_CHW = 1, 2      # sr_resize_u8_pass flags: the epilogue of a resize's last pass
 
 
 # include/surfel_raster.h, once: every function it declares -> (return type, argument types), in the header's order (tests/test_abi.py holds
@@ -190,6 +191,8 @@ PROTOTYPES = {
     "sr_lidar_label_decide": (_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp] + [_i32] * 4 + [_vp, _i32] + _WS + [_vp, _vp]),
     "sr_lidar_label_emit": (_int, [_i32, _vp, _i32, _vp] + [_i32] * 3 + _WS + [_i32] + [_vp] * 6),
     "sr_lidar_vote": (_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp] + _WS + [_vp] * 3),
+    "sr_resize_u8_pass": (_int, [_i32] * 4 + [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _u32, _vp, _vp]),
+    "sr_resize_nearest": (_int, [_i32] * 4 + [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "sr_debug_pair_decisions":(_int, _FG + _GEOM + _BINNING + [_u32, _vp, _vp, _vp]),
     "sr_debug_radix_sort_temp_bytes": (_sz, [_u32]),
     "sr_debug_radix_sort": (_int, [_vp] * 4 + [_u32, _int] + _WS + [_u32, _vp]),

@@ -47,6 +47,7 @@ SOURCES = [
     ("unveil.hip", ["-ffp-contract=off"]),      # 255 x + 0.5 and the composites are a product THEN a sum, as the stock-torch lines they restate
     ("voxel.hip", ["-ffp-contract=off"]),       # the voxel coordinate is ONE subtraction and ONE division in the points' dtype: a bit-exact contract
     ("lidar_label.hip", ["-ffp-contract=off"]), # the projection is the float64 operations as written, one rounding each: the decisions' contract
+    ("resize.hip", ["-ffp-contract=off"]),      # integers, and two float32 operations that stand alone: y * scale of the nearest rule, v / 255
     ("api.hip", []),
     ("build_id.hip", []),                       # + -DSR_SOURCE_DIGEST="..." (build()): recompiled whenever anything else is
 ]
