@@ -6,6 +6,7 @@ import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, _C
 from streetunveiler_amd import _lib
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tools import measure
 dev = "cuda:0"
 lib = _lib.load()
 out = {}
@@ -26,12 +27,7 @@ for tag, (P, W, H) in {k: SCENES[k] for k in cli.configs.split(",")}.items():
                                           H, W, g["shs"], 3, s.campos, False, False, forward_only=fo)
         for _ in range(3): r = step()
         D, V = r[0], int((r[3] > 0).sum())
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(20): step()
-        b.record(); torch.cuda.synchronize()
-        wall = a.elapsed_time(b) / 20
+        wall = measure.alternating_rounds({mode: step}, rounds=1, iters=20, warmup=0)[mode][0]      # (warmed above)
         lib.sr_set_stage_timing(1)
         for _ in range(10): step()
         torch.cuda.synchronize()

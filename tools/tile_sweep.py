@@ -7,6 +7,7 @@ import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
 from streetunveiler_amd import _lib
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians, synthetic_upstream_grads
+from tools import measure
 P, W, H = (int(a) for a in sys.argv[1:4]) if len(sys.argv) > 3 else (6_000_000, 3840, 2160)
 dev = "cuda:0"
 lib = _lib.load()
@@ -28,12 +29,8 @@ for tile in shapes:
                                    s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, H, W, g["shs"].detach(), 3, s.campos, False, False, tile=tile)[0]
     for _ in range(3): step()
     torch.cuda.synchronize(); lib.sr_set_stage_timing(1)
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(10): step()
-    t1.record(); torch.cuda.synchronize()
+    ms = measure.alternating_rounds({"step": step}, rounds=1, iters=10, warmup=0)["step"][0]      # (warmed above; the stage timers run inside the window)
     st = {k: round(ms / n, 4) for k, (ms, n) in _lib.stage_stats().items() if n}; lib.sr_set_stage_timing(0)
-    ms = t0.elapsed_time(t1) / 10
     row = dict(tile=f"{tile[0]}x{tile[1]}", duplicates_D=int(D), ms_per_step=round(ms, 3), msplats_per_s=round(P / ms / 1e3, 1),
                binning_ms=round(sum(st[k] for k in ("depth_sort", "scan", "expand_x", "expand_y", "ranges")), 3), **st)
     rows.append(row); print(json.dumps(row), flush=True)

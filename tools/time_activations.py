@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians, synthetic_upstream_grads
+from tools import measure
 P, W, H, dev = 3_000_000, 1920, 1080, "cuda:0"
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 cam = synthetic_camera(W, H)
@@ -26,10 +27,5 @@ def step(fused):
     c, r, a = GaussianRasterizer(s, fused_activations=fused)(means3D=raw["means3D"], means2D=m2d, shs=raw["shs"], opacities=o, scales=sc, rotations=ro)
     torch.autograd.backward([c, a], [dc, da])
 for name, fused in (("torch activations in front of the operator", False), ("activations fused into K1/K8", True)):
-    for _ in range(3): step(fused)
-    torch.cuda.synchronize()
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps): step(fused)
-    t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / steps:.3f} ms per fwd+bwd")
+    ms = measure.alternating_rounds({name: lambda: step(fused)}, rounds=1, iters=steps, warmup=3)[name][0]
+    print(f"{name}: {ms:.3f} ms per fwd+bwd")

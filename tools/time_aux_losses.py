@@ -10,7 +10,6 @@ The numbers are taken with the profiler off."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +19,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from streetunveiler_amd import aux_loss as al  # noqa: E402
+from tools import measure  # noqa: E402
 
 W, H, CLASSES, P = 1920, 1080, 6, 3_000_000
 
@@ -55,41 +55,22 @@ def main():
     }
     rows = []
     for name, (leaves, fused, stock, nbytes) in ops.items():
-        fns = dict(fused=fused, torch=stock)
-
         def step(fn):
             for t in leaves:
                 t.grad = None
             fn().backward()
 
-        for fn in fns.values():
-            for _ in range(5):
-                step(fn)
-        torch.cuda.synchronize()
-        ms = {k: [] for k in fns}
-        for _ in range(args.rounds):
-            for k, fn in fns.items():                                                # alternating
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.iters):
-                    step(fn)
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1) / args.iters)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        fns = dict(fused=lambda: step(fused), torch=lambda: step(stock))
+        ms = {k: measure.stats(v) for k, v in measure.alternating_rounds(fns, args.rounds, args.iters, warmup=5).items()}
+        med = {k: v["median"] for k, v in ms.items()}
         row = dict(op=name, width=W, height=H, classes=CLASSES, gaussians=P, iters_per_round=args.iters, rounds=args.rounds,
-                   fused_ms=dict(median=med["fused"], min=min(ms["fused"]), max=max(ms["fused"])),
-                   torch_ms=dict(median=med["torch"], min=min(ms["torch"]), max=max(ms["torch"])),
-                   torch_over_fused=med["torch"] / med["fused"], design_bytes=nbytes, fused_design_GBps=nbytes / (med["fused"] * 1e-3) / 1e9)
+                   fused_ms=ms["fused"], torch_ms=ms["torch"], torch_over_fused=med["torch"] / med["fused"], design_bytes=nbytes, fused_design_GBps=nbytes / (med["fused"] * 1e-3) / 1e9)
         rows.append(row)
         print(json.dumps(row), flush=True)
-    doc = dict(device=torch.cuda.get_device_name(0), what="forward + backward of each loss, per step, autograd included; device events around "
+    doc = dict(measure.header(), what="forward + backward of each loss, per step, autograd included; device events around "
                "iters_per_round steps; median / min / max over the rounds; the two implementations alternate; the semantic baseline includes "
                "the one-hot image and the weight upload of the reference's iteration", results=rows)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-    print("->", args.out)
+    measure.write_record(args.out, doc)
 
 
 if __name__ == "__main__":

@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """The reference's per-class distortion renders [REF train.py:94-103] at the C3 size: five class-filtered render() calls
 (boolean-indexed, and with the mask handed to the operator) vs render_class_distortions (one pass)."""
-import os, sys, time
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from streetunveiler_amd.gaussian_renderer import PipelineParams, SurfelModel, render, render_class_distortions
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tools import measure
 P, W, H, dev = int(sys.argv[1]) if len(sys.argv) > 1 else 3_000_000, 1920, 1080, "cuda:0"
 cam = synthetic_camera(W, H).to(dev)
 g = {k: v.to(dev).requires_grad_() for k, v in synthetic_gaussians(P, W, H).items()}
@@ -27,7 +28,5 @@ for name, fn in [("five render() calls, boolean-indexed inputs (reference patter
                  ("five render() calls, mask inside the operator", lambda: loop(PipelineParams(fused_mask=True))),
                  ("render_class_distortions (one pass)", one)]:
     for _ in range(2): fn()
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(5): fn()
-    torch.cuda.synchronize()
-    print(f"{name}: {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms fwd+bwd")
+    ms = measure.per_call_host(lambda: [fn() for _ in range(5)], warmup=0, repeats=1)[0] / 5      # one host window round five calls and a synchronise
+    print(f"{name}: {ms:.2f} ms fwd+bwd")

@@ -14,21 +14,20 @@ host read-back says nothing moved.  It is run ON A SUBSAMPLE of the active point
 seconds for that subsample and seconds per active point at that subsample size.  Nothing is extrapolated: the loop's cost per point grows
 with the number of active points, so the per-point figure at the subsample is a lower bound of the per-point cost at the full size.
 Writes one record to FILE (default profiles/cluster_time.json) with the library's source digest."""
-import json, os, statistics, sys, time
+import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
-from streetunveiler_amd import _lib, radius_components
-from streetunveiler_amd.build import source_digest
+from streetunveiler_amd import radius_components
 from tests.knn_cases import lidar_cloud
+from tools import measure
 
-args = sys.argv[1:]
-opt = {"--points": "3000000", "--baseline-points": "3000", "--json": os.path.join(ROOT, "profiles", "cluster_time.json")}
-for flag in list(opt):
-    if flag in args:
-        i = args.index(flag); opt[flag] = args[i + 1]; del args[i:i + 2]
-N, M, RADIUS, DEV = int(opt["--points"]), int(opt["--baseline-points"]), 0.07, "cuda:0"
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--points", type=int, default=3000000); ap.add_argument("--baseline-points", type=int, default=3000)
+ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "cluster_time.json"))
+opt = ap.parse_args()
+N, M, RADIUS, DEV = opt.points, opt.baseline_points, 0.07, "cuda:0"
 assert torch.cuda.is_available(), "tools/time_cluster.py measures on the GPU; there is no CPU path"
 
 rng = np.random.default_rng(0)
@@ -42,15 +41,7 @@ xyz, active = torch.tensor(pts, device=DEV), torch.tensor(mask, device=DEV)
 
 
 def timed(fn, warmup, repeats):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(); fn(); t1.record(); torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "repeats": repeats}
+    return measure.stats_ms(measure.per_call_events(fn, warmup, repeats))
 
 
 def reference_default_loop(xyz, valid_mask, threshold):
@@ -75,7 +66,7 @@ def reference_default_loop(xyz, valid_mask, threshold):
     return out
 
 
-record = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "library": os.path.relpath(_lib.LIB_PATH, ROOT),
+record = {**measure.header(),
           "scene": f"tests/knn_cases.lidar_cloud({N}, 0), shuffled; active: 30 % of the blob points, 2 % of the background", "points": N,
           "active_points": int(mask.sum()), "radius": RADIUS}
 op = timed(lambda: radius_components(xyz, RADIUS, active), warmup=2, repeats=9)
@@ -90,13 +81,9 @@ sub = np.flatnonzero(mask)[:M]
 sub_mask = np.zeros(N, bool); sub_mask[sub] = True
 sub_active = torch.tensor(sub_mask, device=DEV)
 reference_default_loop(xyz, torch.tensor(np.isin(np.arange(N), sub[:50]), device=DEV), RADIUS)      # warm-up of every torch kernel it uses
-torch.cuda.synchronize()
-seconds = []
-for _ in range(3):
-    t = time.perf_counter()
-    ref = reference_default_loop(xyz, sub_active, RADIUS)
-    torch.cuda.synchronize()
-    seconds.append(time.perf_counter() - t)
+kept = {}
+seconds = [ms / 1e3 for ms in measure.per_call_host(lambda: kept.update(ref=reference_default_loop(xyz, sub_active, RADIUS)), 0, 3)]
+ref = kept["ref"]
 ours = timed(lambda: radius_components(xyz, RADIUS, sub_active), warmup=2, repeats=9)
 # the default loop may split what the exact op keeps whole: every group of the loop must lie inside one component of the op
 g, r = radius_components(xyz, RADIUS, sub_active)[sub_active].cpu().numpy(), ref[sub_active].cpu().numpy()
@@ -112,6 +99,4 @@ record["reference_default_loop_on_subsample"] = {
 print(f"reference default loop on {len(sub)} active points: median {statistics.median(seconds):.2f} s "
       f"({record['reference_default_loop_on_subsample']['ms_per_active_point_at_this_size']:.3f} ms per active point at this size); "
       f"radius_components on the same mask: median {ours['median_ms']:.2f} ms; same partition: {same_partition}")
-os.makedirs(os.path.dirname(os.path.abspath(opt["--json"])), exist_ok=True)
-json.dump(record, open(opt["--json"], "w"), indent=1)
-print("wrote", opt["--json"])
+measure.write_record(opt.json, record)

@@ -13,20 +13,18 @@ that end in a synchronise, every run on a fresh copy of the model (the copy is o
     prune_points (the op, 3 % mask)    against  the reference's prune_points lines
 and torch.cuda.max_memory_allocated over each timed call, less what was allocated when it began.
 Writes one record to FILE (default profiles/densify_time.json) with the library's source digest."""
-import json, os, statistics, sys
+import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from streetunveiler_amd import SurfelAdam, _lib, densify_and_prune, prune_points
-from streetunveiler_amd.build import source_digest
+from streetunveiler_amd import SurfelAdam, densify_and_prune, prune_points
 from tests import densify_cases as dc
+from tools import measure
 
-args = sys.argv[1:]
-opt = {"--points": "3000000", "--json": os.path.join(ROOT, "profiles", "densify_time.json")}
-for flag in list(opt):
-    if flag in args:
-        i = args.index(flag); opt[flag] = args[i + 1]; del args[i:i + 2]
-N, DEV = int(opt["--points"]), "cuda:0"
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--points", type=int, default=3000000); ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "densify_time.json"))
+opt = ap.parse_args()
+N, DEV = opt.points, "cuda:0"
 assert torch.cuda.is_available(), "tools/time_densify.py measures on the GPU; there is no CPU path"
 TH = dict(dc.DEFAULT)
 
@@ -56,24 +54,22 @@ def fresh():
 
 
 def timed(fn, warmup=2, repeats=9):
+    """every run is one per_call_events sample of its own, on a fresh model made outside the window; the first `warmup` runs are dropped"""
     ms, peak = [], []
     for it in range(warmup + repeats):
         m = fresh()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         before = torch.cuda.memory_allocated()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(); fn(m); t1.record(); torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(t0.elapsed_time(t1)); peak.append(torch.cuda.max_memory_allocated() - before)
+        ms += measure.per_call_events(lambda: fn(m), 0, 1, sync_each=True)
+        peak.append(torch.cuda.max_memory_allocated() - before)
         rows = m._xyz.shape[0]
         del m
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "repeats": repeats,
-            "peak_extra_bytes": max(peak), "rows_out": rows}
+    return dict(measure.stats_ms(ms[warmup:]), peak_extra_bytes=max(peak[warmup:]), rows_out=rows)
 
 
 th = (TH["max_grad"], TH["min_opacity"], TH["extent"], TH["max_screen_size"])
-record = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "library": os.path.relpath(_lib.LIB_PATH, ROOT), "points": N,
+record = {**measure.header(), "points": N,
           "sh_coefficients": 16, "adam_state": True, "model_bytes": N * 58 * 4 * 3,
           "mix": {"cloned": int(want.clone.sum()), "split": S, "pruned_by_opacity": int((~want.keep_self & ~want.split).sum()),
                   "note": "synthetic: 5 % cloned, 5 % split, 3 % pruned; not taken from a real training run"},
@@ -86,6 +82,4 @@ for a, b in (("densify_and_prune", "densify_and_prune_torch_float32"), ("prune_p
     record[a]["speedup_over_torch"] = round(record[b]["median_ms"] / record[a]["median_ms"], 2)
     print(f"{a}: median {record[a]['median_ms']} ms ({record[a]['min_ms']} .. {record[a]['max_ms']}), peak extra {record[a]['peak_extra_bytes'] / 2**20:.0f} MiB;  "
           f"{b}: median {record[b]['median_ms']} ms ({record[b]['min_ms']} .. {record[b]['max_ms']}), peak extra {record[b]['peak_extra_bytes'] / 2**20:.0f} MiB")
-os.makedirs(os.path.dirname(os.path.abspath(opt["--json"])), exist_ok=True)
-json.dump(record, open(opt["--json"], "w"), indent=1)
-print("wrote", opt["--json"])
+measure.write_record(opt.json, record)

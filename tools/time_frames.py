@@ -14,7 +14,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -23,23 +22,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from streetunveiler_amd import frames as F  # noqa: E402
-from streetunveiler_amd.build import source_digest  # noqa: E402
+from tools import measure  # noqa: E402
 
 DEV = "cuda:0"
 REPEATS = 9
 
 
 def timed(fn, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(REPEATS):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append(1e3 * (time.perf_counter() - t0))
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+    return {k + "_ms": v for k, v in measure.stats(measure.per_call_host(fn, warmup, REPEATS)).items()}
 
 
 def main():
@@ -90,13 +80,11 @@ def main():
                          "torch_interpolate_nearest": timed(lambda: torch.nn.functional.interpolate(maps[None, None], size=(h, w), mode="nearest")[0, 0]),
                          "differs_from_torch_interpolate_nearest": int((torch.nn.functional.interpolate(maps[None, None], size=(h, w), mode="nearest")[0, 0] != got).sum())}
 
-    out = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "repeats": REPEATS, "pillow": pillow,
+    out = {**measure.header(), "repeats": REPEATS, "pillow": pillow,
            "method": "host clock around the call and a device synchronise, output allocations included; median, min and max of the repeats; "
                      "the tables are computed and uploaded by the warm-up calls and cached", "rows": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
     print(json.dumps(out, indent=1))
+    measure.write_record(args.out, out)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,6 @@ over the rounds and their spread (min, max).  Also: the bytes the fused design h
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +18,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from streetunveiler_amd.image_loss import photometric_loss, photometric_loss_torch  # noqa: E402
+from tools import measure  # noqa: E402
 
 SIZES = ((480, 320), (1920, 1080), (3840, 2160))
 
@@ -56,38 +56,21 @@ def main():
                     t.grad = None
                 fn(image, gt, 0.2, sky, alpha)[0].backward()
 
-            fns = dict(fused=photometric_loss, torch=photometric_loss_torch)
+            fns = dict(fused=lambda: step(photometric_loss), torch=lambda: step(photometric_loss_torch))
             iters = max(5, args.iters // 4) if W >= 3840 else args.iters
-            for fn in fns.values():                      # warm every shape: code objects, the convolution backend's choice of algorithm
-                for _ in range(5):
-                    step(fn)
-            torch.cuda.synchronize()
-            ms = {k: [] for k in fns}
-            for _ in range(args.rounds):
-                for name, fn in fns.items():             # alternating
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(iters):
-                        step(fn)
-                    e1.record()
-                    e1.synchronize()
-                    ms[name].append(e0.elapsed_time(e1) / iters)
-            med = {k: statistics.median(v) for k, v in ms.items()}
+            # (the warm-up covers every shape: code objects, the convolution backend's choice of algorithm)
+            ms = {k: measure.stats(v) for k, v in measure.alternating_rounds(fns, args.rounds, iters, warmup=5).items()}
+            med = {k: v["median"] for k, v in ms.items()}
             nbytes = design_bytes(W, H, 3, composite)
             row = dict(width=W, height=H, channels=3, composite=composite, iters_per_round=iters, rounds=args.rounds,
-                       fused_ms=dict(median=med["fused"], min=min(ms["fused"]), max=max(ms["fused"])),
-                       torch_ms=dict(median=med["torch"], min=min(ms["torch"]), max=max(ms["torch"])),
-                       torch_over_fused=med["torch"] / med["fused"],
+                       fused_ms=ms["fused"], torch_ms=ms["torch"], torch_over_fused=med["torch"] / med["fused"],
                        design_bytes_per_pixel_channel=nbytes / (W * H * 3), design_bytes=nbytes,
                        fused_design_GBps=nbytes / (med["fused"] * 1e-3) / 1e9)
             rows.append(row)
             print(json.dumps(row), flush=True)
-    doc = dict(device=torch.cuda.get_device_name(0), what="forward + backward of the loss, per step, autograd included; device events around "
+    doc = dict(measure.header(), what="forward + backward of the loss, per step, autograd included; device events around "
                "iters_per_round steps; median / min / max over the rounds; the two implementations alternate", results=rows)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-    print("->", args.out)
+    measure.write_record(args.out, doc)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -21,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from streetunveiler_amd import lidar_label as LL      # noqa: E402
+from tools import measure      # noqa: E402
 
 DEV = "cuda:0"
 H, W = 1280, 1920
@@ -56,15 +56,7 @@ def pictures(n, with_images, seed=1):
 
 
 def timed(fn, rounds):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "rounds": rounds}
+    return dict({k + "_ms": v for k, v in measure.stats(measure.per_call_host(fn, 1, rounds)).items()}, rounds=rounds)
 
 
 def main():
@@ -77,7 +69,7 @@ def main():
     ap.add_argument("--baseline-rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lidar_label_time.json"))
     a = ap.parse_args()
-    result = {"device": torch.cuda.get_device_name(0), "picture": [H, W], "labels": 6, "check_range": 10}
+    result = {**measure.header(), "picture": [H, W], "labels": 6, "check_range": 10}
 
     points, w2c, K = scene(a.sweeps, a.returns, 3)
     images, maps = pictures(a.sweeps * 3, True)
@@ -94,9 +86,7 @@ def main():
         print(mode, json.dumps(sweeps[mode]), flush=True)
     one = LL.LabelViews(w2c[:3], K[:3], [(H, W)] * 3, [p.cpu() for p in images[:3]], [p.cpu() for p in maps[:3]])
     first = points[:a.returns].cpu().numpy()
-    t0 = time.perf_counter()
-    LL.label_sweeps_numpy(first, [0, a.returns], one, 3, "merge")
-    sweeps["numpy_checker_one_sweep_cpu_ms"] = (time.perf_counter() - t0) * 1e3
+    sweeps["numpy_checker_one_sweep_cpu_ms"] = measure.per_call_host(lambda: LL.label_sweeps_numpy(first, [0, a.returns], one, 3, "merge"), 0, 1)[0]
     result["label_sweeps"] = sweeps
     del images, maps, views, points
     torch.cuda.empty_cache()
@@ -117,11 +107,7 @@ def main():
                                 "fused": timed(lambda: LL.vote_semantics(points, views), a.rounds),
                                 "torch_float64_twin": timed(lambda: LL.vote_semantics_torch(points, views), a.baseline_rounds)}
     print("vote", json.dumps(result["vote_semantics"]), flush=True)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
-    print(a.out)
+    measure.write_record(a.out, result)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from streetunveiler_amd.gaussian_renderer import PipelineParams, SurfelModel, render_with_mask
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tools import measure
 P, W, H, dev = 3_000_000, 1920, 1080, "cuda:0"
 cam = synthetic_camera(W, H).to(dev)
 g = {k: v.to(dev).requires_grad_() for k, v in synthetic_gaussians(P, W, H).items()}
@@ -17,10 +18,5 @@ def step(fused):
     out = render_with_mask(cam, pc, PipelineParams(fused_mask=fused), bg, m)
     (out["render"].sum() + out["rend_dist"].sum()).backward()
 for name, fused in (("boolean-indexed inputs (reference call pattern)", False), ("mask inside the operator", True)):
-    for _ in range(3): step(fused)
-    torch.cuda.synchronize()
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(10): step(fused)
-    t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / 10:.3f} ms per render_with_mask fwd+bwd")
+    ms = measure.alternating_rounds({name: lambda: step(fused)}, rounds=1, iters=10, warmup=3)[name][0]
+    print(f"{name}: {ms:.3f} ms per render_with_mask fwd+bwd")

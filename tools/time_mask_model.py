@@ -14,7 +14,6 @@ Reported: the median over the rounds with its range (min, max), per call.  Taken
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +23,7 @@ import torch  # noqa: E402
 
 from streetunveiler_amd.mask_model import PROPERTIES, compose_masked, compose_masked_torch  # noqa: E402
 from streetunveiler_amd.optim import SurfelAdam  # noqa: E402
+from tools import measure  # noqa: E402
 
 LRS = (0.00016, 0.0025, 0.0025 / 20.0, 0.05, 0.005, 0.001)     # the reference's six groups
 
@@ -33,27 +33,8 @@ def _shapes(P, degree):
     return [(P, 3), (P, 1, 3), (P, M - 1, 3), (P, 1), (P, 2), (P, 4)], [(P, 3), (P, M, 3), (P, 1), (P, 2), (P, 4)]
 
 
-def _spread(v):
-    return dict(median=statistics.median(v), min=min(v), max=max(v))
-
-
 def _alternate(fns, rounds, iters):
-    """{name: [ms per call, one figure per round]}, the implementations taking turns"""
-    for fn in fns.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ms[name].append(e0.elapsed_time(e1) / iters)
-    return ms
+    return measure.alternating_rounds(fns, rounds, iters, warmup=3)
 
 
 def main():
@@ -109,21 +90,18 @@ def main():
         ms.update(_alternate({k: o.step for k, o in opts.items()}, args.rounds, args.iters))
         row = dict(gaussians=P, sh_degree=args.degree, floats_per_gaussian=floats_per_row, trainable_share=share,
                    trainable_rows=int(mask.sum()), mask="torch.rand(P, generator=manual_seed(0) on the GPU, drawn after the tensors) < share",
-                   rounds=args.rounds, iters_per_round=args.iters, outputs_equal=bool(same), ms={k: _spread(v) for k, v in ms.items()})
+                   rounds=args.rounds, iters_per_round=args.iters, outputs_equal=bool(same), ms={k: measure.stats(v) for k, v in ms.items()})
         for what in ("compose", "compose_backward", "adam"):
             row[f"{what}_reference_over_fused"] = row["ms"][f"{what}_reference"]["median"] / row["ms"][f"{what}_fused"]["median"]
         results.append(row)
         print(json.dumps(row), flush=True)
         del start, delta, params, opts, mask, float_mask
         torch.cuda.empty_cache()
-    doc = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__,
+    doc = dict(measure.header(), torch=torch.__version__,
                what="ms per call; device events around iters_per_round calls; median / min / max over the rounds; fused and reference alternate "
                     "round by round in one process; reference = the reference's getter lines and torch.optim.Adam in float32 torch on the same GPU",
                results=results)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-    print("->", args.out)
+    measure.write_record(args.out, doc)
 
 
 if __name__ == "__main__":

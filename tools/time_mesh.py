@@ -14,19 +14,18 @@ the rate of a device-to-device copy of the volume measured in the same process (
 No baseline exists where this runs -- the original's CPU routine is not installed -- so no speed-up is claimed and nothing passes or fails
 on time.  If skimage imports, its time on the same volume (host arrays, its default method) is reported beside ours, else null.
 Writes FILE (default profiles/mesh_time.json)."""
-import json, math, os, statistics, sys, time
+import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from streetunveiler_amd import TsdfViews, _lib, extract_mesh_unbounded, marching_cubes
-from streetunveiler_amd.build import source_digest
+from streetunveiler_amd import TsdfViews, extract_mesh_unbounded, marching_cubes
 from tests import tsdf_cases as tc
+from tools import measure
 
-args = sys.argv[1:]
-opt = {"--sizes": "256,512,1024", "--views": "16", "--resolution": "512", "--json": os.path.join(ROOT, "profiles", "mesh_time.json")}
-for flag in list(opt):
-    if flag in args:
-        i = args.index(flag); opt[flag] = args[i + 1]; del args[i:i + 2]
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--sizes", default="256,512,1024"); ap.add_argument("--views", type=int, default=16); ap.add_argument("--resolution", type=int, default=512)
+ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "mesh_time.json"))
+opt = ap.parse_args()
 DEV = "cuda:0"
 assert torch.cuda.is_available(), "tools/time_mesh.py measures on the GPU; there is no CPU path"
 try:
@@ -36,15 +35,8 @@ except Exception:
 
 
 def timed(fn, warmup=2, repeats=9):
-    ms, r = [], None
-    for it in range(warmup + repeats):
-        del r
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(); r = fn(); t1.record(); torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(t0.elapsed_time(t1))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "repeats": repeats}, r
+    """every call starts from a synchronised device on which the call before it has freed its result"""
+    return measure.stats_ms(measure.per_call_events(fn, warmup, repeats, sync_each=True))
 
 
 def analytic(n):
@@ -53,18 +45,18 @@ def analytic(n):
     return (torch.sqrt(x * x + y * y + z * z) - 0.7 + 0.05 * (torch.sin(5 * x + 1) * torch.sin(4 * y + 2) * torch.sin(3 * z + 3))).contiguous()
 
 
-record = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "library": os.path.relpath(_lib.LIB_PATH, ROOT),
+record = {**measure.header(),
           "note": "no baseline is installed where this ran: no speed-up is claimed and nothing passes or fails on time", "marching_cubes": {}}
-for n in [int(s) for s in opt["--sizes"].split(",")]:
+for n in [int(s) for s in opt.sizes.split(",")]:
     N = n ** 3
     free = torch.cuda.mem_get_info(0)[0]
     if N >= 2 ** 31 or 4 * N * 2 + 5 * N + (1 << 30) > free:      # the volume, its copy for the rate, the workspace, room for the mesh
         record["marching_cubes"][str(n)] = None
         continue
     vol = analytic(n)
-    copy, other = timed(lambda: vol.clone())
-    del other
-    row, (vertices, faces) = timed(lambda: marching_cubes(vol, 0.0, (-1.0,) * 3, (1.0,) * 3))
+    copy = timed(lambda: vol.clone())
+    row = timed(lambda: marching_cubes(vol, 0.0, (-1.0,) * 3, (1.0,) * 3))
+    vertices, faces = marching_cubes(vol, 0.0, (-1.0,) * 3, (1.0,) * 3)
     nv, nf = int(vertices.shape[0]), int(faces.shape[0])
     moved = 12 * N + 17 * nv + 24 * nf
     copy_rate = 8 * N / (copy["median_ms"] * 1e-3)
@@ -73,20 +65,19 @@ for n in [int(s) for s in opt["--sizes"].split(",")]:
     row["skimage"] = None
     if sk_measure is not None and n <= 512:
         host = vol.cpu().numpy()
-        t0 = time.perf_counter(); sk_measure.marching_cubes(host, 0.0); t1 = time.perf_counter()
-        row["skimage"] = {"method": "skimage.measure.marching_cubes, default method (lewiner), one run on the host array", "ms": round((t1 - t0) * 1e3, 1)}
+        row["skimage"] = {"method": "skimage.measure.marching_cubes, default method (lewiner), one run on the host array",
+                          "ms": round(measure.per_call_host(lambda: sk_measure.marching_cubes(host, 0.0), 0, 1)[0], 1)}
     record["marching_cubes"][str(n)] = row
     print(n, json.dumps(row))
     del vol, vertices, faces
 
-V, RES, W, H = int(opt["--views"]), int(opt["--resolution"]), 1920, 1080
+V, RES, W, H = opt.views, opt.resolution, 1920, 1080
 depth, rgb, full = tc._views(tuple(360.0 * k / V for k in range(V)), 1, H, W)
 views = TsdfViews(depth.to(DEV), rgb.to(DEV), full.to(DEV))
 del depth, rgb
-row, mesh = timed(lambda: extract_mesh_unbounded(views, tc.CENTER, tc.RADIUS, 1.5, resolution=RES), warmup=1, repeats=9)
+row = timed(lambda: extract_mesh_unbounded(views, tc.CENTER, tc.RADIUS, 1.5, resolution=RES), warmup=1, repeats=9)
+mesh = extract_mesh_unbounded(views, tc.CENTER, tc.RADIUS, 1.5, resolution=RES)
 row.update(views=V, map_size=[W, H], resolution=RES, bound=1.5, Nv=int(mesh.vertices.shape[0]), Nf=int(mesh.faces.shape[0]))
 record["extract_mesh_unbounded"] = row
 print("extract_mesh_unbounded", json.dumps(row))
-os.makedirs(os.path.dirname(os.path.abspath(opt["--json"])), exist_ok=True)
-json.dump(record, open(opt["--json"], "w"), indent=1)
-print("wrote", opt["--json"])
+measure.write_record(opt.json, record)

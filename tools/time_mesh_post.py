@@ -17,20 +17,18 @@ Baseline: THE SAME WORK AS STOCK TORCH KERNELS on the same GPU -- edge keys matc
 with scatter_reduce and pointer jumping until a host read-back says nothing changed, boolean-mask compaction.  It is not open3d and not
 an estimate of open3d (which runs a single-threaded search on the host).  Its result is compared with the op's, bit for bit.
 Writes one record to FILE (default profiles/mesh_post_time.json) with the library's source digest."""
-import json, os, statistics, sys
+import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from streetunveiler_amd import _lib, connected_triangles, marching_cubes, post_process_mesh
+from streetunveiler_amd import connected_triangles, marching_cubes, post_process_mesh
 from streetunveiler_amd._call import buf, call, ptr, workspace
-from streetunveiler_amd.build import source_digest
+from tools import measure
 
-args = sys.argv[1:]
-opt = {"--size": "256", "--json": os.path.join(ROOT, "profiles", "mesh_post_time.json")}
-for flag in list(opt):
-    if flag in args:
-        i = args.index(flag); opt[flag] = args[i + 1]; del args[i:i + 2]
-N, DEV, CELL, KEEP, FLOOR = int(opt["--size"]), torch.device("cuda:0"), 32, 50, 50
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--size", type=int, default=256); ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "mesh_post_time.json"))
+opt = ap.parse_args()
+N, DEV, CELL, KEEP, FLOOR = opt.size, torch.device("cuda:0"), 32, 50, 50
 assert torch.cuda.is_available(), "tools/time_mesh_post.py measures on the GPU; there is no CPU path"
 
 
@@ -49,15 +47,7 @@ def sphere_lattice(n):
 
 
 def timed(fn, warmup=2, repeats=9):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(); fn(); t1.record(); torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "repeats": repeats}
+    return measure.stats_ms(measure.per_call_events(fn, warmup, repeats))
 
 
 def breakdown(vertices, faces, repeats=9):
@@ -66,9 +56,10 @@ def breakdown(vertices, faces, repeats=9):
     labels, sizes = torch.empty((nf,), dtype=torch.int32, device=DEV), torch.empty((nf,), dtype=torch.int32, device=DEV)
     bad, counts = torch.empty((1,), dtype=torch.int32, device=DEV), torch.empty((3,), dtype=torch.int32, device=DEV)
     ws = workspace("sr_mesh_post_workspace_bytes", DEV, nv, nf)
+    clock = measure.TorchBackend()
     steps = {name: [] for name in ("sr_mesh_components", "kth_largest_topk", "sr_mesh_filter_count", "read_back", "sr_mesh_filter_emit")}
     for round_ in range(2 + repeats):
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        marks = [clock.event() for _ in range(6)]
         marks[0].record()
         call("sr_mesh_components", DEV, ptr(faces), nv, nf, ptr(labels), ptr(sizes), ptr(bad), *buf(ws))
         marks[1].record()
@@ -117,7 +108,7 @@ vertices, faces = marching_cubes(sphere_lattice(N))
 nv, nf = vertices.shape[0], faces.shape[0]
 clusters, counts = connected_triangles(faces, nv)
 out = post_process_mesh((vertices, faces), KEEP, FLOOR)
-record = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "library": os.path.relpath(_lib.LIB_PATH, ROOT),
+record = {**measure.header(),
           "scene": f"marching_cubes of a {N}^3 volume: one sphere per {CELL}^3 cell, radii 0.6 .. 14 voxels", "vertices": nv, "faces": nf,
           "components": int(counts.shape[0]), "largest_component": int(counts.max()), "smallest_component": int(counts.min()),
           "cluster_to_keep": KEEP, "min_triangles": FLOOR, "vertices_out": int(out.vertices.shape[0]), "faces_out": int(out.faces.shape[0])}
@@ -132,12 +123,7 @@ record["kth_largest_share_of_total"] = round(steps["kth_largest_topk"] / total, 
 record["kth_largest_is_more_than_a_third"] = bool(steps["kth_largest_topk"] > total / 3)
 
 
-def save():
-    os.makedirs(os.path.dirname(os.path.abspath(opt["--json"])), exist_ok=True)
-    json.dump(record, open(opt["--json"], "w"), indent=1)
-
-
-save()      # (what is measured so far, should the baseline not run)
+measure.write_record(opt.json, record)      # (what is measured so far, should the baseline not run)
 base_v, base_f, base_labels = torch_baseline(vertices, faces, KEEP, FLOOR)
 same = bool(torch.equal(base_f, out.faces) and torch.equal(base_v.view(torch.int32), out.vertices.view(torch.int32)))
 record["baseline_stock_torch_kernels"] = dict(timed(lambda: torch_baseline(vertices, faces, KEEP, FLOOR), warmup=1, repeats=9), same_result_as_the_op=same,
@@ -151,5 +137,4 @@ for name in ("connected_triangles", "post_process_mesh", "baseline_stock_torch_k
     r = record[name]
     print(f"{name}: median {r['median_ms']:.3f} ms (min {r['min_ms']:.3f}, max {r['max_ms']:.3f})")
 print("per call:", steps, "k-th largest share:", record["kth_largest_share_of_total"], "baseline same result:", same)
-save()
-print("wrote", opt["--json"])
+measure.write_record(opt.json, record)

@@ -25,6 +25,7 @@ import torch  # noqa: E402
 
 from streetunveiler_amd.optim import SurfelAdam, densification_stats, densification_stats_torch  # noqa: E402
 from tests.optim_cases import GROUPS  # noqa: E402  (the reference's six groups: name, row shape, learning rate)
+from tools import measure  # noqa: E402
 
 COPY_RATE = 6.29e12   # B/s, float4 copy on this GPU
 
@@ -45,22 +46,7 @@ def _percentiles(v):
 
 
 def _alternate(fns, rounds, iters):
-    """{name: [ms per call, one figure per round]}, the implementations taking turns"""
-    for fn in fns.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(rounds):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ms[name].append(e0.elapsed_time(e1) / iters)
-    return ms
+    return measure.alternating_rounds(fns, rounds, iters, warmup=3)
 
 
 def main():
@@ -112,13 +98,10 @@ def main():
         print(json.dumps(row), flush=True)
         del grad, radii, state
         torch.cuda.empty_cache()
-    doc = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, copy_rate_Bps=COPY_RATE,
+    doc = dict(measure.header(), torch=torch.__version__, copy_rate_Bps=COPY_RATE,
                what="ms per call; device events around iters_per_round calls; median / p10 / p90 over the rounds; the implementations alternate "
                     "round by round in one process", results=rows)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-    print("->", args.out)
+    measure.write_record(args.out, doc)
 
 
 if __name__ == "__main__":

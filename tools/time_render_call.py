@@ -7,6 +7,7 @@ import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from streetunveiler_amd.gaussian_renderer import PipelineParams, SurfelModel, render
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tools import measure
 P, W, H, N = (int(a) for a in sys.argv[1:5]) if len(sys.argv) > 4 else (3_000_000, 1920, 1080, 10)
 dev = "cuda:0"
 cam = synthetic_camera(W, H).to(dev)
@@ -24,10 +25,5 @@ def bare():
     c, r, a = GaussianRasterizer(s)(means3D=g["means3D"], means2D=m2d, shs=g["shs"], opacities=g["opacities"], scales=g["scales"], rotations=g["rotations"])
     (c.sum() + a.sum()).backward()
 for name, fn in (("bare operator + sum losses", bare), ("render() + regulariser-style losses", full)):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(N): fn()
-    t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / N:.4f} ms fwd+bwd")
+    ms = measure.alternating_rounds({name: fn}, rounds=1, iters=N, warmup=3)[name][0]
+    print(f"{name}: {ms:.4f} ms fwd+bwd")

@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from streetunveiler_amd.gaussian_renderer import PipelineParams, SurfelModel, render, render_and_semantic, render_semantic
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
+from tools import measure
 P, W, H, dev = 3_000_000, 1920, 1080, "cuda:0"
 cam = synthetic_camera(W, H).to(dev)
 g = {k: v.to(dev).requires_grad_() for k, v in synthetic_gaussians(P, W, H).items()}
@@ -22,10 +23,5 @@ def one_call():
     o = render_and_semantic(cam, pc, pipe, bg)
     (o["render"].sum() + o["rend_dist"].sum() + o["render_semantics"].sum()).backward()
 for name, fn in (("render() + render_semantic() (rgb pass + one 6-channel pass)", two_calls), ("render_and_semantic() (one 9-channel pass)", one_call)):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(10): fn()
-    t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / 10:.3f} ms fwd+bwd")
+    ms = measure.alternating_rounds({name: fn}, rounds=1, iters=10, warmup=3)[name][0]
+    print(f"{name}: {ms:.3f} ms fwd+bwd")

@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians, synthetic_upstream_grads
+from tools import measure
 P, W, H, dev = 3_000_000, 1920, 1080, "cuda:0"
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 cam = synthetic_camera(W, H)
@@ -30,10 +31,5 @@ def two_passes():
     call(bg6[:3].contiguous(), onehot[:, :3].contiguous(), dc6[:3], True)
     call(bg6[3:].contiguous(), onehot[:, 3:].contiguous(), dc6[3:], False)
 for name, fn in (("two 3-channel passes (reference call pattern)", two_passes), ("one 6-channel pass", one_pass)):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps): fn()
-    t1.record(); torch.cuda.synchronize()
-    print(f"{name}: {t0.elapsed_time(t1) / steps:.3f} ms per fwd+bwd")
+    ms = measure.alternating_rounds({name: fn}, rounds=1, iters=steps, warmup=3)[name][0]
+    print(f"{name}: {ms:.3f} ms per fwd+bwd")

@@ -10,7 +10,6 @@ what is held before the step.  Whatever is measured is reported, a size at which
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +18,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from streetunveiler_amd import sky  # noqa: E402
+from tools import measure  # noqa: E402
 
 # (width, height, rounds of the torch baseline): small size first.  At 1920x1080 one step of the baseline gathers 268 M grid rows and its
 # backward adds as many duplicates into 128 rows, which takes seconds: it gets 3 rounds of one step; the fused path always gets --rounds.
@@ -38,7 +38,7 @@ def main():
     model = sky.SkyModel(device=dev)
     c2w = torch.eye(4)
     c2w[:3, 3] = torch.tensor([0.31, 0.62, 0.17])
-    doc = dict(device=torch.cuda.get_device_name(0), what="forward + backward of the sky image per autograd step (the loss is sum(image * g)); "
+    doc = dict(measure.header(), what="forward + backward of the sky image per autograd step (the loss is sum(image * g)); "
                "device events around `iters` steps; median / min / max over the rounds; the two implementations alternate while both have "
                "rounds left; peak_extra_bytes: the most a step allocates beyond what is held before it", results=[])
     for W, H, torch_rounds in SIZES:
@@ -64,29 +64,14 @@ def main():
             peak[k] = torch.cuda.max_memory_allocated() - held
             print(f"{W}x{H} {k}: warmed, peak extra {peak[k]} bytes", flush=True)
         step(fns["fused"])
-        ms = {k: [] for k in fns}
-        for r in range(max(rounds.values())):
-            for k, fn in fns.items():                                                # alternating
-                if r >= rounds[k]:
-                    continue
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(iters[k]):
-                    step(fn)
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1) / iters[k])
-                print(f"{W}x{H} {k} round {r}: {ms[k][-1]:.3f} ms", flush=True)
-        med = {k: statistics.median(v) for k, v in ms.items()}
-        stat = lambda k: dict(median=med[k], min=min(ms[k]), max=max(ms[k]), rounds=rounds[k], iters_per_round=iters[k])
-        row = dict(width=W, height=H, fused_ms=stat("fused"), torch_ms=stat("torch"), torch_over_fused=med["torch"] / med["fused"],
+        ms = measure.alternating_rounds({k: lambda fn=fn: step(fn) for k, fn in fns.items()}, rounds, iters, warmup=0)      # (warmed above)
+        print(f"{W}x{H} ms per step, by round:", {k: [round(t, 3) for t in v] for k, v in ms.items()}, flush=True)
+        stat = lambda k: dict(measure.stats(ms[k]), rounds=rounds[k], iters_per_round=iters[k])
+        row = dict(width=W, height=H, fused_ms=stat("fused"), torch_ms=stat("torch"), torch_over_fused=stat("torch")["median"] / stat("fused")["median"],
                    fused_peak_extra_bytes=peak["fused"], torch_peak_extra_bytes=peak["torch"])
         doc["results"].append(row)
         print(json.dumps(row), flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:                                               # after every size: what is measured is kept
-            json.dump(doc, f, indent=1)
-    print("->", args.out)
+        measure.write_record(args.out, doc)                                          # after every size: what is measured is kept
 
 
 if __name__ == "__main__":

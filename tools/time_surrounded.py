@@ -7,6 +7,7 @@ import torch
 from diff_surfel_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from streetunveiler_amd import _lib
 from streetunveiler_amd.synthetic import posed_scene, synthetic_upstream_grads
+from tools import measure
 ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?"); ap.add_argument("--gaussians", type=int, default=3_000_000); ap.add_argument("--behind", default="0,0.5,0.8")
 a = ap.parse_args()
@@ -27,12 +28,7 @@ for frac in [float(x) for x in a.behind.split(",")]:
         return r
     for _ in range(3): r = step()
     V = int((r > 0).sum())
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20): step()
-    e1.record(); torch.cuda.synchronize()
-    wall = e0.elapsed_time(e1) / 20
+    wall = measure.alternating_rounds({"step": step}, rounds=1, iters=20, warmup=0)["step"][0]      # (warmed above)
     lib.sr_set_stage_timing(1)
     for _ in range(10): step()
     torch.cuda.synchronize()

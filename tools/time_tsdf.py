@@ -9,20 +9,19 @@ rgb, median of 9 runs with the range after 2 warm-up runs, between device events
     every map from the host again on every call, and also samples a normal map it never uses (left out here).
 The baseline runs the slab in chunks of 2^22 samples (its temporaries are tens of full-length tensors per view); the chunking is inside
 its timed window, as it would be for a caller.  Writes one record to FILE (default profiles/tsdf_time.json)."""
-import json, math, os, statistics, sys
+import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from streetunveiler_amd import TsdfViews, _lib, grid_coordinates, unbounded_tsdf, unbounded_tsdf_grid, unbounded_tsdf_torch
-from streetunveiler_amd.build import source_digest
+from streetunveiler_amd import TsdfViews, grid_coordinates, unbounded_tsdf, unbounded_tsdf_grid, unbounded_tsdf_torch
 from tests import tsdf_cases as tc
+from tools import measure
 
-args = sys.argv[1:]
-opt = {"--views": "64", "--slab": "256", "--json": os.path.join(ROOT, "profiles", "tsdf_time.json")}
-for flag in list(opt):
-    if flag in args:
-        i = args.index(flag); opt[flag] = args[i + 1]; del args[i:i + 2]
-V, S, DEV, W, H, RES = int(opt["--views"]), int(opt["--slab"]), "cuda:0", 1920, 1080, 1024
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--views", type=int, default=64); ap.add_argument("--slab", type=int, default=256)
+ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "tsdf_time.json"))
+opt = ap.parse_args()
+V, S, DEV, W, H, RES = opt.views, opt.slab, "cuda:0", 1920, 1080, 1024
 assert torch.cuda.is_available(), "tools/time_tsdf.py measures on the GPU; there is no CPU path"
 
 depth, rgb, full = tc._views(tuple(360.0 * k / V for k in range(V)), 1, H, W)
@@ -42,18 +41,10 @@ def baseline(with_rgb):
 
 
 def timed(fn, warmup=2, repeats=9):
-    ms = []
-    for it in range(warmup + repeats):
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(); r = fn(); t1.record(); torch.cuda.synchronize()
-        if it >= warmup:
-            ms.append(t0.elapsed_time(t1))
-        del r
-    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "repeats": repeats}
+    return measure.stats_ms(measure.per_call_events(fn, warmup, repeats, sync_each=True))
 
 
-record = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "library": os.path.relpath(_lib.LIB_PATH, ROOT),
+record = {**measure.header(),
           "views": V, "map_size": [W, H], "samples": n, "slab_of_grid": [S, S, S, RES],
           "note": "the baseline reads maps that are already on the GPU; the reference uploads every map from the host on every call and samples "
                   "a normal map it never uses, so this setup favours the baseline",
@@ -74,6 +65,4 @@ for key, with_rgb in (("sdf_only", False), ("with_rgb", True)):
     r["fused_grid_ns_per_sample_and_view"] = round(r["fused_grid"]["median_ms"] * 1e6 / (n * V), 4)
     record[key] = r
     print(key, json.dumps(r))
-os.makedirs(os.path.dirname(os.path.abspath(opt["--json"])), exist_ok=True)
-json.dump(record, open(opt["--json"], "w"), indent=1)
-print("wrote", opt["--json"])
+measure.write_record(opt.json, record)

@@ -15,7 +15,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -24,23 +23,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from streetunveiler_amd import unveil as U  # noqa: E402
-from streetunveiler_amd.build import source_digest  # noqa: E402
+from tools import measure  # noqa: E402
 
 DEV = "cuda:0"
 REPEATS = 9
 
 
 def timed(fn, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(REPEATS):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append(1e3 * (time.perf_counter() - t0))
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+    return {k + "_ms": v for k, v in measure.stats(measure.per_call_host(fn, warmup, REPEATS)).items()}
 
 
 def street(P, F, H, W, seed=0):
@@ -114,12 +104,10 @@ def main():
         "mask_pixels_differing_from_twin": int((got["mask"] != twin["mask"]).sum()),
         "hip": timed(lambda: U.inpaint_conditions(full, bg, sky)), "float32_twin": timed(lambda: U.inpaint_conditions_torch(full, bg, sky, 0.01, 5, torch.float32))}
 
-    out = {"device": torch.cuda.get_device_name(0), "source_digest": source_digest(), "repeats": REPEATS,
+    out = {**measure.header(), "repeats": REPEATS,
            "method": "host clock around the call and a device synchronise, read-backs included; median, min and max of the repeats", "rows": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
     print(json.dumps(out, indent=1))
+    measure.write_record(args.out, out)
 
 
 if __name__ == "__main__":

@@ -14,16 +14,14 @@ import argparse
 import json
 import os
 import sys
-import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from streetunveiler_amd import voxel as V  # noqa: E402
-from streetunveiler_amd.build import source_digest  # noqa: E402
+from tools import measure  # noqa: E402
 
 DEV = "cuda:0"
 REPEATS = 9
@@ -31,16 +29,7 @@ VOXEL = 0.1
 
 
 def timed(fn, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(REPEATS):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append(1e3 * (time.perf_counter() - t0))
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+    return {k + "_ms": v for k, v in measure.stats(measure.per_call_host(fn, warmup, REPEATS)).items()}
 
 
 def peak_extra_bytes(fn):
@@ -121,17 +110,14 @@ def main():
     slab = 400.0 * min(1.0, args.loop_voxels / max(occupied, 1))
     pick = pts[:, 0] < slab
     p, c, s = pts[pick].cpu(), col[pick].cpu(), sem[pick].cpu()
-    t0 = time.perf_counter()
-    *_, n_voxels = loop_per_voxel(p, c, s, VOXEL)
-    seconds = time.perf_counter() - t0
+    kept = {}
+    seconds = measure.per_call_host(lambda: kept.update(voxels=loop_per_voxel(p, c, s, VOXEL)[-1]), 0, 1)[0] / 1e3
+    n_voxels = kept["voxels"]
     rows["loop_per_voxel"] = {"device": "cpu", "points": int(p.shape[0]), "voxels": n_voxels, "seconds": seconds, "runs": 1,
                               "ms_per_voxel": 1e3 * seconds / max(n_voxels, 1), "extrapolated": False}
-    rows["source_digest"] = source_digest()
-    rows["device"] = torch.cuda.get_device_name(0)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(rows, f, indent=1)
+    rows.update(measure.header())
     print(json.dumps(rows, indent=1))
+    measure.write_record(args.out, rows)
 
 
 if __name__ == "__main__":

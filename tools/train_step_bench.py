@@ -10,6 +10,7 @@ import torch
 from streetunveiler_amd.gaussian_renderer import SurfelModel
 from streetunveiler_amd.synthetic import synthetic_camera, synthetic_gaussians
 from streetunveiler_amd.train_pattern import fused_pattern, make_weights, one_plan_pattern
+from tools import measure
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=6); ap.add_argument("--warmup", type=int, default=2)
@@ -30,12 +31,5 @@ def step():
     (one_plan_pattern if a.pattern == "one_plan" else fused_pattern)(cam, pc, bg, w)["loss"].backward()
 
 
-for _ in range(a.warmup):
-    step()
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(a.steps):
-    step()
-e1.record(); torch.cuda.synchronize()
-print(json.dumps({"train_step_ms": round(e0.elapsed_time(e1) / a.steps, 4), "pattern": a.pattern, "steps": a.steps, "gaussians": P, "width": W, "height": H}))
+ms = measure.alternating_rounds({"step": step}, rounds=1, iters=a.steps, warmup=a.warmup)["step"][0]
+print(json.dumps({"train_step_ms": round(ms, 4), "pattern": a.pattern, "steps": a.steps, "gaussians": P, "width": W, "height": H}))
